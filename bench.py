@@ -10,10 +10,13 @@ popsize=4096, F=0.5, CR=0.9, bounds +-5.12, in-kernel Philox draws, ftol=-1 /
 xtol=0 so every step does the full work.  N>1: the same shard per GPU (weak
 scaling), one process per GPU, global best exchanged every generation.
 
-`value` = objective evaluations per second = N * popsize * (steps timed) / t, population resident in HBM
-before the timed region.  The K-step block is repeated back to back until the timed region lasts >= 2 s
-(`blocks`; K steps alone take 0.15 ms at the driver's K = 20), bracketed by barrier + synchronize; the median block
-duration (HIP events between blocks) is reported next to it.  Also in the line:
+`value` = objective evaluations per second = N * popsize * K / t and `ms_per_step` = t / K, population resident in HBM
+before the timed region.  Exactly K = --steps steps are timed: one K-step block, bracketed by HIP events on the engine
+stream, behind an untimed K-step block that keeps the device busy while the timed one is launched
+(--min-timed-seconds S > 0 repeats the block back to back until the region lasts S seconds, for profilers).
+`--dump-outputs DIR` writes what the timed steps computed -- the best row `x`, its value `fun` and the final
+`population` (a fixed, seeded sample of its rows when it exceeds 64 MB) -- as DIR/<name>.npy, float64; the run is
+seeded, so two builds can be compared output for output.  Also in the line:
 `minimize_wall` -- evals/s of a whole `minimize()` call after one warm-up call (host-side initial population
 included); `cpu_baseline` / `cpu_baseline_loky` with core count and CPU model; for N > 1 `c5` -- BASELINE config 5
 (DE n=1024, P=131072 in total = strong scaling) through both donor modes, with the number of ranks seen.
@@ -36,6 +39,7 @@ os.environ.setdefault("MKL_NUM_THREADS", "1")
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s measured float4 copy)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: (objective, n, P, strategy)
@@ -281,6 +285,28 @@ def cpu_baseline_loky(objective, n, P, strategy, budget_s=6.0):
                       f"pool started and warmed in {t_pool:.1f}s before timing), cpu model {cpu_model()}"}
 
 
+def dump_outputs(out_dir, run, st, suffix="", budget=DUMP_BYTES):
+    """What the timed path computed in its last step, as a caller of minimize() receives it: the best row `x`, its value
+    `fun` and the final population (the rows a callback sees; DE hands them back in x0) -- DIR/<name>.npy, float64, at
+    most `budget` bytes in all.  A larger population is sampled: a fixed set of rows (numpy default_rng(0), sorted)."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    X = run._population(st.it)
+    P, n = X.shape
+    x = np.asarray(run._best_row(st), dtype=np.float64)
+    fun = np.array([float(st.gfit)])
+    rows = min(P, (budget - x.nbytes - fun.nbytes - 4096) // (8 * n))  # (4096: the .npy headers)
+    if rows < P:
+        idx = np.sort(np.random.default_rng(0).choice(P, rows, replace=False))
+        X = X[torch.as_tensor(idx, device=X.device)]
+    arrays = {"x" + suffix: x, "fun" + suffix: fun, "population" + suffix: X.cpu().numpy().astype(np.float64, copy=False)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {k: list(a.shape) for k, a in arrays.items()}, "generation": int(st.it),
+            "population_rows": "all %d" % P if rows == P else "%d of %d (numpy default_rng(0) sample, sorted)" % (rows, P)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -292,8 +318,10 @@ def main():
     ap.add_argument("--no-configs", action="store_true", help="skip the C2 / C3a / C3b / C4 block")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="CPU work spent on the baseline sample")
     ap.add_argument("--kernel-timing-launches", type=int, default=400)
-    ap.add_argument("--min-timed-seconds", type=float, default=2.0,
-                    help="the K-step block is repeated until the timed region lasts this long (profilers: pass less)")
+    ap.add_argument("--min-timed-seconds", type=float, default=0.0,
+                    help="repeat the K-step block until the timed region lasts this long (default 0: exactly --steps steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (x, fun, population) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -304,9 +332,11 @@ def main():
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
+        import subprocess
+
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                                   f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                                  os.path.abspath(__file__)] + sys.argv[1:])
+                                  os.path.abspath(__file__)] + sys.argv[1:]))
 
     import torch
 
@@ -354,7 +384,6 @@ def main():
         return tt.item()
 
     MAX_BLOCKS = 1 << 20
-    MIN_TIMED_S = args.min_timed_seconds  # (the driver's GPU-busy sampler and timed-region check need seconds)
 
     def self_check(exchange, gens=3):
         """First contact with distinct devices validates itself before anything is timed (VERDICT r5 next #6c): `gens`
@@ -380,9 +409,10 @@ def main():
         return everyone[0]
 
     def measure(exchange, objective=objective, n=n, Ptotal=None, strategy=strategy, donors=os.environ.get("SX_DONORS") or "shard",
-                K=K, W=W, kernel_launches=args.kernel_timing_launches):
-        """One resident run: W warm-up steps, then blocks of K steps until >= 2 s are timed.  Ptotal None: weak
-        scaling (every GPU owns P rows of a global population of world*P; same seed on every rank)."""
+                K=K, W=W, kernel_launches=args.kernel_timing_launches, min_seconds=args.min_timed_seconds, dump=None):
+        """One resident run: W warm-up steps, then ONE timed block of K steps -- or, with min_seconds > 0, the block
+        repeated back to back until the timed region lasts that long.  Ptotal None: weak scaling (every GPU owns P rows
+        of a global population of world*P; same seed on every rank).  dump: a directory for dump_outputs()."""
         lower, upper = np.full(n, -5.12), np.full(n, 5.12)
         run = _de._DeRun(_lib.FUN_IDS[objective], lower, upper, None, 2**31 - 2, Ptotal or world * P, 0.5, 0.9, strategy,
                          None, 0.0, -1.0, False, 1.0, None, "philox", 1234, world, autorun=False, exchange=exchange,
@@ -400,37 +430,44 @@ def main():
                 run.enqueue(K)
                 primed = 2 * K
                 ctx.sync()
-                # K-step blocks, back to back, until the timed region lasts >= 2 s (every rank times the same number)
+                # the timed region: `blocks` K-step blocks (one unless min_seconds asks for more; every rank times the same
+                # number), bracketed by HIP events on the engine stream.  An untimed K-step block runs ahead of it, so the
+                # device is busy while the timed steps are launched: the region holds the K-step blocks and nothing else.
                 blocks, steps_done = 1, 0
                 while True:
                     # an event record costs the stream ~2.6 us: one every >= 200 steps (every block when K >= 200)
                     group = max(1, 200 // K)
                     evs = [torch.cuda.Event(enable_timing=True) for _ in range(blocks // group + 1)]
+                    ev_end = torch.cuda.Event(enable_timing=True)
                     barrier()
-                    t0 = time.perf_counter()
+                    run.enqueue(K)  # (untimed lead-in)
                     evs[0].record(ctx.stream)
                     for b in range(blocks):
                         run.enqueue(K)
                         if (b + 1) % group == 0:
                             evs[(b + 1) // group].record(ctx.stream)
+                    ev_end.record(ctx.stream)
                     ctx.sync()
                     barrier()
-                    t1 = time.perf_counter()
-                    steps_done += blocks * K
-                    enough = t1 - t0 >= MIN_TIMED_S or blocks >= MAX_BLOCKS
+                    steps_done += K + blocks * K
+                    dt = evs[0].elapsed_time(ev_end) * 1e-3
+                    enough = dt >= min_seconds or blocks >= MAX_BLOCKS
                     if dist is not None:
                         enough = reduce_max(0 if enough else 1, torch.int64) == 0  # all ranks or none
                     if enough:
                         break
-                    grow = int(np.ceil(1.3 * blocks * MIN_TIMED_S / max(t1 - t0, 1e-6)))
+                    grow = int(np.ceil(1.3 * blocks * min_seconds / max(dt, 1e-6)))
                     blocks = max(2 * blocks, grow)
                     if dist is not None:
                         blocks = int(reduce_max(blocks, torch.int64))
                     blocks = min(blocks, MAX_BLOCKS)
                 st = run.read_state()  # raises if a wait inside the peer exchange timed out
                 assert st.it == 1 + W + primed + steps_done, (st.it, W, K, blocks, steps_done)
+                # (N > 1: every rank writes its own shard, names suffixed _rank<r>, within an equal part of the budget)
+                dumped = (dump_outputs(dump, run, st, "" if world == 1 else "_rank%d" % rank, DUMP_BYTES // world)
+                          if dump else None)
                 block_ms = sorted(evs[g].elapsed_time(evs[g + 1]) / group for g in range(blocks // group))
-                block_ms = block_ms or [(t1 - t0) * 1e3 / blocks]  # fewer blocks than one event group
+                block_ms = block_ms or [dt * 1e3 / blocks]  # fewer blocks than one event group
 
                 # dominant kernel: HIP events on the engine stream around a replayed hipGraph of generation
                 # kernels (real generations, nothing else on the stream), average per launch
@@ -447,12 +484,11 @@ def main():
             barrier()  # no rank frees its exchange buffer while a peer may still write into it
         finally:
             run.close()
-        dt = t1 - t0
         if dist is not None:
             dt = float(reduce_max(dt, torch.float64))
         return {"run": run, "dt": dt, "steps_timed": blocks * K, "blocks": blocks,
                 "block_ms_median": block_ms[len(block_ms) // 2], "kern_ms": kern_ms, "nl": nl,
-                "kernels_per_gen": kernels_per_gen, "rows_total": Ptotal or world * P}
+                "kernels_per_gen": kernels_per_gen, "rows_total": Ptotal or world * P, "dumped": dumped}
 
     # ---- N > 1: what the first contact with a second physical GPU must not cost ----------------
     # The RCCL transport (one all-gather per generation: the library's own, exercised path) is measured FIRST and its
@@ -496,13 +532,13 @@ def main():
     transports = None
     checks = {}
     if world == 1:
-        m = measure(None)
+        m = measure(None, dump=args.dump_outputs)
     else:
         import threading
 
         threading.Thread(target=watchdog, daemon=True).start()
         checks = {"rccl": guarded("self-check rccl", 300.0, lambda: self_check("rccl"))}  # (raises: nothing valid to time)
-        m_rccl = guarded("rccl", 600.0, lambda: measure("rccl"))
+        m_rccl = guarded("rccl", 600.0, lambda: measure("rccl", dump=args.dump_outputs))
         transports = {"rccl": {"value": m_rccl["rows_total"] * m_rccl["steps_timed"] / m_rccl["dt"],
                                "ms_per_step": m_rccl["dt"] / m_rccl["steps_timed"] * 1e3}}
         m = m_rccl
@@ -531,8 +567,9 @@ def main():
             "ms_per_step": dt / m["steps_timed"] * 1e3,
             "timed": {"blocks": m["blocks"], "steps_timed": m["steps_timed"], "seconds": dt,
                       "block_ms_median": m["block_ms_median"],
-                      "note": "W warm-up steps and two untimed K-step blocks (the K-step graph is instantiated there), then the K-step block "
-                              "repeated back to back until >= 2 s are timed (one barrier + synchronize pair around the region); block_ms_median from HIP events between blocks (one event per "
+                      "note": "W warm-up steps and two untimed K-step blocks (the K-step graph is instantiated there), then one untimed "
+                              "K-step block followed by the timed K-step block (repeated back to back only under --min-timed-seconds), "
+                              "timed by HIP events on the engine stream; block_ms_median from HIP events between blocks (one event per "
                               "max(1, 200 // K) blocks, divided by that count)"},
             "higher_is_better": True,
             "scaling": "weak",
@@ -574,6 +611,8 @@ def main():
         if run.world is not None:  # (3 generations per transport before anything was timed: one answer on every rank)
             line["self_check"] = {k: {"best_f": float.fromhex(v[0]), "global_row": v[1], "generation": v[2]} for k, v in checks.items()}
         line["transport_fallback"] = transport_fallback or getattr(run, "exchange_note", None)
+        if args.dump_outputs:  # (N > 1: from the RCCL measurement; the peer-write transport computes the same)
+            line["outputs"] = (m_rccl if world > 1 else m)["dumped"]
         if c5 is not None:
             line["c5"] = c5
         return line
@@ -584,7 +623,8 @@ def main():
     c5 = None
     p2p_note = None
     if world > 1:
-        c5kw = dict(objective="rosenbrock", n=1024, Ptotal=131072, strategy="best1bin", K=20, W=10, kernel_launches=50)
+        c5kw = dict(objective="rosenbrock", n=1024, Ptotal=131072, strategy="best1bin", K=20, W=10, kernel_launches=50,
+                    min_seconds=2.0)
         c5 = {"workload": "de_rosenbrock_n1024_p131072 (total), best1bin", "n_ranks_seen": dist.get_world_size(),
               "rows_per_gpu": 131072 // world, "scaling": "strong",
               "n1_reference": "configs.C5_full_de_n1024_p131072_1gpu of the N = 1 line (profiles/r6_bench_N1.json)"}

@@ -288,13 +288,15 @@ def gpu_minimize_worker(rank, world, port, cfg, out_dir):
 
 
 def nccl_multi_gpu_worker(rank, world, port, cfg, out_dir):
-    """One rank per PHYSICAL GPU, backend nccl (= RCCL over xGMI): the deployment.  Needs >= world devices (the test
-    that uses it is skipped on one-GPU boxes)."""
+    """One rank per PHYSICAL GPU, backend nccl (= RCCL over xGMI): the deployment.  Needs >= world devices; with world 1
+    (a one-GPU box) the single rank is forced onto the sharded path, so the exchange is still the one under test."""
     import torch
     import torch.distributed as dist
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    if world == 1:
+        os.environ["SX_FORCE_SHARDED"] = "1"
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     os.environ["TORCH_NCCL_TRACE_BUFFER_SIZE"] = os.environ["TORCH_FR_BUFFER_SIZE"] = "256"
     torch.cuda.set_device(rank)

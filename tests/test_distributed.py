@@ -44,6 +44,11 @@ def _spawn(fn, world, cfg):
                 raise
 
 
+# Every rank is a process with a GPU open, and so is the pytest process itself; the shared test machines allow at most six
+# such processes at once, so a test runs at most four ranks (the node's eight ranks run as four, on one GPU or on four).
+MAX_RANKS = 4
+
+
 def _sharded_oracle(cfg, world):
     n = cfg["n"]
     return oe.run_de_sharded(oracle.OBJECTIVES["rosenbrock"], np.full(n, -5.12), np.full(n, 5.12),
@@ -171,11 +176,11 @@ def test_sharded_de_on_gpu_matches_oracle(world, exchange):
 
 
 @pytest.mark.gpu
-def test_c5_full_size_sharded_over_eight_ranks_matches_oracle():
-    """BASELINE config 5 in its sharded form AT SIZE: DE n=1024, P=131072 over 8 ranks (16384 rows each; here the
-    ranks share the one test GPU, so the records travel between kernels: exchange="rccl"), shard-local donors, the
-    initial evaluation + 2 generations == oracle.run_de_sharded bit for bit on every rank (x, f, nit, status)."""
-    _check_sharded_de(8, _de_cfg(1024, 131072, 3, 2026, "rccl"))
+def test_c5_full_size_sharded_over_four_ranks_matches_oracle():
+    """BASELINE config 5 in its sharded form AT SIZE: DE n=1024, P=131072 over MAX_RANKS = 4 ranks (32768 rows
+    each; the ranks share the one test GPU, so the records travel between kernels: exchange="rccl"), shard-local donors,
+    the initial evaluation + 2 generations == oracle.run_de_sharded bit for bit on every rank (x, f, nit, status)."""
+    _check_sharded_de(MAX_RANKS, _de_cfg(1024, 131072, 3, 2026, "rccl"))
 
 
 @pytest.mark.gpu
@@ -202,10 +207,11 @@ def test_p2p_exchange_cases(case):
     (2, dict(n=13, P=40, gens=20, seed=3, strategy="rand2bin", constraints="Random")),   # 5 donors, two Philox calls
     (2, dict(n=300, P=48, gens=12, seed=4, strategy="rand1bin")),                         # whole-wave rows
     (4, dict(n=128, P=256, gens=60, seed=5)),                                             # bounds-test-free kernel
-    # BASELINE config 5's row length and rank count; the population is cut to what 8 ranks can keep co-resident on the
-    # ONE test GPU (ranks that share a device must all fit at once: a rank's waiting workgroups may otherwise fill it
-    # before a peer's record-pushing workgroup is resident -- with one GPU per rank that cannot happen)
-    (8, dict(n=1024, P=2048, gens=4, seed=6)),
+    # BASELINE config 5's row length over as many ranks as may share the test GPU; the population is cut to what the
+    # ranks can keep co-resident on the ONE test GPU (ranks that share a device must all fit at once: a rank's waiting
+    # workgroups may otherwise fill it before a peer's record-pushing workgroup is resident -- with one GPU per rank that
+    # cannot happen)
+    (MAX_RANKS, dict(n=1024, P=2048, gens=4, seed=6)),
     (2, dict(n=3000, P=24, gens=6, seed=12)),    # rows of 2049 ... 4096 elements (refused in round 5)
     (4, dict(n=24, P=130, gens=12, seed=13)),    # 33 + 33 + 33 + 31 rows: the owner of a donor row is row // 33
 ])
@@ -230,9 +236,9 @@ def test_global_donors_reproduce_the_unsharded_run(world, case):
 @pytest.mark.gpu
 @pytest.mark.parametrize("method,extra", [("de", {"exchange": "p2p"}), ("de", {"exchange": "p2p", "donors": "global"}),
                                           ("de", {"exchange": "rccl"}), ("pso", {})])
-def test_eight_ranks_share_one_gpu(method, extra):
-    """The full node's world size (8 ranks: one pushing wavefront per peer, 32 header words per wait) on the one
-    test GPU, DE through both transports and with global donors, PSO through the exchange kernel."""
+def test_four_ranks_share_one_gpu(method, extra):
+    """As many ranks as may share the one test GPU (MAX_RANKS = 4: one pushing wavefront per peer, 16 header words
+    per wait), DE through both transports and with global donors, PSO through the exchange kernel."""
     from _dist_workers import gpu_minimize_worker
 
     n, P, gens, seed = 128, 256, 25, 41
@@ -241,14 +247,14 @@ def test_eight_ranks_share_one_gpu(method, extra):
     if method == "pso":
         cfg["options"].pop("exchange")
         cfg["env"] = {"SX_EXCHANGE": "p2p"}
-    out = _spawn(gpu_minimize_worker, 8, cfg)
+    out = _spawn(gpu_minimize_worker, MAX_RANKS, cfg)
     opts = {k: v for k, v in cfg["options"].items() if k not in ("exchange", "donors")}
     if method == "de" and extra.get("donors") != "global":
-        ref = _de_reference(cfg, 8)
+        ref = _de_reference(cfg, MAX_RANKS)
     else:
         ref = oracle.minimize("rosenbrock", [[-5.12, 5.12]] * n, method=method, options=dict(opts, updating="deferred"),
                               rng="philox")
-    for r in range(8):
+    for r in range(MAX_RANKS):
         fun, nit, nfev, status = np.load(os.path.join(out, f"meta_{r}.npy"))
         assert (fun, nit, nfev, status) == (ref.fun, ref.nit, ref.nfev, ref.status)
         assert np.array_equal(np.load(os.path.join(out, f"x_{r}.npy")), ref.x)
@@ -557,31 +563,35 @@ def _n_gpus():
         return 0
 
 
+def _physical_world():
+    """One rank per physical GPU (RCCL refuses two ranks on one device): 1, 2 or 4 ranks, at most MAX_RANKS."""
+    world = max(1, min(_n_gpus(), MAX_RANKS))
+    return 1 << (world.bit_length() - 1)
+
+
 @pytest.mark.gpu
-@pytest.mark.skipif(_n_gpus() < 2, reason="needs two physical GPUs (RCCL refuses two ranks on one device)")
 @pytest.mark.parametrize("exchange", ["rccl", "p2p"])
 @pytest.mark.parametrize("gens", [9, 130])
 def test_two_physical_gpus_rccl_and_peer_exchange(exchange, gens):
-    """The first box with more than one GPU runs this: one rank per device, process group nccl (RCCL over xGMI), the
-    record exchange through RCCL all-gathers ("rccl": captured into a graph from 50 generations on) and through peer
-    writes into IPC-mapped HBM across a real link ("p2p", after its probe) -- == oracle.run_de_sharded bit for bit on
-    every rank.  Everywhere else these transports are only ever exercised with ranks sharing one device."""
+    """One rank per device, process group nccl (RCCL over xGMI), the record exchange through RCCL all-gathers ("rccl":
+    captured into a graph from 50 generations on) and through peer writes into IPC-mapped HBM across a real link ("p2p",
+    after its probe) -- == oracle.run_de_sharded bit for bit on every rank.  A box with two or more GPUs runs two or four
+    ranks; on a one-GPU box the single rank still takes the sharded path with both transports (nccl_multi_gpu_worker)."""
     from _dist_workers import nccl_multi_gpu_worker
 
-    world = min(_n_gpus(), 8)
-    world = 1 << (world.bit_length() - 1)  # 2, 4 or 8
+    world = _physical_world()
     _check_sharded_de(world, _de_cfg(24, 64 * world, gens, 2024 + gens, exchange), worker=nccl_multi_gpu_worker)
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(_n_gpus() < 2, reason="needs two physical GPUs")
 @pytest.mark.parametrize("method", ["pso", "cpso"])
 def test_two_physical_gpus_pso_is_exact(method):
     """PSO / CPSO sharded over physical GPUs (nccl process group; best record by peer writes or all-gather, the
-    restart's [pbestfit | radii] gather over RCCL) == the unsharded oracle run."""
+    restart's [pbestfit | radii] gather over RCCL) == the unsharded oracle run.  Two ranks on a box with two or more GPUs,
+    one (sharded path) on a one-GPU box."""
     from _dist_workers import nccl_multi_gpu_worker
 
-    world = 2
+    world = min(2, _physical_world())
     opts = {"maxiter": 70, "popsize": 256, "seed": 5, "ftol": -1.0, "xtol": 0.0}
     cfg = {"n": 16, "objective": "sphere", "method": method, "options": opts}
     out = _spawn(nccl_multi_gpu_worker, world, cfg)

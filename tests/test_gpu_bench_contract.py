@@ -30,7 +30,9 @@ def test_bench_line_has_the_contract_fields():
     assert d["vs_baseline"] is None and d["config"]["workload"] == "de_rosenbrock_n128_p4096"
     assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
     t = d["timed"]
-    assert t["seconds"] >= 2.0 and t["steps_timed"] == t["blocks"] * 150 and t["block_ms_median"] > 0
+    # --steps is the number of timed steps: one timed block of exactly 150 steps
+    assert t["blocks"] == 1 and t["steps_timed"] == 150 and t["seconds"] > 0 and t["block_ms_median"] > 0
+    assert abs(d["ms_per_step"] - t["seconds"] * 1e3 / 150) < 1e-9 * d["ms_per_step"]
     w = d["minimize_wall"]
     # (round 3: the initial population is drawn on the device -- a whole minimize() call is within ~10 % of the resident
     #  loop; round 2, host-side Latin hypercube: 62 %)
@@ -72,6 +74,43 @@ def test_bench_other_workload_and_smoke():
     import __graft_entry__
 
     __graft_entry__.smoke()
+
+
+def test_bench_dump_outputs_are_reproducible(tmp_path):
+    """--dump-outputs DIR: what the timed steps computed (best row, its value, the final population) as float64 .npy files;
+    the run is seeded, so a second run with the same arguments writes the same arrays bit for bit."""
+    import numpy as np
+
+    from oracle.objectives import OBJECTIVES
+
+    args = ("--steps", "40", "--warmup", "10", "--no-cpu-baseline", "--no-configs", "--no-minimize-wall")
+    runs = []
+    for k in range(2):
+        d = _run_bench(*args, "--dump-outputs", str(tmp_path / str(k)))
+        assert d["steps"] == 40 and d["timed"]["steps_timed"] == 40 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / str(k)))
+        assert files == ["fun.npy", "population.npy", "x.npy"] and d["outputs"]["population_rows"] == "all 4096"
+        runs.append({f[:-4]: np.load(tmp_path / str(k) / f) for f in files})
+    a, b = runs
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["population"].shape == (4096, 128) and a["x"].shape == (128,) and a["fun"].shape == (1,)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.any(np.all(a["population"] == a["x"], axis=1))  # the best row is a row of the final population
+    assert np.isclose(OBJECTIVES["rosenbrock"](a["x"][None])[0], a["fun"][0], rtol=1e-12, atol=0)
+
+
+def test_bench_dump_outputs_sample_a_large_population(tmp_path):
+    """A population above the 64 MB budget is written as a fixed sample of its rows."""
+    import numpy as np
+
+    d = _run_bench("--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-configs", "--no-minimize-wall",
+                   "--workload", "de_rosenbrock_n1024_p131072", "--dump-outputs", str(tmp_path))
+    assert d["timed"]["steps_timed"] == 4
+    total = sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path))
+    assert total <= 64 << 20
+    pop = np.load(tmp_path / "population.npy")
+    assert pop.shape[1] == 1024 and 1000 < pop.shape[0] < 131072 and pop.dtype == np.float64
+    assert d["outputs"]["population_rows"].startswith("%d of 131072" % pop.shape[0])
 
 
 def test_bench_two_ranks_emits_the_c5_strong_scaling_figures():

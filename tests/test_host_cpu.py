@@ -357,8 +357,15 @@ def test_api_surface_and_validation():
         got = pool.executor().submit(_common._eval_block, np.sum, rows, ()).result()
         assert np.array_equal(got, rows.sum(axis=1))
         pool.close()
-    with pytest.raises(NoDeviceError):
-        sa.optimize.minimize(lambda x: float(np.sum(x)), b, options={"backend": "hip", "updating": "deferred"})
+    import torch
+
+    host_opts = {"backend": "hip", "updating": "deferred", "maxiter": 3, "popsize": 8, "seed": 0}
+    if torch.cuda.is_available():  # (the suite on a GPU box: accepted, and evaluated on the host between the kernels)
+        res = sa.optimize.minimize(lambda x: float(np.sum(x)), b, options=host_opts)
+        assert 1 <= res.nit <= 3 and res.fun == float(np.sum(res.x))
+    else:
+        with pytest.raises(NoDeviceError):
+            sa.optimize.minimize(lambda x: float(np.sum(x)), b, options=host_opts)
     with pytest.raises(ValueError):
         sa.optimize.minimize(f, [-1, 1])
     with pytest.raises(ValueError):
