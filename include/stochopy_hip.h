@@ -466,7 +466,7 @@ typedef struct sx_cma_state {
     int32_t status;     /* SX_STATUS_NONE while running, else the reference's status (-8 .. 1)         */
     int32_t done;       /* 1 once a stopping rule fired                                                */
     int64_t stop_it;    /* generation at which it fired                                                */
-    double reserved[6];
+    double reserved[6]; /* [0..4] VD-CMA's model scalars; [5] arfitness.argmin() of the last generation    */
 } sx_cma_state;
 
 typedef struct sx_cma_args {
@@ -503,6 +503,10 @@ typedef struct sx_cma_args {
 } sx_cma_args;
 
 int sx_cmaes_generation(const sx_cma_args *a, int64_t gen, int do_eigh, void *stream);
+/* The ranking step of the device-resident CMA-ES / VD-CMA generations on its own: order = np.argsort(fit, kind="stable")
+ * (NaN last, ties by lower index); with besthist, state (an sx_cma_state) gets best_row / fbest = order[0] and
+ * reserved[5] = np.argmin(fit) (the first NaN if any), besthist[gen - 1] = fit[order[0]].  Nothing happens once state.done. */
+int sx_cma_rank(const double *fit, int64_t P, int64_t *order, void *state, double *besthist, int64_t gen, void *stream);
 /* The same generation in two steps for candidates sharded over ranks (workers > 1; what the reference's parallel backends
  * shard: _common.py:58-72).  stage 0: this rank's candidates [row0, row0 + rows) -- Philox normals keyed by the global
  * row, sampling GEMM, objective -- into arx_loc (rows,n) / fit_loc (rows); the caller

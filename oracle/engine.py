@@ -298,7 +298,8 @@ def run_pso(fobj, lower, upper, x0, stream, callback=None, maxiter=100, popsize=
             break
         if gamma:
             # d = X - gbest; per-row sqrt(dot) exactly as np.linalg.norm does for 1-D input
-            rad = (max(np.linalg.norm(X[i] - gbest) for i in range(P)) / np.sqrt(4.0 * n)) if P <= 32768 else swarm_radius(X, gbest, n)
+            # (np.max as the reference: it propagates NaN, where the builtin max keeps or drops one by its position)
+            rad = (np.max([np.linalg.norm(X[i] - gbest) for i in range(P)]) / np.sqrt(4.0 * n)) if P <= 32768 else swarm_radius(X, gbest, n)
             if rad < delta:
                 nw = restart_count(it, maxiter, P, gamma)
                 if nw > 0:

@@ -52,7 +52,10 @@ __device__ __forceinline__ bool key_less(double a, double b) { return a < b || (
 // number of keys in front of an element is the population count of the wave's votes (one comparison per 64 keys and
 // element instead of 64; round 3: 25.6 -> a few us at P = 1024, where the old form kept 16 workgroups busy with 256
 // serial comparisons per thread).
-// besthist == NULL: ranking only (the raw fitness behind Penalize's percentiles): no best row, no history entry
+// besthist == NULL: ranking only (the raw fitness behind Penalize's percentiles): no best row, no history entry.
+// The history entry of return_all with 0 rows is arfitness.argmin() (cmaes/_cmaes.py:267), not arindex[0]: they differ
+// when a NaN is present (argsort puts it last, argmin takes the first).  The row that no other row precedes in
+// argmin's order (sx_device.hpp best_before) goes to state->reserved[5].
 constexpr int kRankPerWave = 4;
 __global__ __launch_bounds__(256) void cma_rank_kernel(const double *__restrict__ fit, int64_t P,
                                                        int64_t *__restrict__ order, sx_cma_state *state,
@@ -62,10 +65,12 @@ __global__ __launch_bounds__(256) void cma_rank_kernel(const double *__restrict_
     if (state->done) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * kRankPerWave;
+    const bool hist = besthist != nullptr;
     double fi[kRankPerWave];
     int cnt[kRankPerWave];
+    bool beaten[kRankPerWave];  // some row comes first in argmin's order
 #pragma unroll
-    for (int u = 0; u < kRankPerWave; ++u) fi[u] = i0 + u < P ? fit[i0 + u] : 0.0, cnt[u] = 0;
+    for (int u = 0; u < kRankPerWave; ++u) fi[u] = i0 + u < P ? fit[i0 + u] : 0.0, cnt[u] = 0, beaten[u] = false;
     for (int64_t c0 = 0; c0 < P; c0 += CH) {
         const int len = (int)(P - c0 < CH ? P - c0 : CH);
         __syncthreads();
@@ -80,6 +85,7 @@ __global__ __launch_bounds__(256) void cma_rank_kernel(const double *__restrict_
             for (int u = 0; u < kRankPerWave; ++u) {
                 const bool front = in && (key_less(fk, fi[u]) || (!key_less(fi[u], fk) && kk < i0 + u));
                 cnt[u] += (int)__popcll(__ballot(front));
+                if (hist) beaten[u] |= __ballot(in && (best_before(fk, fi[u]) || (best_tie(fk, fi[u]) && kk < i0 + u))) != 0ull;
             }
         }
     }
@@ -88,11 +94,12 @@ __global__ __launch_bounds__(256) void cma_rank_kernel(const double *__restrict_
         if (lane == u && i0 + u < P) {
             const int64_t rank = cnt[u];
             order[rank] = i0 + u;
-            if (rank == 0 && besthist != nullptr) {
+            if (rank == 0 && hist) {
                 state->best_row = i0 + u;
                 state->fbest = fi[u];
                 besthist[gen - 1] = fi[u];
             }
+            if (hist && !beaten[u]) state->reserved[5] = (double)(i0 + u);
         }
     }
 }
@@ -134,7 +141,7 @@ __global__ __launch_bounds__(256) void cma_history_kernel(const sx_cma_args a, i
     if (t >= rows * n) return;
     const int64_t r = t / n;
     const int e = (int)(t % n);
-    const int64_t src = a.hist_rows > 0 ? r : state->best_row;
+    const int64_t src = a.hist_rows > 0 ? r : (int64_t)state->reserved[5];  // (argmin, see cma_rank_kernel)
     double x = a.arx[src * n + e];
     if (a.pen_ws != nullptr) x = fmin(fmax(x, -1.0), 1.0);  // Penalize: the caller sees the clipped points (:238-256)
     a.hist_x[((gen - 1) * rows + r) * n + e] = x * a.xstd[e] + a.xm[e];
@@ -535,6 +542,12 @@ int cma_candidates(const sx_cma_args *a, int64_t gen, int64_t row0, int64_t rows
 }
 int cma_model_update(const sx_cma_args *a, int64_t gen, int do_eigh, void *stream, int phase = -1, int r0 = 0, int r1 = 0);
 }  // namespace
+
+extern "C" int sx_cma_rank(const double *fit, int64_t P, int64_t *order, void *state, double *besthist, int64_t gen,
+                           void *stream) {
+    SX_REQUIRE(fit && order && state && P >= 1 && (besthist == nullptr || gen >= 1), "sx_cma_rank: bad arguments");
+    return sx::cma_rank_launch(fit, P, order, (sx_cma_state *)state, besthist, gen, stream);
+}
 
 extern "C" int sx_cmaes_generation(const sx_cma_args *a, int64_t gen, int do_eigh, void *stream) {
     if (int rc = check_cma_args(a, gen)) return rc;

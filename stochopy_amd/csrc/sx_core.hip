@@ -807,16 +807,17 @@ __device__ __forceinline__ void scan_records_n(const double *__restrict__ part_f
             f[u] = k < npart ? part_f[k] : __builtin_huge_val();
             i[u] = k < npart ? part_i[k] : INT64_MAX;
         }
-        // this trip's minimum (a tree), then the first record that holds it (k grows with u), then one lexicographic
-        // step into the running pair: a chain of 8 compare-and-select steps otherwise
+        // this trip's minimum in np.argmin's order (a tree), then the first record that holds it (k grows with u), then
+        // one lexicographic step into the running pair: a chain of 8 compare-and-select steps otherwise
         double m = f[0];
 #pragma unroll
-        for (int u = 1; u < kScan; ++u) m = fmin(m, f[u]);  // (the minimum is the same in any order)
-        int64_t first = i[0];  // (all NaN: the first record, as a sequential scan)
+        for (int u = 1; u < kScan; ++u) m = best_min(m, f[u]);  // (the minimum is the same in any order)
+        int64_t first = i[0];
+        double fm = f[0];  // (its own bits: the sign of a zero)
 #pragma unroll
         for (int u = kScan - 1; u >= 0; --u)
-            if (f[u] == m) first = i[u];
-        argmin_combine(bf, bi, m, first);
+            if (best_tie(f[u], m)) first = i[u], fm = f[u];
+        argmin_combine(bf, bi, fm, first);
     }
 }
 // 8 records per thread and trip; all of config 5 on one GPU (131 072 rows = 16 384 records, 64 per thread) 32: two trips
@@ -1071,7 +1072,7 @@ __global__ __launch_bounds__(kFinalThreads) void gather_finalize_kernel(const do
     for (int w = 0; w < world; ++w) {
         const double f = records[w * stride];
         const int64_t gi = (int64_t)records[w * stride + 1];
-        if (f < bf || (f == bf && gi < bi)) {
+        if (best_before(f, bf) || (best_tie(f, bf) && gi < bi)) {  // (np.argmin's order: a NaN record wins)
             bf = f;
             bi = gi;
             best = w;

@@ -446,12 +446,26 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
         for (int u = 0; u < kRecPerLane / 2; ++u) lm[u] = fmin(pfv[2 * u], pfv[2 * u + 1]);
         const double lmin = fmin(fmin(lm[0], lm[1]), fmin(lm[2], lm[3]));
         bf = wave_min_f64(lmin);
-        rec_t br = piv[0];  // (all NaN: record 0, as a sequential scan would)
+        rec_t br = piv[0];
+        double bv = pfv[0];
 #pragma unroll
         for (int u = kRecPerLane - 1; u >= 0; --u)
-            if (pfv[u] == bf) br = piv[u];
-        const unsigned long long hit = __ballot(lmin == bf);
+            if (pfv[u] == bf) br = piv[u], bv = pfv[u];
+        unsigned long long hit = __ballot(lmin == bf);
+        // np.argmin's order: a NaN record wins.  fmin drops NaN, so NaN is looked for beside the chain (one ballot), and
+        // the (rare) NaN case takes a branch of its own
+        bool lnan = false;
+#pragma unroll
+        for (int u = 0; u < kRecPerLane; ++u) lnan |= is_nan(pfv[u]);
+        const unsigned long long nanl = __ballot(lnan);
+        if (nanl) {
+            hit = nanl;
+#pragma unroll
+            for (int u = kRecPerLane - 1; u >= 0; --u)
+                if (is_nan(pfv[u])) br = piv[u], bv = pfv[u];
+        }
         const int src = hit ? (int)__ffsll((long long)hit) - 1 : 0;
+        bf = readlane_f64(bv, src);
         if (LPR == kWave) {
             bi = (int64_t)__builtin_amdgcn_readlane((int)br, src);
         } else {

@@ -1048,9 +1048,21 @@ __device__ __forceinline__ void row_reduce_long(const double *U, int l, double &
     sb = (TWO && !BMUL) ? 0.0 + leafB[0] : leafB[0];
 }
 
-// lexicographic (value, index) minimum = np.argmin's first-minimum rule
+// Order of objective values for the best row, np.argmin's: any NaN (whatever its sign bit) before everything, then <,
+// then the lower index.  (Ranking -- np.argsort -- puts NaN last instead: key_less in sx_cma_loop.hip, sort_key in sx_pso.hip.)
+__device__ __forceinline__ bool is_nan(double v) { return v != v; }
+// a strictly before b, indices aside
+__device__ __forceinline__ bool best_before(double a, double b) { return a < b || (is_nan(a) && !is_nan(b)); }
+// a and b tie (-0.0 == 0.0, NaN == NaN): the lower index decides
+__device__ __forceinline__ bool best_tie(double a, double b) { return a == b || (is_nan(a) && is_nan(b)); }
+// the earlier of two values in that order (ties: a); NaN propagates
+__device__ __forceinline__ double best_min(double a, double b) { return best_before(b, a) ? b : a; }
+// NaN-propagating maximum (np.max): the swarm radius
+__device__ __forceinline__ double max_nan(double a, double b) { return (b > a || is_nan(b)) ? b : a; }
+
+// lexicographic (value, index) minimum in that order = np.argmin's first-minimum rule, first NaN included
 __device__ __forceinline__ void argmin_combine(double &f, int64_t &i, double f2, int64_t i2) {
-    if (f2 < f || (f2 == f && i2 < i)) {
+    if (best_before(f2, f) || (best_tie(f2, f) && i2 < i)) {
         f = f2;
         i = i2;
     }
@@ -1058,7 +1070,8 @@ __device__ __forceinline__ void argmin_combine(double &f, int64_t &i, double f2,
 
 constexpr int kDppRowMirror = 0x140;  // row_mirror: lane i <-> 15-i inside each 16 lanes
 
-// minimum over the 64 lanes, returned to every lane: four DPP steps + four readlanes (no LDS traffic)
+// minimum over the 64 lanes, returned to every lane: four DPP steps + four readlanes (no LDS traffic).  fmin drops a NaN
+// lane: the argmin reductions below look for NaN with one ballot beside this chain (NaN is rare; the chain stays short)
 __device__ __forceinline__ double wave_min_f64(double v) {
     v = fmin(v, dpp_f64<kDppXor1>(v));
     v = fmin(v, dpp_f64<kDppXor2>(v));
@@ -1067,13 +1080,22 @@ __device__ __forceinline__ double wave_min_f64(double v) {
     return fmin(fmin(readlane_f64(v, 0), readlane_f64(v, 16)), fmin(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
 
-// maximum over the 64 lanes, returned to every lane
+// lanes that hold the wave's best value in np.argmin's order: every NaN lane if there is one, else the lanes equal to
+// the fmin minimum m (-0.0 == 0.0)
+__device__ __forceinline__ unsigned long long best_lanes(double f, double m, bool in = true) {
+    const unsigned long long nan = __ballot(in && is_nan(f));
+    return nan ? nan : __ballot(in && f == m);
+}
+
+// maximum over the 64 lanes, returned to every lane; NaN propagates (np.max)
 __device__ __forceinline__ double wave_max_f64(double v) {
+    const bool nan = __ballot(is_nan(v)) != 0ull;
     v = fmax(v, dpp_f64<kDppXor1>(v));
     v = fmax(v, dpp_f64<kDppXor2>(v));
     v = fmax(v, dpp_f64<kDppHalfMirror>(v));
     v = fmax(v, dpp_f64<kDppRowMirror>(v));
-    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+    const double m = fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+    return nan ? __builtin_nan("") : m;
 }
 
 // row_sum<64>'s butterfly (v += lane ^ 1, ^ 2, ^ 4, ^ 8, ^ 16, ^ 32) without LDS traffic.  After the step with lane ^ k both
@@ -1118,12 +1140,11 @@ __device__ __forceinline__ void st_stream(T *p, T v) {
 }
 
 __device__ __forceinline__ void wave_argmin_ordered(double &f, int64_t &i) {
-    const double m = wave_min_f64(f);
-    const unsigned long long mask = __ballot(f == m);
-    const int src = mask ? (int)__ffsll((long long)mask) - 1 : 0;  // all NaN: lane 0, as a sequential scan would
+    const unsigned long long mask = best_lanes(f, wave_min_f64(f));
+    const int src = mask ? (int)__ffsll((long long)mask) - 1 : 0;
     const int lo = __builtin_amdgcn_readlane((int)(i & 0xffffffffll), src);
     const int hi = __builtin_amdgcn_readlane((int)(i >> 32), src);
-    f = m;
+    f = readlane_f64(f, src);  // the winner's own bits (the sign of a zero, of a NaN)
     i = ((int64_t)hi << 32) | (int64_t)(unsigned)lo;
 }
 
@@ -1154,11 +1175,14 @@ __device__ __forceinline__ int64_t wave_min_i64(int64_t v) {
 
 // (min f, smallest index that holds it) over the wave for ANY assignment of indices to lanes, in every lane: the
 // minimum value, then the minimum index among the lanes that hold it -- two DPP reductions instead of six rounds of
-// ds_bpermute exchanges.  (All NaN: index 0, as np.argmin.)
+// ds_bpermute exchanges -- and the value bits from the lane that holds that index.  (No real index: index 0.)
 __device__ __forceinline__ void wave_argmin_all(double &f, int64_t &i) {
     const double m = wave_min_f64(f);
-    const int64_t r = wave_min_i64(f == m ? i : INT64_MAX);
-    f = m;
+    const bool hit = __ballot(is_nan(f)) ? is_nan(f) : f == m;  // (best_lanes, per lane)
+    const int64_t r = wave_min_i64(hit ? i : INT64_MAX);
+    const unsigned long long own = __ballot(hit && i == r);
+    const int src = own ? (int)__ffsll((long long)own) - 1 : 0;
+    f = readlane_f64(f, src);
     i = r == INT64_MAX ? 0 : r;
 }
 

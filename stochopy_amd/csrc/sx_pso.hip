@@ -25,10 +25,11 @@ using namespace sx;
 
 namespace {
 
-// order-preserving map double -> uint64 (larger double <=> larger key)
+// order-preserving map double -> uint64 (larger double <=> larger key); every NaN, whatever its sign bit, is the largest
+// key, as np.argsort puts NaN last (the restart re-seeds NaN particles first, cpso/_cpso.py:420)
 __device__ __forceinline__ unsigned long long sort_key(double f) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(f);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return is_nan(f) ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 // FULL: n == 4 * LPR (64, 128 or 256 -- BASELINE config 3): the row length is a compile-time constant, a row is exactly
@@ -157,13 +158,22 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && !CHAIN
 #pragma unroll
             for (int u = 1; u < kChainRecPerThread; ++u)
                 if (pfv[u] < bf) bf = pfv[u], brec = piv[u];  // (slices are in row order: strict < keeps the first)
+            bool lnan = false;
+#pragma unroll
+            for (int u = 0; u < kChainRecPerThread; ++u) lnan |= is_nan(pfv[u]);
+            if (__ballot(lnan)) {  // (rare) np.argmin's order: the first NaN record wins
+                bf = pfv[0], brec = piv[0];
+#pragma unroll
+                for (int u = 1; u < kChainRecPerThread; ++u)
+                    if (best_before(pfv[u], bf)) bf = pfv[u], brec = piv[u];
+            }
             wave_argmin_ordered(bf, brec);
             if (id.lane == 0) s_wf[id.wave] = bf, s_wi[id.wave] = brec;
             __syncthreads();
             bf = s_wf[0], brec = s_wi[0];
             const int nw = (int)(blockDim.x >> 6);
             for (int wv = 1; wv < nw; ++wv)
-                if (s_wf[wv] < bf) bf = s_wf[wv], brec = s_wi[wv];
+                if (best_before(s_wf[wv], bf)) bf = s_wf[wv], brec = s_wi[wv];  // (waves in row order: strict keeps the first)
             int status = SX_STATUS_NONE;
             if (it_held >= 2) {  // the reference does not test the initial swarm (cpso/_cpso.py:219-240)
                 if (bf <= a.ftol)
@@ -784,7 +794,7 @@ __global__ __launch_bounds__(kSelThreads) void pso_restart_select_kernel(const s
     double m = 0.0;
     for (int64_t k = tid; k < npart; k += kSelThreads) {
         const unsigned sg = nseg == 1 ? 0u : (unsigned)k / unp;
-        m = fmax(m, part_r[(int64_t)sg * seg_stride + ((unsigned)k - sg * unp)]);
+        m = max_nan(m, part_r[(int64_t)sg * seg_stride + ((unsigned)k - sg * unp)]);
     }
     if (done) {
         if (tid == 0) out[0] = 0;
@@ -795,7 +805,7 @@ __global__ __launch_bounds__(kSelThreads) void pso_restart_select_kernel(const s
     __syncthreads();
     m = smax[0];
 #pragma unroll
-    for (int k = 1; k < kSelThreads / kWave; ++k) m = fmax(m, smax[k]);
+    for (int k = 1; k < kSelThreads / kWave; ++k) m = max_nan(m, smax[k]);
     const double radius = m / sqrt(4.0 * (double)a.n);
     int64_t nw = 0;
     if (radius < delta) {
@@ -866,7 +876,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
                     ac += d * d;
                 }
                 ac = sqrt(row_sum<LPR>(ac));
-                if (j0 + (int64_t)q * NW * RPW < r1) mx = fmax(mx, ac);
+                if (j0 + (int64_t)q * NW * RPW < r1) mx = max_nan(mx, ac);
             }
         }
         mx = wave_max_f64(mx);
@@ -874,7 +884,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
         if (lane == 0) sf[wv] = mx;
         __syncthreads();
         double m = sf[0];
-        for (int k = 1; k < NW; ++k) m = fmax(m, sf[k]);
+        for (int k = 1; k < NW; ++k) m = max_nan(m, sf[k]);
         return m;
     };
     const int64_t per_slice = (a.P + kPostHelpers) / (kPostHelpers + 1);
@@ -928,7 +938,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             argmin_combine(bf, bi, f[u], i[u]);
-            rold = fmax(rold, r[u]);
+            rold = max_nan(rold, r[u]);
         }
     }
     const int done0 = a.state->done;
@@ -954,7 +964,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
     if (lane == 0) sf[wv] = rold;
     __syncthreads();
     double r = sf[0];
-    for (int k = 1; k < NW; ++k) r = fmax(r, sf[k]);
+    for (int k = 1; k < NW; ++k) r = max_nan(r, sf[k]);
     r = sqrt(r);  // (the generation kernel leaves squared radii)
     __syncthreads();
     // dx = ||g_old - pbest[best]||_2, thread t < 256 the elements t, t + 256, ... (n <= 256: one each), then the wave, then the waves
@@ -1070,7 +1080,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
                         __HIP_MEMORY_SCOPE_AGENT));
                 else if (r0 < r1)
                     mh = slice_radius(r0, r1, src);  // (a helper that never answered: its slice here)
-                mall = fmax(mall, mh);
+                mall = max_nan(mall, mh);
             }
             m = mall;
         } else {
@@ -1099,14 +1109,14 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
                     ac += d * d;
                 }
                 ac = sqrt(row_sum<LPR>(ac));
-                if (j0 + (int64_t)q * NW * RPW < total) mx = fmax(mx, ac);
+                if (j0 + (int64_t)q * NW * RPW < total) mx = max_nan(mx, ac);
             }
         }
         mx = wave_max_f64(mx);
         if (lane == 0) sf[wv] = mx;
         __syncthreads();
         m = sf[0];
-        for (int k = 1; k < NW; ++k) m = fmax(m, sf[k]);
+        for (int k = 1; k < NW; ++k) m = max_nan(m, sf[k]);
         }
     }
     const double radius = m / sqrt(4.0 * (double)n);  // (kRadiusAbove / kRadiusBelow: of r, within d of the swarm's)

@@ -695,7 +695,7 @@ __global__ __launch_bounds__(kGenThreads, 4) void wide_de_kernel(const sx_de_arg
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long wide_sort_key(double f) {  // (sx_pso.hip sort_key)
     const unsigned long long b = (unsigned long long)__double_as_longlong(f);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return is_nan(f) ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
 template <int FUN, int RNG>

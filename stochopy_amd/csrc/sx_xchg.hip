@@ -217,32 +217,22 @@ __global__ __launch_bounds__(kXfThreads) void xchg_finalize_kernel(
             f[u] = k < npart ? part_f[k] : __builtin_huge_val();
             i[u] = k < npart ? part_i[k] : INT64_MAX;
         }
+        // np.argmin's order (argmin_combine): a NaN record wins, so a shard whose records are all NaN still names a row
 #pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (f[u] < bf || (f[u] == bf && i[u] < bi)) {
-                bf = f[u];
-                bi = i[u];
-            }
+        for (int u = 0; u < 8; ++u) argmin_combine(bf, bi, f[u], i[u]);
     }
 #pragma unroll
     for (int off = 1; off < kWave; off <<= 1) {
         const double f2 = __shfl_xor(bf, off, kWave);
         const int64_t i2 = __shfl_xor((long long)bi, off, kWave);
-        if (f2 < bf || (f2 == bf && i2 < bi)) {
-            bf = f2;
-            bi = i2;
-        }
+        argmin_combine(bf, bi, f2, i2);
     }
     if (lane == 0) {
         sf[wave] = bf;
         si[wave] = bi;
     }
     __syncthreads();
-    for (int w = 0; w < nw; ++w)
-        if (sf[w] < bf || (sf[w] == bf && si[w] < bi)) {
-            bf = sf[w];
-            bi = si[w];
-        }
+    for (int w = 0; w < nw; ++w) argmin_combine(bf, bi, sf[w], si[w]);
     if (state->done || *x.error) return;  // uniform
     const int64_t it = state->it + 1;     // the generation being finalised
     const uint32_t tag = (uint32_t)(it + 1);

@@ -85,9 +85,9 @@ __device__ __forceinline__ bool xchg_wait_best(const uint64_t *slots_p, int n, i
     const bool rec = lane < world;
     double f = rec ? __longlong_as_double((long long)(((uint64_t)f_hi << 32) | f_lo)) : __builtin_huge_val();
     int64_t i = rec ? (int64_t)(((uint64_t)i_hi << 32) | i_lo) : INT64_MAX;
-    const double m = wave_min_f64(f);
-    const unsigned long long mask = __ballot(rec && f == m);
-    const int src = mask ? (int)__ffsll((long long)mask) - 1 : 0;  // NaN everywhere: rank 0, like argmin's first
+    // np.argmin's order: a NaN record wins, the lowest rank among ties (ranks hold rows in order)
+    const unsigned long long mask = best_lanes(f, wave_min_f64(f), rec);
+    const int src = mask ? (int)__ffsll((long long)mask) - 1 : 0;
     const int lo = __builtin_amdgcn_readlane((int)(i & 0xffffffffll), src);
     const int hi = __builtin_amdgcn_readlane((int)(i >> 32), src);
     bf = readlane_f64(f, src);

@@ -358,9 +358,10 @@ def _torch_int32():
 
 
 def best_of_records(records):
-    """Host restatement of the device rule (sx_gather_finalize): first minimum by (f, global row).
-    records: (world, n+2) array-like.  Returns (winner rank, f, global row)."""
+    """Host restatement of the device rule (sx_gather_finalize): first minimum by (f, global row) in np.argmin's order
+    (any NaN first).  records: (world, n+2) array-like.  Returns (winner rank, f, global row)."""
     rec = np.asarray(records)
-    order = np.lexsort((rec[:, 1], rec[:, 0]))
+    nan = np.isnan(rec[:, 0])
+    order = np.lexsort((rec[:, 1], np.where(nan, 0.0, rec[:, 0]), ~nan))
     w = int(order[0])
     return w, float(rec[w, 0]), int(rec[w, 1])

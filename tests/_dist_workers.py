@@ -111,7 +111,9 @@ def cpu_cpso_worker(rank, world, port, cfg, out_dir):
         fobj = oracle.OBJECTIVES[cfg["objective"]]
         row0, Pl = w.shard(P)
         delta = np.log(1.0 + 0.003 * P) / np.max((0.2, np.log(0.01 * maxiter)))
-        X = oe.latin_hypercube(stream, P, n, lower, upper)[row0:row0 + Pl].copy()
+        X0 = oe.latin_hypercube(stream, P, n, lower, upper)
+        X0[cfg.get("nan_rows", [])] = np.nan  # NaN pbestfit there: np.argmin's best row, across the ranks
+        X = X0[row0:row0 + Pl].copy()
         V = np.zeros((Pl, n))
         pbest, pbestfit = X.copy(), fobj(X)
 
@@ -261,7 +263,8 @@ def _minimize_and_save(rank, world, cfg, out_dir):
         fun = sa.factory.batched(_sphere)
     seen = []
     cb = (lambda X, r: seen.append((np.array(X, copy=True), float(r.fun), int(r.nit), int(r.nfev)))) if cfg.get("callback") else None
-    res = sa.optimize.minimize(fun, cfg.get("bounds", [[-5.12, 5.12]] * n), method=cfg["method"], options=opts, callback=cb)
+    x0 = np.array(cfg["x0"]) if "x0" in cfg else None
+    res = sa.optimize.minimize(fun, cfg.get("bounds", [[-5.12, 5.12]] * n), x0=x0, method=cfg["method"], options=opts, callback=cb)
     if "xall" in res:
         np.save(os.path.join(out_dir, f"xall_{rank}.npy"), res.xall)
         np.save(os.path.join(out_dir, f"funall_{rank}.npy"), res.funall)

@@ -26,6 +26,8 @@ import json
 import os
 import sys
 
+import warnings
+
 import numpy as np
 
 REF = os.environ.get("STOCHOPY_REFERENCE", "/root/reference")
@@ -604,8 +606,117 @@ def na():
     print("wrote na_xall.npz", os.path.getsize(os.path.join(HERE, "na_xall.npz")))
 
 
+
+# --------------------------------------------------------------------------- #
+# 8. non-finite objective values: np.argmin takes the first NaN (any sign bit), np.argsort puts NaN last, np.max
+#    propagates it.  Runs with a NaN / inf entry in x0, objectives with a NaN slab or a plateau of tied minima
+#    (-0.0 and 0.0).  Fitness values are stored as raw uint64 bits so that NaN signs survive.
+# --------------------------------------------------------------------------- #
+def nf_slab(X):
+    """sphere around -0.5; NaN where x0 > 1 (inf - inf: on x86 its sign bit is set), a positive NaN where x2 > 1.5,
+    -inf where x1 < -1.95 (rows of a population)."""
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    f = ((X + 0.5) ** 2).sum(axis=1)
+    inf = np.full(len(X), np.inf)
+    f = np.where(X[:, 0] > 1.0, inf - inf, f)
+    f = np.where(X[:, 2] > 1.5, np.abs(inf - inf), f)
+    return np.where(X[:, 1] < -1.95, -np.inf, f)
+
+
+def nf_cma_slab(X):
+    """sphere around 0.3, NaN where x0 > 0.9 (few enough candidates per generation for the model to stay finite)."""
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    return np.where(X[:, 0] > 0.9, np.nan, ((X - 0.3) ** 2).sum(axis=1))
+
+
+def nf_plateau(X):
+    """the minimum is a plateau: zero on the box |x| <= 0.5 (-0.0 where x0 < 0, 0.0 elsewhere), the squared excess outside."""
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    d = np.maximum(np.abs(X) - 0.5, 0.0)
+    f = (d * d).sum(axis=1)
+    return np.where((X[:, 0] < 0.0) & (f == 0.0), -0.0, f)
+
+
+def nf_rosenbrock(X):
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    return np.array([stochopy.factory.rosenbrock(x) for x in X])
+
+
+NF_OBJECTIVES = {"slab": nf_slab, "cma_slab": nf_cma_slab, "plateau": nf_plateau, "rosenbrock": nf_rosenbrock}
+
+
+def nf_x0(P, n, lo, hi, seed, form):
+    x0 = np.random.RandomState(seed).uniform(lo, hi, (P, n))
+    if form == "nan":
+        x0[5, 2] = np.nan
+    elif form == "nan_late":
+        x0[P - 1, 0] = np.nan
+    elif form == "inf":
+        x0[3, 1] = np.inf
+        x0[P - 2, n - 1] = -np.inf
+    return x0
+
+
+def nonfinite():
+    out = dict(STAMP)
+    cases = []
+    arrays = {}
+
+    def bits(a):
+        return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+    def add(tag, objective, method, n, bounds, opts, form=None):
+        fobj = NF_OBJECTIVES[objective]
+        x0 = None if form is None else nf_x0(opts["popsize"], n, bounds[0], bounds[1], 3, form)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)
+            res = minimize(lambda x: float(fobj(x)[0]), [bounds] * n, x0=None if x0 is None else x0.copy(), method=method,
+                           options=dict(opts))
+        entry = {"tag": tag, "objective": objective, "method": method, "ndim": n, "bounds": list(bounds),
+                 "options": opts, "x0_form": form, "nit": int(res.nit), "status": int(res.status),
+                 "fun_bits": hex(int(bits(res.fun)))}
+        arrays[tag + "__x"] = np.asarray(res.x, dtype=np.float64)
+        if x0 is not None:
+            arrays[tag + "__x0"] = x0
+        if opts.get("return_all"):
+            arrays[tag + "__xall"] = np.asarray(res.xall, dtype=np.float64)
+            arrays[tag + "__funall"] = bits(res.funall)
+        cases.append(entry)
+        print(" ", tag, "fun", float(res.fun), "nit", res.nit, "status", res.status)
+
+    base = {"maxiter": 20, "popsize": 12, "seed": 1}
+    for strat in ("best1bin", "rand1bin"):
+        for upd in ("deferred", "immediate"):
+            add("de_%s_%s_nan" % (strat, upd), "rosenbrock", "de", 4, (-2.0, 2.0), dict(base, strategy=strat, updating=upd), "nan")
+    add("de_best1bin_deferred_nan_late", "rosenbrock", "de", 4, (-2.0, 2.0), dict(base, strategy="best1bin", updating="deferred"), "nan_late")
+    add("de_rand1bin_immediate_inf", "rosenbrock", "de", 4, (-2.0, 2.0), dict(base, strategy="rand1bin", updating="immediate"), "inf")
+    for method in ("pso", "cpso"):
+        for upd in ("deferred", "immediate"):
+            add("%s_%s_nan" % (method, upd), "rosenbrock", method, 4, (-2.0, 2.0), dict(base, updating=upd), "nan")
+        add("%s_deferred_inf" % method, "rosenbrock", method, 4, (-2.0, 2.0), dict(base, updating="deferred"), "inf")
+    # a long CPSO run (restarts fire when the best row is finite): with a NaN best row the radius is NaN, no restart
+    add("cpso_long_nan_best", "rosenbrock", "cpso", 4, (-2.0, 2.0), dict(base, maxiter=200, updating="deferred"), "nan")
+    add("cpso_long_inf", "rosenbrock", "cpso", 4, (-2.0, 2.0), dict(base, maxiter=200, updating="deferred"), "inf")
+    hist = {"maxiter": 12, "popsize": 16, "seed": 6, "return_all": True, "verbosity": 0.0}
+    for method in ("de", "pso", "cpso", "na"):
+        o = dict(hist) if method == "na" else dict(hist, updating="deferred")
+        add("%s_slab" % method, "slab", method, 4, (-2.0, 2.0), o)
+        add("%s_plateau" % method, "plateau", method, 4, (-2.0, 2.0), o)
+    for method in ("cmaes", "vdcma"):
+        for verb in (0.0, 0.5):
+            add("%s_slab_v%g" % (method, verb), "cma_slab", method, 6, (-3.0, 3.0),
+                {"maxiter": 25, "popsize": 20, "seed": 12, "sigma": 0.5, "return_all": True, "verbosity": verb})
+    add("cmaes_plateau_v0", "plateau", "cmaes", 4, (-2.0, 2.0),
+        {"maxiter": 20, "popsize": 12, "seed": 3, "sigma": 0.3, "return_all": True, "verbosity": 0.0})
+    out["cases"] = cases
+    dump("nonfinite.json", out)
+    np.savez_compressed(os.path.join(HERE, "nonfinite_xall.npz"), **arrays)
+    print("wrote nonfinite_xall.npz", os.path.getsize(os.path.join(HERE, "nonfinite_xall.npz")), "bytes")
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["rng", "factory", "suite", "configs", "penalize", "vdcma", "immediate", "na"]
+    which = sys.argv[1:] or ["rng", "factory", "suite", "configs", "penalize", "vdcma", "immediate", "na", "nonfinite"]
+    if "nonfinite" in which:
+        nonfinite()
     if "na" in which:
         na()
     if "immediate" in which:

@@ -119,6 +119,70 @@ def test_cpso_fit_radius_gather_two_ranks_gloo_cpu(constraints):
         assert np.array_equal(got["rows"], np.concatenate(ref["_restart_rows"]))
 
 
+def test_record_rule_puts_nan_first():
+    """The host's record rule is np.argmin's: any NaN record (either sign) before every number, then the lower row."""
+    from stochopy_amd import parallel
+
+    neg_nan = np.frombuffer(np.uint64(0xFFF8000000000000).tobytes(), dtype=np.float64)[0]
+    rec = np.array([[-np.inf, 3.0, 0.0], [np.nan, 900.0, 0.0], [neg_nan, 400.0, 0.0], [0.5, 1.0, 0.0]])
+    w, f, gi = parallel.best_of_records(rec)
+    assert (w, gi) == (2, 400) and np.isnan(f)
+    assert parallel.best_of_records(rec[[0, 3]]) == (0, -np.inf, 3)
+
+
+def test_cpso_nan_row_on_rank_1_two_ranks_gloo_cpu():
+    """world_size 2 on CPU, a NaN row on rank 1 and the finite minimum on rank 0: the exchanged best is the NaN row
+    (np.argmin), its radius is NaN, no restart fires -- as in the unsharded oracle run from the same x0."""
+    from _dist_workers import cpu_cpso_worker
+
+    n, P, seed = 4, 40, 77
+    cfg = {"n": n, "P": P, "maxiter": 120, "gamma": 1.0, "npart": 3, "seed": seed, "objective": "ackley",
+           "constraints": None, "xtol": 1e-12, "ftol": 1e-12, "nan_rows": [P // 2 + 3]}
+    out = _spawn(cpu_cpso_worker, 2, cfg)
+    lower, upper = np.full(n, -32.768), np.full(n, 32.768)
+    x0 = oe.latin_hypercube(oracle.PhiloxStream(seed), P, n, lower, upper)
+    x0[cfg["nan_rows"]] = np.nan
+    assert np.argmin(oracle.OBJECTIVES["ackley"](x0[:P // 2])) < P // 2  # rank 0 holds a finite minimum
+    ref = oe.run_pso(oracle.OBJECTIVES["ackley"], lower, upper, x0, oracle.PhiloxStream(seed), maxiter=120, popsize=P,
+                     competitivity=1.0, xtol=1e-12, ftol=1e-12)
+    assert np.isnan(ref["fun"]) and ref["_restarts"] == []
+    for r in range(2):
+        got = np.load(os.path.join(out, f"cpso_{r}.npz"))
+        assert int(got["nit"]) == ref["nit"] and int(got["status"]) == ref["status"]
+        assert np.isnan(float(got["fun"])) and np.array_equal(got["x"], ref["x"], equal_nan=True)
+        assert got["restarts"].size == 0
+
+
+# NaN in x0 on rank 1 (one row, or the whole shard) with the finite minimum on rank 0: the exchanged best row is the
+# first NaN row (np.argmin); no trial replaces it (strict <), so the run ends at maxiter with x = that row, fun = nan
+_NAN_SHARD_RUNS = [("de", {"exchange": "rccl"}, {}), ("de", {"exchange": "p2p"}, {}),
+                   ("pso", {}, {"SX_EXCHANGE": "p2p"}), ("pso", {}, {"SX_EXCHANGE": "rccl"}),
+                   ("cpso", {}, {"SX_EXCHANGE": "p2p"})]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shard", ["one_row", "all_rows"])
+@pytest.mark.parametrize("method,extra,env", _NAN_SHARD_RUNS, ids=["de-rccl", "de-p2p", "pso-p2p", "pso-rccl", "cpso-p2p"])
+def test_two_ranks_nan_on_rank_1(method, extra, env, shard):
+    from _dist_workers import gpu_minimize_worker
+
+    n, P, gens = 24, 128, 12
+    x0 = np.random.RandomState(5).uniform(-5.12, 5.12, (P, n))
+    x0[3] = 0.9  # rank 0: a finite minimum well below the rest
+    first = P // 2 + 7 if shard == "one_row" else P // 2
+    if shard == "one_row":
+        x0[first, 5] = np.nan
+    else:
+        x0[P // 2:] = np.nan
+    opts = {"maxiter": gens, "popsize": P, "seed": 31, "updating": "deferred", **extra}
+    cfg = {"n": n, "objective": "rosenbrock", "method": method, "options": opts, "x0": x0, "env": env}
+    out = _spawn(gpu_minimize_worker, 2, cfg)
+    for r in range(2):
+        fun, nit, nfev, status = np.load(os.path.join(out, f"meta_{r}.npy"))
+        assert np.isnan(fun) and (nit, status) == (gens, -1), (r, fun, nit, status)
+        assert np.array_equal(np.load(os.path.join(out, f"x_{r}.npy")), x0[first], equal_nan=True), r
+
+
 @pytest.mark.parametrize("method,constraints", [("cmaes", None), ("cmaes", "Penalize"), ("vdcma", None)])
 def test_cma_candidate_gather_two_ranks_gloo_cpu(method, constraints):
     """world_size 2 on CPU: CMA-ES / VD-CMA shard the candidates (rows drawn and evaluated by their owner, gathered with

@@ -267,8 +267,54 @@ def _sort_key_np(f):
     return np.where(b >> np.uint64(63), ~b, b | np.uint64(0x8000000000000000))
 
 
+def _restart_fitness(P, kind, rs):
+    if kind == "spread":
+        fit = rs.uniform(0.0, 100.0, P)
+    elif kind == "converged":
+        fit = 3.7 + 1.0e-9 * rs.rand(P)
+    elif kind == "outliers":
+        fit = 1.0e-3 * rs.rand(P)
+        fit[rs.choice(P, 7, replace=False)] = 10.0 ** rs.uniform(3, 200, 7)
+    elif kind == "ties":
+        fit = np.round(rs.rand(P) * 20.0) / 20.0
+    elif kind == "two_values":
+        fit = np.where(rs.rand(P) < 0.3, 1.0, 2.0)
+    elif kind in ("nan", "neg_nan"):  # NaN pbestfit (a NaN row of x0 keeps it): argsort puts them last, re-seeded first
+        fit = rs.uniform(0.0, 100.0, P)
+        sign = 0xFFF8000000000000 if kind == "neg_nan" else 0x7FF8000000000000
+        fit[rs.choice(P, 40, replace=False)] = np.frombuffer(np.uint64(sign).tobytes(), dtype=np.float64)[0]
+        if kind == "neg_nan":
+            fit[rs.choice(P, 5, replace=False)] = np.nan  # both signs in one swarm
+    elif kind == "inf":
+        fit = rs.uniform(0.0, 100.0, P)
+        fit[rs.choice(P, 30, replace=False)] = np.inf
+        fit[rs.choice(P, 30, replace=False)] = -np.inf
+    elif kind == "all_nan":
+        fit = np.full(P, np.nan)
+    else:
+        fit = 0.5 + 1.0e-6 * rs.rand(P)
+        fit[rs.choice(P, P // 3, replace=False)] = 1.0e30
+    return fit
+
+
+_RESTART_KINDS = ["spread", "converged", "outliers", "ties", "two_values", "reseeded", "nan", "neg_nan", "inf", "all_nan"]
+
+
+def _check_restart_threshold(fit, nw, thr, tag):
+    """The threshold key against the reference's rule, `idx = pbestfit.argsort()[: -nw - 1 : -1]` (cpso/_cpso.py:420):
+    it is the key of fit[idx[-1]], every NaN the largest key; the rows at or above it (what sx_pso_restart_apply re-seeds)
+    hold every row of idx, and only those when fit[idx[-1]] is not tied."""
+    idx = fit.argsort()[: -nw - 1 : -1]
+    keys = np.where(np.isnan(fit), np.uint64(0xFFFFFFFFFFFFFFFF), _sort_key_np(fit))
+    assert thr == keys[idx[-1]], tag + (hex(int(thr)), hex(int(keys[idx[-1]])))
+    reseeded = np.flatnonzero(keys >= np.uint64(thr))
+    assert set(idx.tolist()) <= set(reseeded.tolist()), tag
+    if np.count_nonzero(keys == keys[idx[-1]]) == 1:
+        assert np.array_equal(np.sort(idx), reseeded), tag
+
+
 @pytest.mark.parametrize("P", [8192, 12000, 16384])
-@pytest.mark.parametrize("kind", ["spread", "converged", "outliers", "ties", "two_values", "reseeded"])
+@pytest.mark.parametrize("kind", _RESTART_KINDS)
 def test_restart_selection_kernel_vs_numpy(sa, P, kind):
     """sx_pso_restart_select at the swarm sizes where it first cuts the keys down to a sample-guided window (round 3:
     256 samples ranked, the target's sample rank +- 24, keys above counted, keys inside packed into LDS) before the radix
@@ -284,20 +330,7 @@ def test_restart_selection_kernel_vs_numpy(sa, P, kind):
     L, t, p = ctx.L, _device.torch(), _device.ptr
     rs = np.random.RandomState(P + len(kind))
     n, maxiter, delta, gamma = 8, 1000, 1.0e-2, 1.0
-    if kind == "spread":
-        fit = rs.uniform(0.0, 100.0, P)
-    elif kind == "converged":
-        fit = 3.7 + 1.0e-9 * rs.rand(P)
-    elif kind == "outliers":
-        fit = 1.0e-3 * rs.rand(P)
-        fit[rs.choice(P, 7, replace=False)] = 10.0 ** rs.uniform(3, 200, 7)
-    elif kind == "ties":
-        fit = np.round(rs.rand(P) * 20.0) / 20.0
-    elif kind == "two_values":
-        fit = np.where(rs.rand(P) < 0.3, 1.0, 2.0)
-    else:
-        fit = 0.5 + 1.0e-6 * rs.rand(P)
-        fit[rs.choice(P, P // 3, replace=False)] = 1.0e30
+    fit = _restart_fitness(P, kind, rs)
     with t.cuda.stream(ctx.stream):
         g = ctx.L.sx_num_partials(P, n)
         d = {k: ctx.zeros((P, n)) for k in ("X", "V", "pbest")}
@@ -319,5 +352,44 @@ def test_restart_selection_kernel_vs_numpy(sa, P, kind):
             nw = int((P - 1.0) / (1.0 + np.exp(1.0 / 0.09 * (it / maxiter - gamma + 0.5))))
             assert int(got[0]) == max(nw, 0), (it, got[0], nw)
             if nw > 0:
-                want = np.sort(_sort_key_np(fit))[::-1][nw - 1]
-                assert got[1] == want, (kind, P, it, nw, hex(int(got[1])), hex(int(want)))
+                if not np.isnan(fit).any():
+                    want = np.sort(_sort_key_np(fit))[::-1][nw - 1]
+                    assert got[1] == want, (kind, P, it, nw, hex(int(got[1])), hex(int(want)))
+                _check_restart_threshold(fit, nw, got[1], (kind, P, it, nw))
+
+
+@pytest.mark.parametrize("kind", _RESTART_KINDS)
+def test_restart_selection_gathered_vs_numpy(sa, kind):
+    """sx_pso_restart_select_gathered (the sharded swarm: every rank's [pbestfit | partial radii] gathered, two ranks here)
+    against the same argsort rule over the whole swarm."""
+    import ctypes as C
+
+    from stochopy_amd import _device, _lib
+
+    ctx = _device.Context()
+    L, t, p = ctx.L, _device.torch(), _device.ptr
+    world, Ploc, n, maxiter, delta, gamma = 2, 6000, 8, 1000, 1.0e-2, 1.0
+    P = world * Ploc
+    fit = _restart_fitness(P, kind, np.random.RandomState(len(kind)))
+    g = ctx.L.sx_num_partials(Ploc, n)
+    gathered = np.concatenate([np.concatenate([fit[r * Ploc:(r + 1) * Ploc], np.full(g, 1.0e-6)]) for r in range(world)])
+    with t.cuda.stream(ctx.stream):
+        d = {k: ctx.zeros((Ploc, n)) for k in ("X", "V", "pbest")}
+        d_fit, d_gath = ctx.upload(fit[:Ploc].copy()), ctx.upload(gathered)
+        d_gbest, d_pf, d_pi = ctx.zeros((n,)), ctx.zeros((g,)), ctx.zeros((g,), dtype=t.int64)
+        out = ctx.zeros((3,), dtype=t.int64)
+        for it in (40, 480, 560, 900):
+            st = _lib.SxState(it=it, gbidx=0, gfit=0.0, dx=0.0, status=_lib.SX_STATUS_NONE, done=0)
+            d_state = ctx.upload(np.frombuffer(bytes(st), dtype=np.int64).copy())
+            a = _lib.SxPsoArgs()
+            a.X, a.V, a.pbest, a.pbestfit, a.gbest = (x.data_ptr() for x in (d["X"], d["V"], d["pbest"], d_fit, d_gbest))
+            a.state, a.part_f, a.part_i = d_state.data_ptr(), d_pf.data_ptr(), d_pi.data_ptr()
+            a.P, a.ld, a.row0, a.n, a.fun_id, a.rng, a.maxiter = Ploc, n, 0, n, 0, _lib.SX_RNG_PHILOX, maxiter
+            _lib.check(L.sx_pso_restart_select_gathered(C.byref(a), p(d_gath), world, delta, gamma, p(out), ctx.stream_ptr),
+                       "sx_pso_restart_select_gathered")
+            ctx.sync()
+            got = out.cpu().numpy().view(np.uint64)
+            nw = int((P - 1.0) / (1.0 + np.exp(1.0 / 0.09 * (it / maxiter - gamma + 0.5))))
+            assert int(got[0]) == max(nw, 0), (it, got[0], nw)
+            if nw > 0:
+                _check_restart_threshold(fit, nw, got[1], (kind, it, nw))

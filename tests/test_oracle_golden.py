@@ -299,3 +299,57 @@ def test_default_updating_is_the_references(method):
     deferred = oracle.minimize("ackley", bounds, method=method, options=dict(opts, updating="deferred"))
     assert default["fun"] == immediate["fun"] and np.array_equal(default["x"], immediate["x"])
     assert default["fun"] != deferred["fun"]
+
+
+# --------------------------------------------------------------------------- #
+# non-finite objective values (tests/golden/nonfinite.*): NaN / inf in x0, a NaN slab, a plateau with -0.0 and 0.0
+# --------------------------------------------------------------------------- #
+def _nf_slab(X):
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    f = ((X + 0.5) ** 2).sum(axis=1)
+    inf = np.full(len(X), np.inf)
+    f = np.where(X[:, 0] > 1.0, inf - inf, f)  # (sign bit set on x86)
+    f = np.where(X[:, 2] > 1.5, np.abs(inf - inf), f)
+    return np.where(X[:, 1] < -1.95, -np.inf, f)
+
+
+def _nf_cma_slab(X):
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    return np.where(X[:, 0] > 0.9, np.nan, ((X - 0.3) ** 2).sum(axis=1))
+
+
+def _nf_plateau(X):
+    X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+    d = np.maximum(np.abs(X) - 0.5, 0.0)
+    f = (d * d).sum(axis=1)
+    return np.where((X[:, 0] < 0.0) & (f == 0.0), -0.0, f)
+
+
+# the objectives of tests/golden/make_golden.py nonfinite()
+_NF_OBJECTIVES = {"slab": _nf_slab, "cma_slab": _nf_cma_slab, "plateau": _nf_plateau, "rosenbrock": OBJECTIVES["rosenbrock"]}
+
+
+def _nonfinite_cases():
+    return load_golden("nonfinite.json")["cases"]
+
+
+@pytest.mark.parametrize("case", _nonfinite_cases(), ids=lambda c: c["tag"])
+def test_oracle_reproduces_nonfinite_golden(case):
+    """oracle.minimize against the reference bit for bit: x (NaN positions included), fun and funall as raw bits (NaN
+    signs included), nit, status."""
+    import warnings
+
+    arrays = np.load(os.path.join(GOLDEN, "nonfinite_xall.npz"))
+    tag = case["tag"]
+    x0 = arrays[tag + "__x0"].copy() if case["x0_form"] else None
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        res = oracle.minimize(_NF_OBJECTIVES[case["objective"]], [case["bounds"]] * case["ndim"], x0=x0,
+                              method=case["method"], options=dict(case["options"]), rng="numpy-legacy")
+    bits = lambda a: np.asarray(a, dtype=np.float64).view(np.uint64)  # noqa: E731
+    assert (res.nit, res.status) == (case["nit"], case["status"])
+    assert hex(int(bits(res.fun))) == case["fun_bits"], (tag, res.fun)
+    assert np.array_equal(bits(res.x), bits(arrays[tag + "__x"])), (tag, res.x, arrays[tag + "__x"])
+    if case["options"].get("return_all"):
+        assert np.array_equal(bits(res.funall), arrays[tag + "__funall"]), tag
+        assert np.array_equal(bits(res.xall), bits(arrays[tag + "__xall"])), tag
