@@ -89,13 +89,11 @@ int64_t sx_fun_terms(int fun_id, int n);
 int64_t sx_num_partials(int64_t P, int n);
 int sx_rows_per_workgroup(int n); /* rows of one workgroup of the row kernels = rows behind one (part_f, part_i) record */
 /* Rows of more than this many elements are served by the one-workgroup-per-row kernels (one record per row, no chained /
- * peer-exchange form): what a host loop needs to know to size its record buffers and to pick the two-kernel path. */
+ * peer-exchange form): what a host loop needs to know to size its record buffers and to pick the two-kernel path.  2048:
+ * where the one-workgroup-per-row kernels become the faster ones. */
 int sx_wide_from(void);
-/* The same threshold, set for the runs that follow: n <= 0 restores the library's own (2048: where the one-workgroup-per-row
- * kernels become the faster ones); otherwise clamped to [256, 4096], the range the wavefront-per-row kernels can serve.  A run
- * that needs the chained kernel's peer exchange or its global-donor gathers on rows of 2049 ... 4096 elements raises it to 4096
- * for its duration (optimize/_de.py).  Returns the previous value.  Process-wide, not thread-safe. */
-int sx_set_wide_from(int n);
+/* sx_num_partials for a DE run whose sx_de_args.wide_from is `wide_from` (0: sx_wide_from()). */
+int64_t sx_de_num_partials(int64_t P, int n, int wide_from);
 int sx_eval(int fun_id, const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd,
             double *f, double *part_f, int64_t *part_i, void *stream);
 
@@ -147,8 +145,8 @@ typedef struct sx_de_args {
     const double *lower;    /* DEVICE (n)                                             */
     const double *upper;    /* DEVICE (n)                                             */
     sx_state *state;        /* DEVICE                                                 */
-    double *part_f;         /* DEVICE (sx_num_partials(P))                            */
-    int64_t *part_i;        /* DEVICE (sx_num_partials(P))                            */
+    double *part_f;         /* DEVICE (sx_de_num_partials(P, n, wide_from))           */
+    int64_t *part_i;        /* DEVICE (sx_de_num_partials(P, n, wide_from))           */
     /* SX_RNG_HOST inputs for ONE generation (the numpy-legacy stream, App. B):      */
     const double *r1;       /* DEVICE (P,n) rand(P,n), de/_de.py:250                  */
     const int32_t *donors;  /* DEVICE (k,P) first k rows of delete_shuffle_sync, :304 */
@@ -163,6 +161,10 @@ typedef struct sx_de_args {
     int32_t constraints;    /* 0 none, 1 Random                                       */
     int32_t rng;            /* SX_RNG_HOST / SX_RNG_PHILOX                            */
     int32_t maxiter;
+    int32_t wide_from;      /* rows of more than this many elements take the one-workgroup-per-row kernels; 0 = sx_wide_from().
+                               Clamped to [256, 4096], the rows the wavefront-per-row kernels can serve.  A run that needs the
+                               chained kernel's peer exchange or global-donor gathers on rows of 2049 ... 4096 elements sets 4096 */
+    int32_t pad;
     double F, CR, xtol, ftol;
     uint32_t key0, key1;    /* Philox key = seed                                      */
 } sx_de_args;

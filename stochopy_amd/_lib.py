@@ -52,6 +52,7 @@ class SxDeArgs(C.Structure):
         ("irand", vp), ("resample", vp),
         ("P", i64), ("ld", i64), ("row0", i64),
         ("n", i32), ("fun_id", i32), ("strategy", i32), ("constraints", i32), ("rng", i32), ("maxiter", i32),
+        ("wide_from", i32), ("pad", i32),
         ("F", f64), ("CR", f64), ("xtol", f64), ("ftol", f64),
         ("key0", C.c_uint32), ("key1", C.c_uint32),
     ]
@@ -115,13 +116,13 @@ class SxCmaArgs(C.Structure):
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
     "sx_wide_from": (C.c_int, []),
-    "sx_set_wide_from": (C.c_int, [C.c_int]),
     "sx_last_error": (C.c_char_p, []),
     "sx_device_count": (C.c_int, []),
     "sx_struct_size": (C.c_int, [C.c_int]),
     "sx_sum_plan": (C.c_int, [i64, vp, C.c_int]),
     "sx_fun_terms": (i64, [C.c_int, C.c_int]),
     "sx_num_partials": (i64, [i64, C.c_int]),
+    "sx_de_num_partials": (i64, [i64, C.c_int, C.c_int]),
     "sx_rows_per_workgroup": (C.c_int, [C.c_int]),
     "sx_eval": (C.c_int, [C.c_int, vp, i64, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
     "sx_philox_lhs": (C.c_int, [vp, i64, C.c_int, i64, i64, i64, vp, vp, C.c_uint32, C.c_uint32, vp]),
@@ -235,6 +236,10 @@ def lib():
         fn.argtypes = args
     if handle.sx_abi_version() != 1:
         raise HipLibraryError("ABI version mismatch; rebuild the library")
+    for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs)):
+        if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
+            raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
+                                  f"{C.sizeof(mirror)}; rebuild the library")
     _lib = handle
     return _lib
 

@@ -103,20 +103,12 @@ extern "C" int64_t sx_fun_terms(int fun_id, int n) {
     return n;
 }
 
-extern "C" int64_t sx_num_partials(int64_t P, int n) { return (int64_t)row_geometry(P, n).blocks; }
-namespace sx {
-int g_wide_from = kWideFrom;
+extern "C" int64_t sx_num_partials(int64_t P, int n) { return (int64_t)row_geometry(P, n, kWideFrom).blocks; }
+extern "C" int64_t sx_de_num_partials(int64_t P, int n, int wide_from) {
+    return (int64_t)row_geometry(P, n, run_wide_from(wide_from)).blocks;
 }
-extern "C" int sx_rows_per_workgroup(int n) { return n > sx::wide_from() ? 1 : rows_per_block(n); }
-extern "C" int sx_wide_from(void) { return sx::wide_from(); }
-// n <= 0: back to the library's own threshold; otherwise clamped to [256, 4096] (what the wavefront-per-row kernels can serve).
-// Returns the previous value.  Process-wide, not thread-safe: set it before a run's first call and restore it after its last
-// (everything that depends on it -- record counts, geometries, which kernels run -- is read per call).
-extern "C" int sx_set_wide_from(int n) {
-    const int prev = sx::g_wide_from;
-    sx::g_wide_from = n <= 0 ? kWideFrom : (n < 256 ? 256 : (n > kMaxDim ? kMaxDim : n));
-    return prev;
-}
+extern "C" int sx_rows_per_workgroup(int n) { return n > kWideFrom ? 1 : rows_per_block(n); }
+extern "C" int sx_wide_from(void) { return kWideFrom; }
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out) {
@@ -547,7 +539,7 @@ static int64_t eval_r8_min_rows(int64_t dflt) {
     return forced >= 0 ? forced : dflt;
 }
 static bool eval_r8_long_ok(int64_t P, int n, const double *xm, const double *part_f, int clip, int nleaf, bool cheap) {
-    const bool has_rival = n > sx::wide_from() || n == 512 || n == 1024 || n == 2048;
+    const bool has_rival = n > kWideFrom || n == 512 || n == 1024 || n == 2048;
     return eval_r8_long_mode() != 0 && n > 256 && n <= kMaxDim && nleaf >= 1 && nleaf <= kMaxLeaf && xm == nullptr &&
            part_f == nullptr && clip == 0 && P >= eval_r8_min_rows(has_rival ? 32768 : cheap ? 8192 : 16384);
 }
@@ -588,7 +580,7 @@ template <int FUN>
 static int launch_eval(const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd, double *f,
                        const PlanArg &plan, double *part_f, int64_t *part_i, hipStream_t s, int clip = 0,
                        const double *pen_v = nullptr, double *pen_out = nullptr) {
-    const Geometry g = row_geometry(P, n);
+    const Geometry g = row_geometry(P, n, kWideFrom);
     // whole batches and whole workgroups: the guard-free form; one batch per row on top: the compile-time plan
     // (plain evaluation only -- the clip / penalty variants keep the general kernel, to keep the build small)
     const int lpr = lanes_per_row(n);
@@ -676,8 +668,8 @@ extern "C" int sx_eval(int fun_id, const double *X, int64_t P, int n, int64_t ld
                        fun_id == SX_FUN_STYBLINSKI_TANG;  // (light_objective<FUN>())
     const bool long_rows = n <= kMaxDim && eval_r8_long_ok(P, n, xm, part_f, 0, 1, cheap) &&
                            (eval_r8_long_mode() == 2 || !cheap || n <= 3584);
-    if (is_wide(n) && !long_rows) return wide_eval(fun_id, X, P, n, ldx, xm, xstd, f, part_f, part_i, 0, nullptr, nullptr, s);
-    if (is_wide(n) && n <= kWideMaxDim)
+    if (is_wide(n, kWideFrom) && !long_rows) return wide_eval(fun_id, X, P, n, ldx, xm, xstd, f, part_f, part_i, 0, nullptr, nullptr, s);
+    if (is_wide(n, kWideFrom) && n <= kWideMaxDim)
         if (int rc = wide_warm_plan(fun_id, n, s)) return rc;  // (the generations that follow are wide launches)
     PlanArg plan;
     if (make_plan_arg(fun_id, n, &plan)) return -1;
@@ -707,7 +699,7 @@ extern "C" int sx_cmaes_eval_penalized(int fun_id, const double *X, int64_t P, i
     SX_REQUIRE(fun_id >= 0 && fun_id < SX_FUN_COUNT, "sx_cmaes_eval_penalized: unknown fun_id");
     SX_REQUIRE((v == nullptr) == (pen == nullptr), "sx_cmaes_eval_penalized: v and pen must be given together");
     hipStream_t s = (hipStream_t)stream;
-    if (is_wide(n)) return wide_eval(fun_id, X, P, n, n, xm, xstd, f_raw, nullptr, nullptr, 1, v, pen, s);
+    if (is_wide(n, kWideFrom)) return wide_eval(fun_id, X, P, n, n, xm, xstd, f_raw, nullptr, nullptr, 1, v, pen, s);
     PlanArg plan;
     if (make_plan_arg(fun_id, n, &plan)) return -1;
     switch (fun_id) {

@@ -47,9 +47,9 @@ de_kernel_t kernel_for(const sx_de_args *a) {
 }
 
 Geometry geometry(const sx_de_args *a) {
-    Geometry g = row_geometry(a->P, a->n);
+    Geometry g = row_geometry(a->P, a->n, de_wide_from(a));
     // rows of up to 256 elements stage nothing but the trial vector (sx_device.hpp gen_row_stride)
-    if (!is_wide(a->n)) g.lds = (size_t)rows_per_block(a->n) * gen_row_stride(a->n) * sizeof(double);
+    if (!is_wide(a->n, de_wide_from(a))) g.lds = (size_t)rows_per_block(a->n) * gen_row_stride(a->n) * sizeof(double);
     return g;
 }
 
@@ -59,7 +59,7 @@ extern "C" int sx_de_generation(const sx_de_args *a, int finalize, void *stream)
     if (int rc = check_args(a)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const Geometry g = geometry(a);
-    if (is_wide(a->n)) {  // rows of more than sx_wide_from() elements: one workgroup per row (sx_wide.hip), one record per row
+    if (is_wide(a->n, de_wide_from(a))) {  // rows of more than the run's wide_from elements: one workgroup per row (sx_wide.hip), one record per row
         if (int rc = wide_de_launch(a, s)) return rc;
     } else {
         PlanArg plan;
@@ -86,7 +86,7 @@ extern "C" int sx_de_graph_create(const sx_de_args *a, int ngen, sx_graph **out)
     SX_REQUIRE(out != nullptr && ngen >= 1 && a->gbest != nullptr, "sx_de_graph_create: bad arguments");
     SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_de_graph_create: graphs need in-kernel (Philox) draws");
     PlanArg plan = {};
-    const bool wide = is_wide(a->n);
+    const bool wide = is_wide(a->n, de_wide_from(a));
     if (!wide && make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     const Geometry g = geometry(a);
     sx_graph *gr = new sx_graph();
@@ -139,8 +139,8 @@ extern "C" int sx_de_shard_generation(const sx_de_args *a, double *record, void 
 static int check_chain(const sx_de_args *a, bool peer_exchange) {
     if (int rc = check_args(a)) return rc;
     SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_de_chain: needs in-kernel (Philox) draws");
-    SX_REQUIRE(!is_wide(a->n), "sx_de_chain: rows served by the one-workgroup-per-row kernels (n > sx_wide_from()) take the two-kernel path (sx_de_generation)");
-    SX_REQUIRE(peer_exchange || sx_num_partials(a->P, a->n) <= 512,
+    SX_REQUIRE(!is_wide(a->n, de_wide_from(a)), "sx_de_chain: rows served by the one-workgroup-per-row kernels (n > wide_from) take the two-kernel path (sx_de_generation)");
+    SX_REQUIRE(peer_exchange || geometry(a).blocks <= 512,
                "sx_de_chain: more than 512 workgroup records (use the two-kernel path)");
     return 0;
 }

@@ -413,9 +413,9 @@ int check_args(const sx_pso_args *a) {
 }
 
 Geometry geometry(int64_t P, int n) {
-    Geometry g = row_geometry(P, n);
+    Geometry g = row_geometry(P, n, kWideFrom);
     // rows of up to 256 elements stage nothing but the new position (sx_device.hpp gen_row_stride)
-    if (!is_wide(n)) g.lds = (size_t)rows_per_block(n) * gen_row_stride(n) * sizeof(double);
+    if (!is_wide(n, kWideFrom)) g.lds = (size_t)rows_per_block(n) * gen_row_stride(n) * sizeof(double);
     return g;
 }
 
@@ -1175,7 +1175,7 @@ extern "C" int sx_pso_generation(const sx_pso_args *a, int finalize, void *strea
     if (int rc = check_args(a)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const Geometry g = geometry(a->P, a->n);
-    if (is_wide(a->n)) {  // rows of more than sx_wide_from() elements: one workgroup per particle (sx_wide.hip)
+    if (is_wide(a->n, kWideFrom)) {  // rows of more than kWideFrom elements: one workgroup per particle (sx_wide.hip)
         if (int rc = wide_pso_launch(a, s)) return rc;
     } else {
         PlanArg plan;
@@ -1291,7 +1291,7 @@ extern "C" int sx_pso_graph_create(const sx_pso_args *a, int ngen, double *part_
     SX_REQUIRE((part_r == nullptr) == (sel3 == nullptr), "sx_pso_graph_create: restart needs part_r AND sel3");
     SX_REQUIRE(part_r == nullptr || (a->lower && a->upper), "sx_pso_graph_create: bounds missing");
     PlanArg plan = {};
-    const bool wide = is_wide(a->n);
+    const bool wide = is_wide(a->n, kWideFrom);
     if (!wide && make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     const Geometry g = geometry(a->P, a->n);
     sx_graph *gr = new sx_graph();

@@ -32,10 +32,10 @@ struct Geometry {
     unsigned blocks, threads;
     size_t lds;
 };
-inline Geometry row_geometry(int64_t P, int n) {
-    // wide rows (n > kWideFrom, sx_wide.hip): one row and one record per workgroup; the kernels that still walk such a row with
+inline Geometry row_geometry(int64_t P, int n, int wide_from) {
+    // wide rows (n > wide_from, sx_wide.hip): one row and one record per workgroup; the kernels that still walk such a row with
     // ONE wavefront (candidate / selection / radius kernels: no staging) are launched with 64 threads and no dynamic LDS
-    if (n > sx::wide_from()) return Geometry{(unsigned)P, (unsigned)kWave, 0};
+    if (n > wide_from) return Geometry{(unsigned)P, (unsigned)kWave, 0};
     const int wpb = waves_per_block(n);
     const int rpb = rows_per_block(n);
     return Geometry{(unsigned)((P + rpb - 1) / rpb), (unsigned)(wpb * kWave),

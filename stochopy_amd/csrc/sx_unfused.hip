@@ -105,7 +105,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void pso_move_kernel(cons
     const bool shrink = a.constraints != 0;
     double beta = __builtin_huge_val();
     const int nq = (n + LPR - 1) / LPR;
-    // wide rows (n > sx_wide_from(): one wavefront per row, no dynamic LDS -- has_stash = 0): with Shrink the raw velocities are
+    // wide rows (n > kWideFrom: one wavefront per row, no dynamic LDS -- has_stash = 0): with Shrink the raw velocities are
     // formed AGAIN behind the row-wide beta instead of waiting in LDS -- same operands, same operations, same bits
     const bool stash = shrink && has_stash;
     // raw velocity of the two elements (q0 + t) * LPR + l, t = 0, 1 (one Philox call)
@@ -215,7 +215,7 @@ extern "C" int sx_de_propose(const sx_de_args *a, double *cand, void *stream) {
     SX_REQUIRE(a->rng != SX_RNG_HOST || (a->r1 && a->donors && a->irand), "sx_de_propose: host draws missing");
     SX_REQUIRE(a->constraints == 0 || (a->lower && a->upper && (a->rng != SX_RNG_HOST || a->resample)),
                "sx_de_propose: bounds / resample draws missing");
-    const Geometry g = row_geometry(a->P, a->n);
+    const Geometry g = row_geometry(a->P, a->n, run_wide_from(a->wide_from));
     if (a->rng == SX_RNG_PHILOX) {
         SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((de_propose_kernel<SX_RNG_PHILOX, LPR>), dim3(g.blocks), dim3(g.threads), 0,
                                                  (hipStream_t)stream, *a, cand))
@@ -234,8 +234,8 @@ extern "C" int sx_pso_move(const sx_pso_args *a, void *stream) {
     SX_REQUIRE(a->rng == SX_RNG_HOST || a->rng == SX_RNG_PHILOX, "sx_pso_move: unknown rng mode");
     SX_REQUIRE(a->rng != SX_RNG_HOST || (a->r1 && a->r2), "sx_pso_move: host draws missing");
     SX_REQUIRE(a->constraints == 0 || (a->lower && a->upper), "sx_pso_move: bounds missing");
-    const Geometry g = row_geometry(a->P, a->n);
-    const size_t lds = a->n > sx::wide_from() ? 0 : (size_t)rows_per_block(a->n) * a->n * sizeof(double);
+    const Geometry g = row_geometry(a->P, a->n, kWideFrom);
+    const size_t lds = a->n > kWideFrom ? 0 : (size_t)rows_per_block(a->n) * a->n * sizeof(double);
     if (a->rng == SX_RNG_PHILOX) {
         SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((pso_move_kernel<SX_RNG_PHILOX, LPR>), dim3(g.blocks), dim3(g.threads), lds,
                                                  (hipStream_t)stream, *a, lds != 0 ? 1 : 0))
@@ -252,7 +252,7 @@ extern "C" int sx_rows_select(const double *cand, int64_t ldc, const double *f, 
                               double *part_f, int64_t *part_i, void *stream) {
     SX_REQUIRE(cand && f && xin && xout && xfun && state && part_f && part_i, "sx_rows_select: null pointer");
     SX_REQUIRE(P >= 1 && n >= 1 && ldc >= n && ldx >= n, "sx_rows_select: bad shape");
-    const Geometry g = row_geometry(P, n);
+    const Geometry g = row_geometry(P, n, kWideFrom);
     SX_DISPATCH_LPR(n, hipLaunchKernelGGL((rows_select_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0, (hipStream_t)stream,
                                           cand, ldc, f, xin, xout, ldx, xfun, candfit, P, n, state, part_f, part_i))
     SX_LAUNCH_CHECK();

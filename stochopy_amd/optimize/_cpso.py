@@ -10,16 +10,14 @@ best/termination kernel; the competitive restart (:405-426) is three small kerne
 (csrc/sx_pso.hip).
 """
 import ctypes as C
-
 import os
 
 import numpy as np
 
 from .. import _device, _lib, _rng
 from . import _common
-from ._helpers import OptimizeResult, register
-
-_CAPTURE_MODE = "thread_local"  # see parallel.World.CAPTURE_MODE: torch's NCCL watchdog may poll events while we capture
+from ._helpers import register
+from ._population import _PopulationRun
 
 __all__ = ["minimize"]
 
@@ -93,103 +91,29 @@ def minimize(
     return run.result()
 
 
-class _PsoRun:
+class _PsoRun(_PopulationRun):
+    MEMBERS, WHOLE = "particles", "swarm"
     CHECK_EVERY = 32  # philox mode: the host reads the device state every this many generations
     GRAPH_CHUNK = 16  # generations per hipGraph replay (2 or 5 kernel nodes each)
 
     def __init__(self, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, gamma, constraints, xtol, ftol, return_all,
                  verbosity, callback, rng, seed, workers, autorun=True, immediate=False):
-        self.fun_id, self.lower, self.upper = fun_id, lower, upper
-        self.external = None if isinstance(fun_id, int) else fun_id  # caller-supplied objective: move -> fun -> select
-        self.maxiter, self.P, self.n = maxiter, P, len(lower)
+        super().__init__("cpso" if gamma else "pso", fun_id, lower, upper, x0, maxiter, P, xtol, ftol, return_all, verbosity,
+                         callback, rng, seed, workers, immediate)
         self.w, self.c1, self.c2, self.gamma, self.constraints = w, c1, c2, gamma, constraints
-        self.xtol, self.ftol = xtol, ftol
-        self.return_all, self.verbosity, self.callback = return_all, verbosity, callback
-        self.rng, self.seed = rng, seed
-        self.world = None
-        self.Ptotal = P
-        self.row0 = 0
-        self.immediate = immediate  # pso_async: one sequential sweep per generation (csrc/sx_async.hip)
-        import os
-
-        if workers != 1 and rng != "philox":
-            workers = _common.replicated_workers("cpso" if gamma else "pso", workers,
-                                                 'rng="numpy-legacy" replays ONE host stream in the order of the whole swarm '
-                                                 '(rng="philox" shards: draws keyed by the global row)')
-        if workers != 1 or os.environ.get("SX_FORCE_SHARDED") == "1":  # env switch: a 1-rank group (tests)
-            from ..parallel import require_world
-
-            self.world = require_world(workers)
-            if rng != "philox":
-                raise ValueError('a sharded run needs rng="philox" (draws keyed by the global row; see parallel.py)')
-            self.row0, self.P = self.world.shard(P)  # self.P is the LOCAL swarm from here on
-            if gamma and P % self.world.size != 0:
-                # (PSO takes any popsize -- blocks of ceil(P / workers) rows, the last rank short; the competitive restart's
-                # swarm-wide selection gathers equal [pbestfit | radii] segments per rank)
-                raise ValueError(f"cpso with workers={self.world.size}: popsize={P} must be a multiple of workers (pso, de, "
-                                 "cmaes and vdcma take any popsize)")
-            if immediate:
-                raise ValueError("immediate updating is a single-GPU sweep")
-        if immediate and self.external is not None:
-            raise ValueError("immediate updating evaluates particles one by one inside the sweep kernel: "
-                             "only the factory objectives can do that")
-        self.x0 = x0
+        # pso_async assigns X[i] row by row, i.e. works in place on the caller's x0 (cpso/_cpso.py:389)
+        self.x0_in_place = immediate
+        if self.world is not None and gamma and P % self.world.size != 0:
+            # (PSO takes any popsize -- blocks of ceil(P / workers) rows, the last rank short; the competitive restart's
+            # swarm-wide selection gathers equal [pbestfit | radii] segments per rank)
+            raise ValueError(f"cpso with workers={self.world.size}: popsize={P} must be a multiple of workers (pso, de, "
+                             "cmaes and vdcma take any popsize)")
         self.ctx = _device.Context()
-        self._graph = None
-        self._rccl_graph = None
-        self._rccl_graph_note = None
         # sharded swarm: the per-generation best travels by peer writes over xGMI (one one-workgroup kernel,
         # parallel.PeerExchange) when that transport passes its self-test on every rank, else by one all-gather
-        self.px, self.exchange, self.exchange_note = None, None, None
-        if self.world is not None:
-            self.exchange = "rccl"
-            if os.environ.get("SX_EXCHANGE", "auto") != "rccl":
-                from ..parallel import PeerExchange
-
-                self.px, self.exchange_note = PeerExchange.negotiate(
-                    self.ctx, self.world, self.n, float(os.environ.get("SX_XCHG_TIMEOUT_S", "20")))
-                if self.px is not None:
-                    self.exchange = "p2p"
-                elif os.environ.get("SX_EXCHANGE") == "p2p":
-                    raise RuntimeError(f"SX_EXCHANGE=p2p is not available: {self.exchange_note}")
+        self.px, self.exchange, self.exchange_note = self._negotiate_exchange()
         if autorun:
-            t = _device.torch()
-            with t.cuda.stream(self.ctx.stream):
-                ok = False
-                try:
-                    self._run()
-                    ok = True
-                finally:
-                    try:
-                        if self.px is not None:
-                            # Peers may still be reading this rank's exchange / population memory (their last kernels,
-                            # remote donor rows): nobody unmaps or frees anything before EVERY rank has drained its
-                            # stream.  The meeting point is reached by failing ranks too (it carries a success flag):
-                            # a rank whose objective / callback raised makes its peers raise, not hang in a barrier.
-                            if ok:
-                                self.ctx.sync()
-                            if not self.world.all_agree(ok) and ok:
-                                raise RuntimeError("a peer rank failed during the run (its own exception says why)")
-                    finally:
-                        self.close()
-
-    def close(self):
-        if self._rccl_graph is not None:
-            self.ctx.sync()
-            self._rccl_graph = None
-        if self._graph is not None:
-            self.ctx.sync()
-            self.ctx.L.sx_graph_destroy(self._graph)
-            self._graph = None
-        if getattr(self, "_chain_graphs", None):
-            self.ctx.sync()
-            for g in self._chain_graphs.values():
-                self.ctx.L.sx_graph_destroy(g)
-            self._chain_graphs = {}
-        if self.px is not None:
-            self.ctx.sync()
-            self.px.close()
-            self.px = None
+            self._autorun()
 
     # ------------------------------------------------------------------ setup
     def _setup(self):
@@ -274,8 +198,6 @@ class _PsoRun:
         self.chain = bool(self.world is None and self.rng == "philox" and self.external is None and not self.immediate
                           and not self.gamma and self.callback is None and not self.return_all
                           and os.environ.get("SX_PSO_CHAIN", "0") == "1" and ctx.L.sx_pso_chain_supported(C.byref(a)))
-        self.launches = 0
-        self._chain_graphs = {}
         if self.chain:
             rpb = int(ctx.L.sx_rows_per_workgroup(n))
             # many cheap generations per look at the device (a look is a finalise-only launch + a synchronisation)
@@ -311,7 +233,7 @@ class _PsoRun:
             self.xall = ctx.empty((self.maxiter, rows, n))
             self.funall = ctx.empty((self.maxiter, rows))
             if self.nout > 0:
-                X1, f1 = self._whole_swarm()  # candfit == pbestfit for the initial swarm
+                X1, f1 = self._whole_population(1)  # candfit == pbestfit for the initial swarm
                 self.xall[0].copy_(X1[: self.nout])
                 self.funall[0].copy_(f1[: self.nout])
             else:
@@ -321,32 +243,20 @@ class _PsoRun:
         self.restarts = []
 
     # --------------------------------------------------------------- helpers
-    def _whole_swarm(self):
-        """(positions, their fitness) as the caller sees them: with workers > 1 every rank gathers all shards
-        (callbacks / return_all only)."""
-        if self.world is None:
-            return self.X, self.candfit
-        self.world.all_gather_rows(self.X, self.Xfull)
-        self.world.all_gather_rows(self.candfit, self.candfull)
-        return self.Xfull, self.candfull
+    def _population(self, it):
+        return self.X
 
-    def _record(self, it):
-        if not self.return_all:
-            return
-        X, cand = self._whole_swarm()
-        if self.nout > 0:
-            self.xall[it - 1].copy_(X[: self.nout])
-            self.funall[it - 1].copy_(cand[: self.nout])
-        else:
-            k = int(cand.argmin())
-            self.xall[it - 1, 0].copy_(X[k])
-            self.funall[it - 1, 0] = cand[k]
+    def _best_row(self, st):
+        """The swarm's best position (host copy)."""
+        return self._chain_row(st.reserved[1]) if self.chain else self.gbest.cpu().numpy()
 
-    def _partial_result(self, st):
-        res = OptimizeResult(x=self.gbest.cpu().numpy(), fun=st.gfit, nfev=st.it * self.Ptotal, nit=st.it)
-        if self.return_all:
-            res.update({"xall": self.xall[: st.it].cpu().numpy(), "funall": self.funall[: st.it].cpu().numpy()})
-        return res
+    def _settle_status(self, st):
+        """The chained kernel stops on `fun <= ftol` with status 1; _common.py:135-140 calls it 0 when the best moved
+        by <= xtol.  Both generations' best rows are still resident (nothing is produced after `done`)."""
+        status = int(st.status)
+        if self.chain and status == 1 and np.linalg.norm(self._chain_row(st.reserved[0]) - self._best_row(st)) <= self.xtol:
+            status = 0
+        return status
 
     def _generation(self):
         ctx = self.ctx
@@ -425,116 +335,50 @@ class _PsoRun:
         ctx.sync()  # d_rows / d_newx must outlive the kernel
         self.restarts.append((it, nw))
 
-    # ------------------------------------------------------------------ loop
-    def _run(self):
-        ctx = self.ctx
-        self._setup()
-        st = self.st
-        if self.callback is not None:
-            self.callback(self._whole_swarm()[0].cpu().numpy(), self._partial_result(st))
-        # return_all with in-kernel draws: history copies (cpso/_cpso.py:283-295) are device-side and ordered on
-        # the engine stream, so the host need not look at every generation
-        record_async = (self.return_all and self.rng == "philox" and self.callback is None and self.nout > 0
-                        and self.maxiter > 1)
-        stepwise = (self.rng == "numpy-legacy" or self.callback is not None or self.return_all) and not record_async
-        while not st.done:
-            if record_async:
-                for j in range(min(max(self.maxiter - st.it, 1), self.CHECK_EVERY)):
-                    self._generation()
-                    self._record(st.it + 1 + j)  # generations after convergence are no-ops; their slots are cut off
-                    if self.gamma:
-                        self._restart_device()
-                st = ctx.read_state(self.state)
-            elif stepwise:
-                self._generation()
-                self._record(st.it + 1)
-                st = ctx.read_state(self.state)
-                if self.callback is not None:
-                    self.callback(self._whole_swarm()[0].cpu().numpy(), self._partial_result(st))
-                if not st.done and self.gamma:
-                    if self.rng == "numpy-legacy":
-                        self._restart_host_order(st.it)
-                    else:
-                        self._restart_device()
-            elif self.immediate or self.external is not None:
-                # long sweeps: look after every few of them.  A caller's device objective between our kernels:
-                # chunks of generations captured into one graph (kernels + objective) and replayed, else eagerly
-                look = 8 if self.immediate else self.CHECK_EVERY
-                todo = min(max(self.maxiter - st.it, 1), look)
-                while self.external is not None and todo >= self.GRAPH_CHUNK and self._capture_sharded_chunk():
-                    self._rccl_graph.replay()
-                    todo -= self.GRAPH_CHUNK
-                for _ in range(todo):
-                    self._generation()
-                    if self.gamma:
-                        self._restart_device()
-                st = ctx.read_state(self.state)
+    def _after_generation(self, it):
+        """The competitive restart (cpso/_cpso.py:296-300, after the callback)."""
+        if self.gamma:
+            if self.rng == "numpy-legacy":
+                self._restart_host_order(it)
             else:
-                self.enqueue(min(max(self.maxiter - st.it, 1), self.CHECK_EVERY))
-                st = self.read_state()
-                if self.px is not None and self.px.failed():
-                    raise RuntimeError("peer exchange timed out: a rank did not reach the generation the others "
-                                       "were waiting for (SX_XCHG_TIMEOUT_S)")
-        self.st = st
-        status = int(st.status)
-        xbest = self.gbest.cpu().numpy()
-        if self.chain:
-            xbest = self._chain_row(st.reserved[1])
-            # the chained kernel stops on `fun <= ftol` with status 1; _common.py:135-140 calls it 0 when the best moved
-            # by <= xtol.  Both generations' best rows are still resident (nothing is produced after `done`).
-            if status == 1 and np.linalg.norm(self._chain_row(st.reserved[0]) - xbest) <= self.xtol:
-                status = 0
-        res = OptimizeResult(
-            x=xbest,
-            success=status >= 0,
-            status=status,
-            message=_common.messages[status],
-            fun=float(st.gfit),
-            nfev=int(st.it) * self.Ptotal,
-            nit=int(st.it),
-        )
-        if self.return_all:
-            res.update({"xall": self.xall[: st.it].cpu().numpy(), "funall": self.funall[: st.it].cpu().numpy()})
-        # pso_async assigns X[i] row by row, i.e. works in place on the caller's x0 (cpso/_cpso.py:389)
-        if self.immediate and isinstance(self.x0, np.ndarray) and self.x0.dtype == np.float64:
-            self.x0[...] = self.X.cpu().numpy()
-        if self.rng == "numpy-legacy":
-            self.stream.sync_back()
-        ctx.sync()
-        # (peer exchange: the one meeting point of all ranks -- success flag included -- is `all_agree` in the caller's
-        #  `finally`; a barrier here would pair with a failing rank's all_gather there: mismatched collectives)
-        self._res = res
+                self._restart_device()
+
+    # ------------------------------------------------------------------ loop
+    def _enqueue_external(self, remaining):
+        """A caller's device objective between our kernels: chunks of generations captured into one graph (kernels +
+        objective) and replayed, else eagerly."""
+        todo = min(remaining, self.CHECK_EVERY)
+        while todo >= self.GRAPH_CHUNK and self._capture_sharded_chunk():
+            self._rccl_graph.replay()
+            todo -= self.GRAPH_CHUNK
+        for _ in range(todo):
+            self._generation()
+            if self.gamma:
+                self._restart_device()
+
+    def _enqueue_and_look(self, st, remaining):
+        self.enqueue(min(remaining, self.CHECK_EVERY))
+        return self.read_state()
 
     # ---- chained mode (one kernel per generation) ----
     def _chain_launch(self, parity, finalize_only):
         _lib.check(self.ctx.L.sx_pso_chain_launch(C.byref(self.args), _device.ptr(self.best_rows), parity, finalize_only,
                                                   self.ctx.stream_ptr), "sx_pso_chain_launch")
 
-    def _chain_graph(self, par, size):
-        key = (par, size)
-        if key not in self._chain_graphs:
-            g = C.c_void_p()
-            _lib.check(self.ctx.L.sx_pso_chain_graph_create(C.byref(self.args), _device.ptr(self.best_rows), size, par,
-                                                            C.byref(g)), "sx_pso_chain_graph_create")
-            self._chain_graphs[key] = g
-        return self._chain_graphs[key]
+    def _create_chain_graph(self, par, size):
+        g = C.c_void_p()
+        _lib.check(self.ctx.L.sx_pso_chain_graph_create(C.byref(self.args), _device.ptr(self.best_rows), size, par, C.byref(g)),
+                   "sx_pso_chain_graph_create")
+        return g
 
-    def _enqueue_chain(self, ngen):
-        while ngen >= self.GRAPH_CHUNK:  # (GRAPH_CHUNK is even: a replay leaves the launch parity where it found it)
-            _lib.check(self.ctx.L.sx_graph_launch(self._chain_graph(self.launches & 1, self.GRAPH_CHUNK),
-                                                  self.ctx.stream_ptr), "sx_graph_launch")
-            self.launches += self.GRAPH_CHUNK
-            ngen -= self.GRAPH_CHUNK
-        for _ in range(ngen):
-            self._chain_launch(self.launches & 1, 0)
-            self.launches += 1
+    @staticmethod
+    def plan_chain(ngen, chunk):
+        """Whole `chunk`-generation graphs (chunk is even: a replay leaves the launch parity where it found it), then one
+        eager launch per generation left (a list of graph lengths, 0 = one eager launch)."""
+        return [chunk] * (ngen // chunk) + [0] * (ngen % chunk)
 
-    def read_state(self):
-        """Host view of the run: (chained mode) finalise the last generation into state[2], then read it."""
-        if not self.chain:
-            return self.ctx.read_state(self.state)
-        self._chain_launch(self.launches & 1, 1)
-        return self.ctx.read_state(self.state[16:24])
+    def _chain_plan(self, ngen):
+        return self.plan_chain(ngen, self.GRAPH_CHUNK)
 
     def _chain_row(self, rec):
         """The best row a record points to: best_rows[q][workgroup of the row]."""
@@ -573,8 +417,6 @@ class _PsoRun:
     def _capture_sharded_chunk(self):
         """GRAPH_CHUNK sharded generations (kernels + all-gathers) as one graph; False if that is not possible
         (gloo stages through the host; SX_RCCL_GRAPH=0; a failed capture) -- same collectives either way."""
-        import os
-
         if self._rccl_graph is not None:
             return True
         if (self._rccl_graph_note is not None or (self.world is not None and self.world.backend != "nccl")
@@ -582,25 +424,13 @@ class _PsoRun:
                 or (self.external is not None and (os.environ.get("SX_EXT_GRAPH") == "0"
                                                    or not getattr(self.external, "capturable", True)))):
             return False
-        t = _device.torch()
-        try:
-            self.ctx.sync()
-            if self.world is not None:
-                self.world.quiesce_for_capture(self.ctx)
-            g = t.cuda.CUDAGraph()
-            with t.cuda.graph(g, stream=self.ctx.stream, capture_error_mode=_CAPTURE_MODE):
-                for _ in range(self.GRAPH_CHUNK):
-                    self._generation()
-                    if self.gamma:
-                        self._restart_device()
-            self._rccl_graph = g
-            return True
-        except Exception as e:  # capture is an optimisation, never a requirement
-            self._rccl_graph_note = f"graph capture of the rccl path failed: {e}"
-            return False
+        self._rccl_graph = self._capture(self.GRAPH_CHUNK, self._generation_and_restart, "_rccl_graph_note")
+        return self._rccl_graph is not None
 
-    def result(self):
-        return self._res
+    def _generation_and_restart(self):
+        self._generation()
+        if self.gamma:
+            self._restart_device()
 
 
 register("cpso", minimize)

@@ -16,9 +16,8 @@ import numpy as np
 
 from .. import _device, _lib, _rng
 from . import _common
-from ._helpers import OptimizeResult, register
-
-_CAPTURE_MODE = "thread_local"  # see parallel.World.CAPTURE_MODE: torch's NCCL watchdog may poll events while we capture
+from ._helpers import register
+from ._population import _PopulationRun
 
 __all__ = ["minimize"]
 
@@ -105,39 +104,19 @@ def minimize(
     return run.result()
 
 
-class _DeRun:
+class _DeRun(_PopulationRun):
     GRAPH_CHUNK = 50
+    TAIL_CHUNK = 10  # a second, short graph: runs of fewer than GRAPH_CHUNK generations are replayed too (even: parity)
+    _warned_island = False
 
     def __init__(self, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol, return_all,
                  verbosity, callback, rng, seed, workers, autorun=True, exchange=None, donors=None, immediate=False):
-        self.fun_id, self.lower, self.upper = fun_id, lower, upper
-        # a caller-supplied objective (factory.batched) cannot be fused: propose -> fun -> select
-        self.external = None if isinstance(fun_id, int) else fun_id
-        self.maxiter, self.P, self.n = maxiter, P, len(lower)
+        super().__init__("de", fun_id, lower, upper, x0, maxiter, P, xtol, ftol, return_all, verbosity, callback, rng, seed,
+                         workers, immediate)
         self.F, self.CR, self.strategy, self.constraints = F, CR, strategy, constraints
-        self.xtol, self.ftol = xtol, ftol
-        self.return_all, self.verbosity, self.callback = return_all, verbosity, callback
-        self.rng, self.seed = rng, seed
         self.k = _lib.DE_DONORS[strategy]
-        self.world = None
-        self.Ptotal = P
-        self.row0 = 0
-        self.immediate = immediate  # de_async: one sequential sweep per generation (csrc/sx_async.hip)
-        if workers != 1 and rng != "philox":
-            workers = _common.replicated_workers("de", workers, 'rng="numpy-legacy" replays ONE host stream in the order of the '
-                                                 'whole population (rng="philox" shards: draws keyed by the global row)')
-        if workers != 1 or os.environ.get("SX_FORCE_SHARDED") == "1":  # the env switch lets a 1-rank group
-            from ..parallel import require_world                         # exercise the exchange path (tests)
-
-            self.world = require_world(workers)
-            if rng != "philox":
-                raise ValueError('a sharded run needs rng="philox" (draws keyed by the global row; see parallel.py)')
-            self.row0, self.P = self.world.shard(P)  # this rank's rows; self.P is the LOCAL population from here on
-            if immediate:
-                raise ValueError("immediate updating is a single-GPU sweep")
-        if immediate and self.external is not None:
-            raise ValueError("immediate updating evaluates individuals one by one inside the sweep kernel: "
-                             "only the factory objectives can do that")
+        # the reference works in place on x0 (de/_de.py:208 + _common.py:128-129): mirrored on one GPU
+        self.x0_in_place = self.world is None
         if donors not in (None, "shard", "global"):
             raise ValueError('donors must be "shard" or "global"')
         self.global_donors = donors == "global" and self.world is not None
@@ -162,126 +141,56 @@ class _DeRun:
                 raise ValueError(f"strategy {strategy} draws {self.k} donors: too few rows "
                                  f"({'population' if self.global_donors else 'smallest shard'} of "
                                  f"{self.Ptotal if self.global_donors else smallest})")
-        self.x0 = x0
+        # Rows of more than wide_from() (2048) elements take the one-workgroup-per-row kernels (csrc/sx_wide.hip, two kernels per
+        # generation); the peer exchange and the global-donor gathers live in the chained kernel, which serves rows of up to
+        # NARROW_DIM (4096) elements: a run that ASKS for them keeps the wavefront-per-row kernels up to there (its args'
+        # wide_from; every other run, and every other method, uses the library's threshold).  exchange="auto" keeps the faster
+        # wide kernels and the all-gather on rows of 2049 ... 4096 elements.
+        needs_narrow = (self.world is not None and self.external is None
+                        and (donors == "global" or (exchange or os.environ.get("SX_EXCHANGE")) == "p2p"))
+        self.wide_from = _lib.NARROW_DIM if needs_narrow else 0
+        self.wide = self.n > (self.wide_from or _lib.wide_from())
+        self.npart = int(_lib.lib().sx_de_num_partials(self.P, self.n, self.wide_from))  # records per generation
         # single GPU + in-kernel draws + nothing to report per generation: one kernel per generation
         # ("chained finalize", include/stochopy_hip.h sx_de_chain_launch)
         # -- every wavefront re-reduces the per-workgroup records, so only while those are few (<= 512)
-        # Rows of more than wide_from() (2048) elements take the one-workgroup-per-row kernels (csrc/sx_wide.hip, two kernels per
-        # generation); the peer exchange and the global-donor gathers live in the chained kernel, which serves rows of up to
-        # NARROW_DIM (4096) elements: a run that ASKS for them on rows of 2049 ... 4096 elements gets the wavefront-per-row
-        # kernels for its duration (sx_set_wide_from; restored by close()).  exchange="auto" keeps the faster wide kernels and
-        # the all-gather there.
-        self._wide_from_prev = None
-        needs_narrow = (self.world is not None and self.external is None
-                        and (donors == "global" or (exchange or os.environ.get("SX_EXCHANGE")) == "p2p"))
-        if needs_narrow and _lib.wide_from() < self.n <= _lib.NARROW_DIM:
-            self._wide_from_prev = int(_lib.lib().sx_set_wide_from(_lib.NARROW_DIM))
-        try:
-            npart = int(_lib.lib().sx_num_partials(self.P, self.n))
-            self.wide = self.n > _lib.wide_from()
-            self.chain = (rng == "philox" and self.world is None and callback is None and not return_all
-                          and npart <= 512 and not immediate and self.external is None and not self.wide)
-            self.launches = 0
-            self.ctx = _device.Context()
-            # multi-GPU: the chained kernel with the peer exchange in its prologue, if the transport checks out
-            self.px = None
-            self.exchange = None
-            if self.world is not None:
-                exchange = exchange or os.environ.get("SX_EXCHANGE") or "auto"
-                if exchange not in ("auto", "p2p", "rccl"):
-                    raise ValueError('exchange must be "auto", "p2p" or "rccl"')
-                self.exchange, self.exchange_note = "rccl", None
-                if self.external is not None:
-                    if exchange == "p2p" or self.global_donors:
-                        raise ValueError("a caller-supplied objective runs between kernels: the peer exchange lives "
-                                         'inside the fused generation kernel (use exchange="rccl", donors="shard")')
-                    exchange = "rccl"
-                if self.wide:  # the peer exchange lives in the chained kernel, which serves rows of <= NARROW_DIM elements
-                    if exchange == "p2p" or self.global_donors:
-                        raise ValueError(f"rows of {self.n} elements (> {_lib.NARROW_DIM}) exchange the global best with one "
-                                         'all-gather per generation (exchange="rccl", donors="shard")')
-                    exchange = "rccl"
-                if exchange != "rccl":
-                    from ..parallel import PeerExchange
-
-                    timeout = float(os.environ.get("SX_XCHG_TIMEOUT_S", "20"))
-                    self.px, self.exchange_note = PeerExchange.negotiate(self.ctx, self.world, self.n, timeout)
-                    if self.px is not None:
-                        self.exchange, self.chain = "p2p", True
-                    elif exchange == "p2p":
-                        raise RuntimeError(f'exchange="p2p" is not available: {self.exchange_note}')
-                if self.global_donors and self.px is None:
-                    raise RuntimeError('donors="global" needs the peer exchange (exchange="p2p"/"auto"): '
-                                       f'{self.exchange_note or "it was switched off"}')
-            self._graph = None
-            self._chain_graphs = {}
-            self._tail_seen = {}
-            self._ext_graphs, self._ext_graph_note = {}, None
-            self._shard_calls = None
-            self._rccl_graph = None
-            self._rccl_graphs, self._rccl_tail_seen = {}, {}
-            self._rccl_graph_note = None
-            if autorun:
-                t = _device.torch()
-                with t.cuda.stream(self.ctx.stream):
-                    ok = False
-                    try:
-                        self._run()
-                        ok = True
-                    finally:
-                        try:
-                            if self.px is not None:
-                                # Peers may still be reading this rank's exchange / population memory (their last kernels,
-                                # remote donor rows): nobody unmaps or frees anything before EVERY rank has drained its
-                                # stream.  The meeting point is reached by failing ranks too (it carries a success flag):
-                                # a rank whose objective / callback raised makes its peers raise, not hang in a barrier.
-                                if ok:
-                                    self.ctx.sync()
-                                if not self.world.all_agree(ok) and ok:
-                                    raise RuntimeError("a peer rank failed during the run (its own exception says why)")
-                        finally:
-                            self.close()
-        except BaseException:
-            self._restore_wide_from()
-            raise
-
-    def _restore_wide_from(self):
-        if self._wide_from_prev is not None:
-            _lib.lib().sx_set_wide_from(self._wide_from_prev)
-            self._wide_from_prev = None
+        self.chain = (rng == "philox" and self.world is None and callback is None and not return_all
+                      and self.npart <= 512 and not immediate and self.external is None and not self.wide)
+        self.ctx = _device.Context()
+        # multi-GPU: the chained kernel with the peer exchange in its prologue, if the transport checks out
+        if self.world is not None:
+            exchange = exchange or os.environ.get("SX_EXCHANGE") or "auto"
+            if exchange not in ("auto", "p2p", "rccl"):
+                raise ValueError('exchange must be "auto", "p2p" or "rccl"')
+            if self.external is not None and (exchange == "p2p" or self.global_donors):
+                raise ValueError("a caller-supplied objective runs between kernels: the peer exchange lives "
+                                 'inside the fused generation kernel (use exchange="rccl", donors="shard")')
+            if self.wide and (exchange == "p2p" or self.global_donors):
+                # the peer exchange lives in the chained kernel, which serves rows of <= NARROW_DIM elements
+                raise ValueError(f"rows of {self.n} elements (> {_lib.NARROW_DIM}) exchange the global best with one "
+                                 'all-gather per generation (exchange="rccl", donors="shard")')
+            if self.external is not None or self.wide:
+                exchange = "rccl"
+        self.px, self.exchange, self.exchange_note = self._negotiate_exchange(exchange)
+        if self.px is not None:
+            self.chain = True
+        if self.global_donors and self.px is None:
+            raise RuntimeError('donors="global" needs the peer exchange (exchange="p2p"/"auto"): '
+                               f'{self.exchange_note or "it was switched off"}')
+        self._tail_seen = {}
+        self._shard_calls = None
+        self._rccl_tail_seen = {}
+        if autorun:
+            self._autorun()
 
     def close(self):
-        if self._wide_from_prev is not None:
-            self.ctx.sync()
-            self._restore_wide_from()
-        if self._rccl_graph is not None or self._ext_graphs:
-            self.ctx.sync()
-            self._rccl_graph = None
-            self._rccl_graphs = {}
-            self._ext_graphs = {}
-        if self._graph is not None:
-            self.ctx.L.sx_graph_destroy(self._graph)
-            self._graph = None
-        for g in self._chain_graphs.values():
-            self.ctx.L.sx_graph_destroy(g)
-        self._chain_graphs = {}
-        if self.px is not None:
-            self.ctx.sync()
-            if self.global_donors:
-                self.bufs = None  # views of the shared allocation that px.close() releases
-            self.px.close()
-            self.px = None
+        if self.global_donors and self.px is not None:
+            self.bufs = None  # views of the shared allocation that px.close() releases
+        super().close()
 
     def read_state(self):
-        """Host view of the run: (chained mode) finalise the last generation into state[2], then read it."""
-        ctx = self.ctx
-        if not self.chain:
-            return ctx.read_state(self.state)
-        self._chain_launch(self.launches & 1, 1)
-        st = ctx.read_state(self.state[16:24])
-        if self.px is not None and self.px.failed():
-            raise RuntimeError("peer exchange timed out: a rank did not reach the generation the others "
-                               "were waiting for (SX_XCHG_TIMEOUT_S)")
+        st = super().read_state()
+        self.it_enq = int(st.it)  # (generations after convergence are no-ops: the device's count is the one to go on with)
         return st
 
     def _chain_launch(self, parity, finalize_only):
@@ -293,29 +202,22 @@ class _DeRun:
             _lib.check(ctx.L.sx_de_chain_launch(C.byref(self.args), parity, finalize_only, ctx.stream_ptr),
                        "sx_de_chain_launch")
 
-    _warned_island = False
-    TAIL_CHUNK = 10  # a second, short graph: runs of fewer than GRAPH_CHUNK generations are replayed too (even: parity)
-
-    def _chain_graph(self, par, size=None):
-        size = size or self.GRAPH_CHUNK
-        key = (par, size)
-        if key not in self._chain_graphs:
-            g = C.c_void_p()
-            if self.px is not None:
-                _lib.check(self.ctx.L.sx_de_p2p_graph_create(C.byref(self.args), C.byref(self.px.args),
-                                                             size, par, C.byref(g)), "sx_de_p2p_graph_create")
-            else:
-                _lib.check(self.ctx.L.sx_de_chain_graph_create(C.byref(self.args), size, par, C.byref(g)),
-                           "sx_de_chain_graph_create")
-            self._chain_graphs[key] = g
-        return self._chain_graphs[key]
+    def _create_chain_graph(self, par, size):
+        g = C.c_void_p()
+        if self.px is not None:
+            _lib.check(self.ctx.L.sx_de_p2p_graph_create(C.byref(self.args), C.byref(self.px.args), size, par, C.byref(g)),
+                       "sx_de_p2p_graph_create")
+        else:
+            _lib.check(self.ctx.L.sx_de_chain_graph_create(C.byref(self.args), size, par, C.byref(g)),
+                       "sx_de_chain_graph_create")
+        return g
 
     def prepare_graphs(self):
         """Instantiate the hipGraph(s) up front (otherwise the first full chunk pays for it)."""
         if self.world is not None and not self.chain:
             return
         if self.chain:
-            self._chain_graph(0)  # chunk sizes are even: replays always start at parity 0 unless eager launches intervene
+            self._chain_graph(0, self.GRAPH_CHUNK)  # chunk sizes are even: replays always start at parity 0 unless eager launches intervene
             self._chain_graph(0, self.TAIL_CHUNK)
         elif self.rng == "philox" and self._graph is None:
             g = C.c_void_p()
@@ -344,16 +246,8 @@ class _DeRun:
         ngen %= tail
         return plan + [0] * ngen
 
-    def _enqueue_chain(self, ngen):
-        ctx = self.ctx
-        for size in self.plan_chain(ngen, self.launches, self._tail_seen, self.GRAPH_CHUNK, self.TAIL_CHUNK):
-            par = self.launches & 1
-            if size == 0:
-                self._chain_launch(par, 0)
-                self.launches += 1
-            else:
-                _lib.check(ctx.L.sx_graph_launch(self._chain_graph(par, size), ctx.stream_ptr), "sx_graph_launch")
-                self.launches += size
+    def _chain_plan(self, ngen):
+        return self.plan_chain(ngen, self.launches, self._tail_seen, self.GRAPH_CHUNK, self.TAIL_CHUNK)
 
     def _sharded_generation(self):
         """One generation on this rank's shard + the global-best exchange (parallel.py): two host calls into
@@ -382,18 +276,11 @@ class _DeRun:
         if (self._rccl_graph_note is not None or self.world.backend != "nccl"
                 or os.environ.get("SX_RCCL_GRAPH") == "0"):
             return False
-        t = _device.torch()
-        try:
-            self.world.quiesce_for_capture(self.ctx)
-            g = t.cuda.CUDAGraph()
-            with t.cuda.graph(g, stream=self.ctx.stream, capture_error_mode=_CAPTURE_MODE):
-                for _ in range(size):
-                    self._sharded_generation()
-            self._rccl_graphs[size] = self._rccl_graph = g
-            return True
-        except Exception as e:  # capture is an optimisation, never a requirement
-            self._rccl_graph_note = f"graph capture of the rccl path failed: {e}"
+        g = self._capture(size, self._sharded_generation, "_rccl_graph_note")
+        if g is None:
             return False
+        self._rccl_graphs[size] = self._rccl_graph = g
+        return True
 
     def enqueue(self, ngen):
         """Enqueue `ngen` generations on the engine stream without any host synchronisation.
@@ -459,7 +346,7 @@ class _DeRun:
             self.bufs[1].copy_(ctx.upload(X0))
         self.fit = ctx.empty((P,))
         self.candfit = ctx.empty((P,))
-        npart = int(ctx.L.sx_num_partials(P, n))
+        npart = self.npart
         self.part_f = ctx.empty((npart,))
         self.part_i = ctx.empty((npart,), dtype=t.int64)
         # initial evaluation and best (de/_de.py:212-218)
@@ -524,6 +411,7 @@ class _DeRun:
         # chained mode reads the best row straight from the population (row state.gbidx): no copy to maintain
         a.gbest = None if self.chain else self.gbest.data_ptr()
         a.P, a.ld, a.row0, a.n = P, n, self.row0, n
+        a.wide_from = self.wide_from
         a.fun_id, a.strategy = (self.fun_id if self.external is None else 0), _lib.DE_STRATEGIES[self.strategy]
         if self.external is not None:
             self.cand = ctx.empty((P, n))
@@ -575,30 +463,6 @@ class _DeRun:
         """Device view of generation `it`'s population (P, n)."""
         return self.bufs[1] if self.immediate else self.bufs[it & 1]
 
-    def _whole_population(self, it):
-        """(population, candidate fitness) of generation `it` as the caller sees them: with workers > 1 every
-        rank gathers all shards (callbacks / return_all only -- the reference's parallel backends also hand the
-        whole population to the callback on every rank)."""
-        X = self._population(it)
-        if self.world is None:
-            return X, self.candfit
-        self.world.all_gather_rows(X, self.Xfull)
-        self.world.all_gather_rows(self.candfit, self.candfull)
-        return self.Xfull, self.candfull
-
-    def _record(self, it):
-        """return_all bookkeeping for generation `it` (de/_de.py:270-278)."""
-        if not self.return_all:
-            return
-        X, cand = self._whole_population(it)
-        if self.nout > 0:
-            self.xall[it - 1].copy_(X[: self.nout])
-            self.funall[it - 1].copy_(cand[: self.nout])  # candidate fitness, de/_de.py:270-273
-        else:
-            k = int(cand.argmin())
-            self.xall[it - 1, 0].copy_(X[k])
-            self.funall[it - 1, 0] = cand[k]
-
     def _best_row(self, st):
         """The best individual of generation st.it (host copy)."""
         if self.px is not None:  # generation `it` was finalised from the records in slot parity (it-1)&1
@@ -619,12 +483,6 @@ class _DeRun:
             if np.linalg.norm(prev - self._best_row(st)) <= self.xtol:
                 status = 0
         return status
-
-    def _partial_result(self, st):
-        res = OptimizeResult(x=self._best_row(st), fun=st.gfit, nfev=st.it * self.Ptotal, nit=st.it)
-        if self.return_all:
-            res.update({"xall": self.xall[: st.it].cpu().numpy(), "funall": self.funall[: st.it].cpu().numpy()})
-        return res
 
     def _host_draws(self):
         """One generation of the numpy-legacy stream, in the reference's order."""
@@ -659,7 +517,7 @@ class _DeRun:
         _lib.check(L.sx_rows_select(p(self.cand), n, p(self.cand_f), p(cur), p(nxt), n, p(self.fit), p(self.candfit),
                                     self.P, n, p(self.state), p(self.part_f), p(self.part_i), ctx.stream_ptr),
                    "sx_rows_select")
-        npart = int(L.sx_num_partials(self.P, n))
+        npart = self.npart
         if self.world is None:
             _lib.check(L.sx_select_finalize(p(self.part_f), p(self.part_i), npart, p(self.bufs[0]), p(self.bufs[1]), n, n,
                                             p(self.gbest), p(self.state), self.maxiter, self.xtol, self.ftol,
@@ -683,23 +541,15 @@ class _DeRun:
         if (self._ext_graph_note is not None or self.rng != "philox" or not getattr(self.external, "capturable", True)
                 or (self.world is not None and self.world.backend != "nccl") or os.environ.get("SX_EXT_GRAPH") == "0"):
             return False
-        t = _device.torch()
         it0 = self.it_enq
-        try:
-            self.ctx.sync()
-            if self.world is not None:
-                self.world.quiesce_for_capture(self.ctx)
-            g = t.cuda.CUDAGraph()
-            with t.cuda.graph(g, stream=self.ctx.stream, capture_error_mode=_CAPTURE_MODE):
-                for _ in range(self.EXT_CHUNK):
-                    self._external_generation()
-            self._ext_graphs[parity] = g
-        except Exception as e:  # capture is an optimisation, never a requirement
-            self._ext_graph_note = f"graph capture around the objective failed: {e}"
+        g = self._capture(self.EXT_CHUNK, self._external_generation, "_ext_graph_note")
         self.it_enq = it0  # capturing ran nothing
-        return parity in self._ext_graphs
+        if g is not None:
+            self._ext_graphs[parity] = g
+        return g is not None
 
-    def _enqueue_external(self, ngen):
+    def _enqueue_external(self, remaining):
+        ngen = min(remaining, 4 * self.EXT_CHUNK)
         while ngen >= self.EXT_CHUNK and self._external_graph(self.it_enq & 1):
             self._ext_graphs[self.it_enq & 1].replay()
             self.it_enq += self.EXT_CHUNK
@@ -709,8 +559,10 @@ class _DeRun:
 
     def _generation(self):
         """One generation on the engine stream: the fused kernel + best/termination, or the sequential sweep;
-        with workers > 1 the shard's generation + the exchange of the global best."""
+        with workers > 1 the shard's generation + the exchange of the global best.  numpy-legacy: the host draws first."""
         ctx = self.ctx
+        if self.rng == "numpy-legacy":
+            self._host_draws()
         if self.external is not None:
             self._external_generation()
         elif self.px is not None:
@@ -724,71 +576,12 @@ class _DeRun:
             _lib.check(ctx.L.sx_de_generation(C.byref(self.args), 1, ctx.stream_ptr), "sx_de_generation")
 
     # ------------------------------------------------------------------ loop
-    def _run(self):
-        ctx = self.ctx
-        self._setup()
-        st = self.st
-        if self.callback is not None:
-            self.callback(self._whole_population(1)[0].cpu().numpy(), self._partial_result(st))
-        # return_all with in-kernel draws: the per-generation history copies (de/_de.py:270-278) are device-side
-        # and ordered on the engine stream, so the host need not look at every generation
-        record_async = (self.return_all and self.rng == "philox" and self.callback is None and self.nout > 0
-                        and self.maxiter > 1)
-        stepwise = (self.rng == "numpy-legacy" or self.callback is not None or self.return_all) and not record_async
-        while not st.done:
-            # maxiter <= 1: the reference still runs one generation before it tests `it >= maxiter`
-            remaining = max(self.maxiter - st.it, 1)
-            if record_async:
-                for j in range(min(remaining, 32)):
-                    self._generation()
-                    self._record(st.it + 1 + j)  # generations after convergence are no-ops; their slots are cut off
-                st = self.read_state()
-                self.it_enq = int(st.it)
-            elif stepwise:
-                if self.rng == "numpy-legacy":
-                    self._host_draws()
-                self._generation()
-                self._record(st.it + 1)
-                st = self.read_state()
-                self.it_enq = int(st.it)
-                if self.callback is not None:
-                    self.callback(self._whole_population(st.it)[0].cpu().numpy(), self._partial_result(st))
-            elif self.immediate:  # sweeps are long (P sequential individuals): look after every few of them
-                for _ in range(min(remaining, 8)):
-                    self._generation()
-                st = ctx.read_state(self.state)
-            elif self.external is not None:  # kernels and the caller's objective, queued on the engine stream
-                self._enqueue_external(min(remaining, 4 * self.EXT_CHUNK))
-                st = self.read_state()
-                self.it_enq = int(st.it)
-            elif self.chain and self.px is None:
-                st = self._run_chain_ahead(st)
-            else:
-                # termination is tested on the device every generation; the host looks every <=4 chunks
-                self.enqueue(min(remaining, 4 * self.GRAPH_CHUNK))
-                st = self.read_state()
-        self.st = st
-        status = self._settle_status(st)
-        res = OptimizeResult(
-            x=self._best_row(st),
-            success=status >= 0,
-            status=status,
-            message=_common.messages[status],
-            fun=float(st.gfit),
-            nfev=int(st.it) * self.Ptotal,
-            nit=int(st.it),
-        )
-        if self.return_all:
-            res.update({"xall": self.xall[: st.it].cpu().numpy(), "funall": self.funall[: st.it].cpu().numpy()})
-        # the reference works in place on x0 (de/_de.py:208 + _common.py:128-129): mirror that
-        if self.world is None and isinstance(self.x0, np.ndarray) and self.x0.dtype == np.float64:
-            self.x0[...] = self._population(st.it).cpu().numpy()
-        if self.rng == "numpy-legacy":
-            self.stream.sync_back()
-        ctx.sync()
-        # (peer exchange: the one meeting point of all ranks -- success flag included -- is `all_agree` in the caller's
-        #  `finally`; a barrier here would pair with a failing rank's all_gather there: mismatched collectives)
-        self._res = res
+    def _enqueue_and_look(self, st, remaining):
+        if self.chain and self.px is None:
+            return self._run_chain_ahead(st)
+        # termination is tested on the device every generation; the host looks every <=4 chunks
+        self.enqueue(min(remaining, 4 * self.GRAPH_CHUNK))
+        return self.read_state()
 
     def _run_chain_ahead(self, st):
         """One GPU, chained kernels: the host looks at the state every four replays as before, but one more replay is
@@ -820,8 +613,6 @@ class _DeRun:
                 return st
             first = False
 
-    def result(self):
-        return self._res
 
 
 register("de", minimize)

@@ -438,3 +438,58 @@ def nccl_single_rank_blocks_worker(rank, world, port, cfg, out_dir):
         np.save(os.path.join(out_dir, f"blocks_{rank}.npy"), np.array([out["blocks"][0], out["blocks"][1]]))
     finally:
         dist.destroy_process_group()
+
+
+def nccl_single_rank_two_runs_worker(rank, world, port, cfg, out_dir):
+    """One rank over RCCL, two live DE runs on rows of 2049 ... 4096 elements: A asks for the peer exchange (so it keeps the
+    wavefront-per-row kernels), B for the all-gather (the one-workgroup-per-row kernels, one record per row).  B is sized
+    while A is alive; its width and record count are checked before B launches anything; after A has closed, B runs a few
+    generations and must compute what the same run built alone computes."""
+    import torch
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["SX_FORCE_SHARDED"] = "1"
+    torch.cuda.set_device(0)
+    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", 0))
+    try:
+        from stochopy_amd import _lib
+        from stochopy_amd.optimize import _de
+
+        n, P, gens = cfg["n"], cfg["P"], cfg["gens"]
+
+        def make(exchange):
+            return _de._DeRun(_lib.FUN_IDS["rosenbrock"], np.full(n, -5.12), np.full(n, 5.12), None, 2**31 - 2, P, 0.5, 0.9,
+                              "best1bin", None, 0.0, -1.0, False, 1.0, None, "philox", cfg["seed"], 1, autorun=False,
+                              exchange=exchange)
+
+        def steps(run):
+            try:
+                with torch.cuda.stream(run.ctx.stream):
+                    run._setup()
+                    run.enqueue(gens)
+                    st = run.read_state()
+                    return int(st.it), float(st.gfit), run.bufs[st.it & 1].cpu().numpy().copy()
+            finally:
+                run.close()
+
+        a = make("p2p")
+        try:
+            with torch.cuda.stream(a.ctx.stream):
+                a._setup()
+            b = make("rccl")
+            try:  # host state only: nothing of B has been launched yet
+                assert a.exchange == "p2p" and not a.wide and a.args.wide_from == _lib.NARROW_DIM, (a.exchange, a.wide)
+                assert b.exchange == "rccl" and b.wide and b.npart == P, (b.exchange, b.wide, getattr(b, "npart", None))
+            except BaseException:
+                b.close()
+                raise
+        finally:
+            a.close()
+        beside = steps(b)
+        alone = steps(make("rccl"))
+        assert beside[:2] == alone[:2] and np.array_equal(beside[2], alone[2]), (beside[:2], alone[:2])
+        np.save(os.path.join(out_dir, f"two_runs_{rank}.npy"), np.array([beside[0], beside[1]]))
+    finally:
+        dist.destroy_process_group()

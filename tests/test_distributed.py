@@ -558,6 +558,19 @@ def test_rccl_path_graph_capture_single_rank():
 
 
 @pytest.mark.gpu
+def test_two_live_de_runs_keep_their_own_row_width():
+    """A DE run that asks for the peer exchange on rows of 3000 elements keeps the wavefront-per-row kernels; a second
+    run alive beside it, over the all-gather, takes the one-workgroup-per-row kernels (one record per row) all the same --
+    the width is a property of the run (sx_de_args.wide_from), not of the process -- and, once the first has closed,
+    computes bit for bit what it computes alone."""
+    from _dist_workers import nccl_single_rank_two_runs_worker
+
+    out = _spawn(nccl_single_rank_two_runs_worker, 1, {"n": 3000, "P": 40, "gens": 6, "seed": 21})
+    it, _ = np.load(os.path.join(out, "two_runs_0.npy"))
+    assert int(it) == 7
+
+
+@pytest.mark.gpu
 def test_rccl_path_blocks_of_twenty_generations_replay_a_captured_graph():
     """`bench.py --gpus N --steps 20` steps the RCCL transport in blocks of 20 generations (< GRAPH_CHUNK): from the second
     block on a block is ONE replay of a captured 20-generation graph (round 5; it used to be 20 eager generations of two

@@ -460,6 +460,37 @@ def test_chained_generations_are_planned_as_few_graph_replays():
     assert all(k[1] % 2 == 0 and 10 < k[1] < 50 for k in seen)
 
 
+def test_pso_chained_generations_are_whole_graphs_then_single_launches():
+    """_PsoRun's chained plan through the shared enqueue (_PopulationRun._enqueue_chain): whole GRAPH_CHUNK-generation
+    graphs, then one launch per generation left; a graph is the one built for the launch parity it starts at, and the
+    launches carry on with the parity the generations count gives them."""
+    import types
+
+    from stochopy_amd.optimize._cpso import _PsoRun
+
+    assert _PsoRun.plan_chain(70, 32) == [32, 32] + [0] * 6
+    assert _PsoRun.plan_chain(31, 32) == [0] * 31
+    assert _PsoRun.plan_chain(256, 32) == [32] * 8
+    events = []
+    run = _PsoRun.__new__(_PsoRun)  # the host logic only: the library calls are stand-ins
+    run.ctx = types.SimpleNamespace(L=types.SimpleNamespace(sx_graph_launch=lambda g, s: events.append(("graph",) + g) or 0),
+                                    stream_ptr=None)
+    run.launches, run._chain_graphs, run.GRAPH_CHUNK = 0, {}, 32
+    run._create_chain_graph = lambda par, size: (par, size)
+    run._chain_launch = lambda par, finalize_only: events.append(("launch", par, finalize_only))
+    expected, at = [], 0
+    for ngen in (70, 5, 64, 31, 33):
+        run._enqueue_chain(ngen)
+        for _ in range(ngen // 32):
+            expected.append(("graph", at & 1, 32))
+            at += 32
+        for _ in range(ngen % 32):
+            expected.append(("launch", at & 1, 0))
+            at += 1
+    assert events == expected and run.launches == at == 203
+    assert sorted(run._chain_graphs) == [(0, 32), (1, 32)]  # one graph per parity, built once
+
+
 @pytest.mark.parametrize("P,n", [(2, 3), (7, 5), (100, 70), (513, 2), (4096, 128)])
 def test_philox_latin_hypercube_oracle_properties(P, n):
     """The counter-based initial population of the throughput mode (oracle side; the HIP kernel is compared with it bit
