@@ -16,10 +16,16 @@ stream, behind an untimed K-step block that keeps the device busy while the time
 (--min-timed-seconds S > 0 repeats the block back to back until the region lasts S seconds, for profilers).
 `--dump-outputs DIR` writes what the timed steps computed -- the best row `x`, its value `fun` and the final
 `population` (a fixed, seeded sample of its rows when it exceeds 64 MB) -- as DIR/<name>.npy, float64; the run is
-seeded, so two builds can be compared output for output.  Also in the line:
-`minimize_wall` -- evals/s of a whole `minimize()` call after one warm-up call (host-side initial population
-included); `cpu_baseline` / `cpu_baseline_loky` with core count and CPU model; for N > 1 `c5` -- BASELINE config 5
-(DE n=1024, P=131072 in total = strong scaling) through both donor modes, with the number of ranks seen.
+seeded, so two builds can be compared output for output.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the line.  With N > 1 that
+includes both transports and the self-checks that come before them, since `value` is the faster transport's.
+`--full` adds what takes runs of its own: `roofline` -- the generation kernel timed alone over
+--kernel-timing-launches replays, against HBM peak; `minimize_wall` -- evals/s of a whole `minimize()` call after one
+warm-up call (host-side initial population included); `configs` -- BASELINE configs 2-5 and the other shapes;
+`cpu_baseline` / `cpu_baseline_loky` with core count and CPU model; for N > 1 `c5` -- BASELINE config 5 (DE n=1024,
+P=131072 in total = strong scaling) through both donor modes, with the number of ranks seen.  The --no-* switches
+leave parts of that out.
 """
 import argparse
 import json
@@ -313,11 +319,14 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--workload", default="de_rosenbrock_n128_p4096", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-minimize-wall", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C2 / C3a / C3b / C4 block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, minimize_wall, the other configs and the CPU baselines (N = 1), or "
+                         "c5 (N > 1); a plain run does only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-minimize-wall", action="store_true", help="with --full: skip minimize_wall")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C2 / C3a / C3b / C4 block")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="CPU work spent on the baseline sample")
-    ap.add_argument("--kernel-timing-launches", type=int, default=400)
+    ap.add_argument("--kernel-timing-launches", type=int, default=400, help="with --full: launches the roofline times")
     ap.add_argument("--min-timed-seconds", type=float, default=0.0,
                     help="repeat the K-step block until the timed region lasts this long (default 0: exactly --steps steps)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -409,10 +418,12 @@ def main():
         return everyone[0]
 
     def measure(exchange, objective=objective, n=n, Ptotal=None, strategy=strategy, donors=os.environ.get("SX_DONORS") or "shard",
-                K=K, W=W, kernel_launches=args.kernel_timing_launches, min_seconds=args.min_timed_seconds, dump=None):
+                K=K, W=W, kernel_launches=args.kernel_timing_launches if args.full else 0,
+                min_seconds=args.min_timed_seconds, dump=None):
         """One resident run: W warm-up steps, then ONE timed block of K steps -- or, with min_seconds > 0, the block
         repeated back to back until the timed region lasts that long.  Ptotal None: weak scaling (every GPU owns P rows
-        of a global population of world*P; same seed on every rank).  dump: a directory for dump_outputs()."""
+        of a global population of world*P; same seed on every rank).  dump: a directory for dump_outputs().
+        kernel_launches > 0: the generation kernel is then timed alone for the roofline (kern_ms None otherwise)."""
         lower, upper = np.full(n, -5.12), np.full(n, 5.12)
         run = _de._DeRun(_lib.FUN_IDS[objective], lower, upper, None, 2**31 - 2, Ptotal or world * P, 0.5, 0.9, strategy,
                          None, 0.0, -1.0, False, 1.0, None, "philox", 1234, world, autorun=False, exchange=exchange,
@@ -469,18 +480,20 @@ def main():
                 block_ms = sorted(evs[g].elapsed_time(evs[g + 1]) / group for g in range(blocks // group))
                 block_ms = block_ms or [dt * 1e3 / blocks]  # fewer blocks than one event group
 
-                # dominant kernel: HIP events on the engine stream around a replayed hipGraph of generation
-                # kernels (real generations, nothing else on the stream), average per launch
-                nl = max(1, kernel_launches // run.GRAPH_CHUNK) * run.GRAPH_CHUNK
-                ev0 = torch.cuda.Event(enable_timing=True)
-                ev1 = torch.cuda.Event(enable_timing=True)
-                run.enqueue(run.GRAPH_CHUNK)
-                ev0.record(ctx.stream)
-                run.enqueue(nl)
-                ev1.record(ctx.stream)
-                ctx.sync()
                 kernels_per_gen = 1 if run.chain else (2 if run.world is None else 3)
-                kern_ms = ev0.elapsed_time(ev1) / nl
+                nl, kern_ms = 0, None
+                if kernel_launches > 0:
+                    # dominant kernel: HIP events on the engine stream around a replayed hipGraph of generation
+                    # kernels (real generations, nothing else on the stream), average per launch
+                    nl = max(1, kernel_launches // run.GRAPH_CHUNK) * run.GRAPH_CHUNK
+                    ev0 = torch.cuda.Event(enable_timing=True)
+                    ev1 = torch.cuda.Event(enable_timing=True)
+                    run.enqueue(run.GRAPH_CHUNK)
+                    ev0.record(ctx.stream)
+                    run.enqueue(nl)
+                    ev1.record(ctx.stream)
+                    ctx.sync()
+                    kern_ms = ev0.elapsed_time(ev1) / nl
             barrier()  # no rank frees its exchange buffer while a peer may still write into it
         finally:
             run.close()
@@ -542,9 +555,9 @@ def main():
         transports = {"rccl": {"value": m_rccl["rows_total"] * m_rccl["steps_timed"] / m_rccl["dt"],
                                "ms_per_step": m_rccl["dt"] / m_rccl["steps_timed"] * 1e3}}
         m = m_rccl
-    def build_line(m, c5=None, transport_fallback=None):
-        run, dt, kern_ms, nl, kernels_per_gen = m["run"], m["dt"], m["kern_ms"], m["nl"], m["kernels_per_gen"]
-        value = m["rows_total"] * m["steps_timed"] / dt
+    def roofline(m):
+        """--full: the generation kernel timed alone (measure's kernel_launches) against HBM peak."""
+        kern_ms, nl, kernels_per_gen = m["kern_ms"], m["nl"], m["kernels_per_gen"]
         bytes_per_launch = algorithmic_bytes_per_eval(n, k) * P
         achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
         traffic, traffic_src = None, None
@@ -557,6 +570,23 @@ def main():
                     "_commit", "unrecorded")
             except Exception:
                 traffic = None
+        return {
+            "bound": "hbm",
+            "kernel": "de_generation_kernel<%s,philox>" % objective,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": bytes_per_launch,
+            "kernel_us": kern_ms * 1e3,
+            "timing": "HIP events on the engine stream around %d generations (%d kernel(s) each)" % (nl, kernels_per_gen),
+        }
+
+    def build_line(m, c5=None, transport_fallback=None):
+        run, dt = m["run"], m["dt"]
+        value = m["rows_total"] * m["steps_timed"] / dt
         line = {
             "metric": "objective-fn evals/sec",
             "value": value,
@@ -588,20 +618,9 @@ def main():
                 "donors": (None if run.world is None else "global (rows read from their owners over xGMI)"
                            if run.global_donors else "shard-local (island model with a shared global best)"),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": "de_generation_kernel<%s,philox>" % objective,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": bytes_per_launch,
-                "kernel_us": kern_ms * 1e3,
-                "timing": "HIP events on the engine stream around %d generations (%d kernel(s) each)" % (nl, kernels_per_gen),
-            },
         }
+        if m["kern_ms"] is not None:
+            line["roofline"] = roofline(m)
         # what actually ran, at the top level (the driver's SCALE run reads this, not the nested blocks): ranks seen, the
         # transport behind `value`, BOTH transports' values when N > 1, and why if the peer transport is not the one
         line["n_ranks_seen"] = dist.get_world_size() if dist is not None else 1
@@ -619,15 +638,17 @@ def main():
 
     # BASELINE config 5 with N > 1: DE n=1024, P=131072 IN TOTAL (strong scaling; the N = 1 point is
     # configs.C5_full_de_n1024_p131072_1gpu of the N = 1 line), shard-local donors through both transports and global
-    # donors (which need the peer mappings) -- RCCL first here too, every stage under the watchdog
+    # donors (which need the peer mappings) -- RCCL first here too, every stage under the watchdog.  Only with --full:
+    # without it c5 stays None and N > 1 measures the two transports of the headline alone
     c5 = None
     p2p_note = None
     if world > 1:
         c5kw = dict(objective="rosenbrock", n=1024, Ptotal=131072, strategy="best1bin", K=20, W=10, kernel_launches=50,
                     min_seconds=2.0)
-        c5 = {"workload": "de_rosenbrock_n1024_p131072 (total), best1bin", "n_ranks_seen": dist.get_world_size(),
-              "rows_per_gpu": 131072 // world, "scaling": "strong",
-              "n1_reference": "configs.C5_full_de_n1024_p131072_1gpu of the N = 1 line (profiles/r6_bench_N1.json)"}
+        if args.full:
+            c5 = {"workload": "de_rosenbrock_n1024_p131072 (total), best1bin", "n_ranks_seen": dist.get_world_size(),
+                  "rows_per_gpu": 131072 // world, "scaling": "strong",
+                  "n1_reference": "configs.C5_full_de_n1024_p131072_1gpu of the N = 1 line (profiles/r6_bench_N1.json)"}
 
         def c5_entry(r, mode):
             return {"value": 131072 * r["steps_timed"] / r["dt"], "unit": "evals/s",
@@ -638,13 +659,14 @@ def main():
 
         if rank == 0:
             state["line"] = build_line(m_rccl)
-        try:
-            r = guarded("c5 shard-local donors over rccl", 600.0, lambda: measure("rccl", donors="shard", **c5kw))
-            c5["donors_shard_rccl"] = c5_entry(r, "shard")
-        except Exception as e:  # noqa: BLE001
-            c5["donors_shard_rccl"] = {"error": str(e)[:300]}
-        if rank == 0:
-            state["line"] = build_line(m_rccl, c5)
+        if c5 is not None:
+            try:
+                r = guarded("c5 shard-local donors over rccl", 600.0, lambda: measure("rccl", donors="shard", **c5kw))
+                c5["donors_shard_rccl"] = c5_entry(r, "shard")
+            except Exception as e:  # noqa: BLE001
+                c5["donors_shard_rccl"] = {"error": str(e)[:300]}
+            if rank == 0:
+                state["line"] = build_line(m_rccl, c5)
         p2p_off = ("SX_BENCH_P2P=0" if os.environ.get("SX_BENCH_P2P", "1") == "0" else
                    "SX_EXCHANGE=rccl" if os.environ.get("SX_EXCHANGE") == "rccl" else None)
         if p2p_off is None:
@@ -664,18 +686,21 @@ def main():
                     m = m_p2p
                 if rank == 0:
                     state["line"] = build_line(m, c5)
-                for mode in ("shard", "global"):
-                    r, note = measure_p2p_or_none(f"c5 {mode} donors over p2p", 300.0, donors=mode, **c5kw)
-                    c5[f"donors_{mode}_p2p"] = c5_entry(r, mode) if r is not None else {"error": note}
-                    if rank == 0:
-                        state["line"] = build_line(m, c5)
+                if c5 is not None:
+                    for mode in ("shard", "global"):
+                        r, note = measure_p2p_or_none(f"c5 {mode} donors over p2p", 300.0, donors=mode, **c5kw)
+                        c5[f"donors_{mode}_p2p"] = c5_entry(r, mode) if r is not None else {"error": note}
+                        if rank == 0:
+                            state["line"] = build_line(m, c5)
             else:
                 transports["p2p"] = {"error": p2p_note}
-                c5["donors_global_p2p"] = {"error": "needs the peer mappings: " + (p2p_note or "")}
+                if c5 is not None:
+                    c5["donors_global_p2p"] = {"error": "needs the peer mappings: " + (p2p_note or "")}
         else:
             p2p_note = p2p_off + ("" if p2p_off.startswith("self-check") else " (switched off by the environment)")
             transports["p2p"] = {"skipped": p2p_note}
-            c5["donors_global_p2p"] = {"error": "needs the peer exchange: " + p2p_note}
+            if c5 is not None:
+                c5["donors_global_p2p"] = {"error": "needs the peer exchange: " + p2p_note}
         state["deadline"] = None
 
     run = m["run"]
@@ -683,14 +708,15 @@ def main():
     if rank == 0:
         line = build_line(m, c5, None if (transports is None or "value" in transports.get("p2p", {})) else
                           f"peer-write transport not used: {p2p_note}")
-        if world == 1 and not args.no_minimize_wall:
+        extras = world == 1 and args.full  # (a plain run stops at the headline)
+        if extras and not args.no_minimize_wall:
             line["minimize_wall"] = minimize_wall(objective, n, P, strategy)
-        if world == 1 and not args.no_configs:
+        if extras and not args.no_configs:
             try:
                 line["configs"] = other_configs()
             except Exception as e:  # noqa: BLE001  (keep the headline line whatever happens here)
                 line["configs"] = {"error": str(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(objective, n, min(P, 4096), strategy, args.cpu_baseline_seconds)
             line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
             try:  # the reference's own parallel-backend scheme, as a second reported baseline

@@ -1,5 +1,5 @@
-"""The bench.py contract (one JSON line with the driver's fields, roofline and cpu_baseline) and the
-__graft_entry__ smoke run, exercised end to end on the GPU."""
+"""The bench.py contract (one JSON line with the driver's fields; with --full also roofline, configs and cpu_baseline)
+and the __graft_entry__ smoke run, exercised end to end on the GPU."""
 import json
 import os
 import subprocess
@@ -22,8 +22,22 @@ def _run_bench(*extra, env=None):
     return json.loads(lines[0])
 
 
+_EXTRAS = {"roofline", "minimize_wall", "configs", "cpu_baseline", "cpu_baseline_loky", "gpu_over_cpu", "c5"}
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the run stops at the headline: the contract fields and the timed block, none of what takes runs of
+    its own (the kernel timed alone, minimize_wall, the other configs, the CPU baselines)."""
+    d = _run_bench()
+    assert d["metric"] == "objective-fn evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"]) == (1, 150, 50, "f64")
+    assert d["timed"]["blocks"] == 1 and d["timed"]["steps_timed"] == 150
+    assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    assert not _EXTRAS & set(d), sorted(_EXTRAS & set(d))
+
+
 def test_bench_line_has_the_contract_fields():
-    d = _run_bench("--cpu-baseline-seconds", "2")
+    d = _run_bench("--full", "--cpu-baseline-seconds", "2")
     assert d["metric"] == "objective-fn evals/sec" and d["unit"] == "evals/s" and d["higher_is_better"] is True
     assert (d["n_gpus"], d["steps"], d["warmup"], d["scaling"], d["dtype"], d["data"]) == (1, 150, 50, "weak", "f64",
                                                                                           "synthetic")
@@ -69,7 +83,7 @@ def test_bench_line_has_the_contract_fields():
 
 
 def test_bench_other_workload_and_smoke():
-    d = _run_bench("--no-cpu-baseline", "--no-configs", "--workload", "de_rosenbrock_n1024_p16384")
+    d = _run_bench("--full", "--no-cpu-baseline", "--no-configs", "--workload", "de_rosenbrock_n1024_p16384")
     assert "cpu_baseline" not in d and d["config"]["dim"] == 1024 and d["roofline"]["frac"] > 0.3
     import __graft_entry__
 
@@ -114,7 +128,7 @@ def test_bench_dump_outputs_sample_a_large_population(tmp_path):
 
 
 def test_bench_two_ranks_emits_the_c5_strong_scaling_figures():
-    """bench.py --gpus 2 as the driver launches it (torch.distributed.run, one process per rank) -- here with both
+    """bench.py --gpus 2 --full as the driver launches it (torch.distributed.run, one process per rank) -- here with both
     ranks on the one test GPU and gloo for the process group: the weak-scaled metric line plus BASELINE config 5
     (P = 131072 in total) through both donor modes, with the number of ranks the process group saw."""
     # NO external launcher: `python bench.py --gpus 2` re-executes itself under torch.distributed.run (VERDICT r2 #3: the
@@ -124,8 +138,8 @@ def test_bench_two_ranks_emits_the_c5_strong_scaling_figures():
     # own GPU and the default exchange applies.  Global donors need the peer mapping: reported as unavailable here.
     env = dict(os.environ, SX_BENCH_DEVICE="0", SX_BENCH_BACKEND="gloo", SX_EXCHANGE="rccl")
     env.pop("WORLD_SIZE", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--kernel-timing-launches", "50"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "20", "--warmup",
+                          "5", "--kernel-timing-launches", "50"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout

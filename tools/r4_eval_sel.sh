@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r4b
 timeout 2400 python -m pytest tests -m gpu -q -x -n 4 2>&1 | tail -3
 timeout 300 python tools/bench_eval.py 2>&1 | grep sx_eval > gpurun_out/r4b/eval_long_rows.txt
 cat gpurun_out/r4b/eval_long_rows.txt
-timeout 600 python bench.py --steps 2000 --warmup 200 2>/dev/null | python -c "
+timeout 600 python bench.py --full --steps 2000 --warmup 200 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('M', d['ms_per_step'], d['roofline']['frac'])

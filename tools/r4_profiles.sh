@@ -7,8 +7,8 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r4
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/bench_N1.json 2> $OUT/bench_N1.err < /dev/null; echo "bench rc=$?"
-python $R/bench.py --steps 20 --warmup 5 > $OUT/bench_N1_driver_args.json 2>> $OUT/bench_N1.err < /dev/null; echo "bench (driver args) rc=$?"
+python $R/bench.py --full > $OUT/bench_N1.json 2> $OUT/bench_N1.err < /dev/null; echo "bench rc=$?"
+python $R/bench.py --full --steps 20 --warmup 5 > $OUT/bench_N1_driver_args.json 2>> $OUT/bench_N1.err < /dev/null; echo "bench (driver args) rc=$?"
 prof() { # tag, command...
   tag=$1; shift
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$tag -o run -- "$@" > $OUT/prof_$tag.log 2>&1 < /dev/null
@@ -24,8 +24,8 @@ prof cpso_c3b python $R/tools/run_cpso_c3b.py
 # BASELINE config 5's shard shape (DE n=1024, P=16384) and the whole config on one GPU (P=131072) on the CURRENT binary
 prof de_n1024_p16384 python $R/bench.py $BA --workload de_rosenbrock_n1024_p16384 --steps 200 --warmup 20
 prof de_n1024_p131072 python $R/bench.py $BA --workload de_rosenbrock_n1024_p131072 --steps 40 --warmup 5
-python $R/bench.py $BA --workload de_rosenbrock_n1024_p16384 --steps 200 --warmup 20 > $OUT/bench_c5_shard.json 2>> $OUT/bench_N1.err < /dev/null
-python $R/bench.py $BA --workload de_rosenbrock_n1024_p131072 --steps 40 --warmup 5 > $OUT/bench_c5_full_1gpu.json 2>> $OUT/bench_N1.err < /dev/null
+python $R/bench.py --full $BA --workload de_rosenbrock_n1024_p16384 --steps 200 --warmup 20 > $OUT/bench_c5_shard.json 2>> $OUT/bench_N1.err < /dev/null
+python $R/bench.py --full $BA --workload de_rosenbrock_n1024_p131072 --steps 40 --warmup 5 > $OUT/bench_c5_full_1gpu.json 2>> $OUT/bench_N1.err < /dev/null
 pmc() { # tag counters -- command
   tag=$1; shift; ctr=$1; shift
   timeout 400 rocprofv3 --pmc $ctr --output-format csv -d $OUT/pmc_$tag -o run -- "$@" > $OUT/pmc_$tag.log 2>&1 < /dev/null
