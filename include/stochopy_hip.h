@@ -58,7 +58,7 @@ const char *sx_last_error(void);
 /* number of visible HIP devices (<0 on error); used by the loader to fail loudly */
 int sx_device_count(void);
 /* sizeof(sx_state / sx_de_args / sx_pso_args / sx_xchg_args) as compiled: lets a binding check its struct
- * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args; -1 otherwise) */
+ * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args; -1 otherwise) */
 int sx_struct_size(int which);
 
 /* ------------------------------------------------------------------------- *
@@ -678,6 +678,47 @@ void sx_mt_de_async_draws(sx_mt *g, int64_t P, int k, int n, int32_t *donors, in
 /* interchange with np.random.get_state()/set_state(): key[624], pos, has_gauss, cached_gaussian */
 void sx_mt_get_state(sx_mt *g, uint32_t *key, int *pos, int *has_gauss, double *gauss);
 void sx_mt_set_state(sx_mt *g, const uint32_t *key, int pos, int has_gauss, double gauss);
+
+/* ------------------------------------------------------------------------- *
+ * Samplers: many independent, device-resident Markov chains (csrc/sx_sample.hip).
+ * Replaces the sample loops of stochopy/sample/mcmc/_mcmc.py:104-156 (Metropolis-Hastings, one block of
+ * k = max(1, int(perc * ndim)) variables perturbed per sample) and stochopy/sample/hmc/_hmc.py:135-185 with
+ * numerical_gradient (:215-231): one row group per chain, the chain's rows in LDS for the whole launch, no
+ * exchange between chains.  One launch advances every chain by `steps` samples.
+ *
+ * Draws: rng = SX_RNG_HOST reads them from `normals` / `logu` (one chain: the reference's own stream, drawn by
+ * the host in the reference's order); SX_RNG_PHILOX makes them in the kernel, counter = (slot, chain, sample,
+ * purpose) -- a chain's draws depend on its index and the key only.
+ *
+ * Per-chain state (all DEVICE, written by the launch that generates sample 0 and carried from launch to launch):
+ *   cur (C,n) current sample, fcur (C) its value, nacc (C) accepted proposals, nfeas (C) proposals that passed the
+ *   feasibility test, facc / iacc (C) best ACCEPTED value and its sample index (inf / 0 while nothing was accepted:
+ *   the reference's fmin / imin), fmin / imin (C) numpy's argmin over the samples so far (first NaN wins),
+ *   xbest (C,n) the sample the method reports as x: iacc's for mcmc, imin's for hmc.
+ * ------------------------------------------------------------------------- */
+enum { SX_SAMPLE_MCMC = 0, SX_SAMPLE_HMC = 1 };
+enum { SX_JAC_FINITE_DIFF = 0, SX_JAC_ANALYTIC = 1 };
+
+typedef struct sx_sample_args {
+    double *cur, *fcur, *facc, *fmin, *xbest;
+    int64_t *iacc, *imin, *nacc, *nfeas;
+    const double *x0;      /* initial samples, row stride x0_stride (0: one row for all chains); NULL: Philox uniform in the box */
+    double *xall, *funall; /* (C, maxiter, n) / (C, maxiter), or both NULL (return_all off) */
+    const double *lower, *upper, *step; /* (n); step = stepsize * 0.5 * (upper - lower), formed by the caller */
+    const double *normals; /* SX_RNG_HOST: mcmc (maxiter-1, k) block normals of samples 1.., hmc (maxiter-1, n) momenta */
+    const double *logu;    /* SX_RNG_HOST: (maxiter) log of the acceptance uniform of sample i (entry 0 unused) */
+    int64_t C, x0_stride, maxiter;
+    int32_t n, fun_id, method, rng, reject /* constraints="Reject" */, k /* mcmc block length */, nleap, jac;
+    double fd_step;        /* hmc finite_diff_abs_step */
+    uint32_t key0, key1;
+} sx_sample_args;
+
+/* samples [it0, it0 + steps) of every chain; it0 = 0 starts the chains (sample 0 is the initial point) */
+int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *stream);
+/* chains one workgroup carries for this method / row length (launch geometry; results do not depend on it) */
+int sx_sample_chains_per_workgroup(int method, int jac, int n);
+/* G[i,:] = analytic gradient of objective fun_id at X[i,:] (the hmc kernel's device functions), X / G (P,n) DEVICE */
+int sx_sample_gradient(int fun_id, const double *X, int64_t P, int n, double *G, void *stream);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,22 @@ class SxCmaArgs(C.Structure):
     ]
 
 
+SX_SAMPLE_MCMC, SX_SAMPLE_HMC = 0, 1
+SX_JAC_FINITE_DIFF, SX_JAC_ANALYTIC = 0, 1
+
+
+class SxSampleArgs(C.Structure):
+    _fields_ = [
+        ("cur", vp), ("fcur", vp), ("facc", vp), ("fmin", vp), ("xbest", vp),
+        ("iacc", vp), ("imin", vp), ("nacc", vp), ("nfeas", vp),
+        ("x0", vp), ("xall", vp), ("funall", vp), ("lower", vp), ("upper", vp), ("step", vp), ("normals", vp), ("logu", vp),
+        ("C", i64), ("x0_stride", i64), ("maxiter", i64),
+        ("n", i32), ("fun_id", i32), ("method", i32), ("rng", i32), ("reject", i32), ("k", i32), ("nleap", i32), ("jac", i32),
+        ("fd_step", f64),
+        ("key0", C.c_uint32), ("key1", C.c_uint32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/stochopy_hip.h declares
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
@@ -191,6 +207,9 @@ PROTOTYPES = {
     "sx_eigh_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(f64), vp]),
     "sx_eigh_set_refine": (C.c_int, [C.c_int]),
     "sx_eigh_set_flow": (C.c_int, [C.c_int]),
+    "sx_sample_run": (C.c_int, [C.POINTER(SxSampleArgs), i64, i64, vp]),
+    "sx_sample_chains_per_workgroup": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "sx_sample_gradient": (C.c_int, [C.c_int, vp, i64, C.c_int, vp, vp]),
     "sx_mt_create": (vp, [C.c_uint32]),
     "sx_mt_destroy": (None, [vp]),
     "sx_mt_seed": (None, [vp, C.c_uint32]),
@@ -236,7 +255,8 @@ def lib():
         fn.argtypes = args
     if handle.sx_abi_version() != 1:
         raise HipLibraryError("ABI version mismatch; rebuild the library")
-    for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs)):
+    for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs,
+                                    SxSampleArgs)):
         if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
             raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
                                   f"{C.sizeof(mirror)}; rebuild the library")

@@ -33,6 +33,7 @@ extern "C" int sx_struct_size(int which) {
         case 4: return (int)sizeof(sx_cma_state);
         case 5: return (int)sizeof(sx_cma_args);
         case 6: return (int)sizeof(sx_vd_args);
+        case 7: return (int)sizeof(sx_sample_args);
     }
     return -1;
 }

@@ -174,6 +174,11 @@ enum : uint32_t {
     kPurposeNaUniform = 7,  // NA: the double behind uniform(low, high) of (sample, axis)
     kPurposeInitJitter = 8, // initial population (Philox mode): the uniform inside the stratum, keyed by (row, element)
     kPurposeInitPerm = 9,   // ... and the keys of column j's stratum permutation (slot = j)
+    // the samplers' chains (sx_sample.hip): row = the chain, gen = the sample.  Elements use the rows' (slot, half) layout above
+    kPurposeSampleProposal = 10, // mcmc: the normal of variable e (used when e is in the sample's block): half 0 cosine, half 1 sine
+    kPurposeSampleMomentum = 11, // hmc: the momentum normal of element e, same halves
+    kPurposeSampleAccept = 12,   // the acceptance uniform: slot 0, first double of the call
+    kPurposeSampleInit = 13,     // the initial point (gen 0): the uniform of element e
 };
 
 // Element e of a row sits in lane l = e % LPR of the row's lanes at step q = e / LPR (LPR a power of two).
@@ -371,6 +376,91 @@ struct Obj<SX_FUN_STYBLINSKI_TANG> {  // benchmark.py:139-156
     }
     static __device__ __forceinline__ double finish(double sa, double, int n) {
         return 0.5 * sa + 39.16599 * (double)n;
+    }
+};
+
+// ---------------------------------------------------------------------------
+// Closed-form gradients of the seven objectives (hmc with jac="analytic", sx_sample.hip).  Grad<FUN>::REDUCE: the
+// element pass needs row totals first -- pre(x, e, a, b) gives element e's contribution to a sum (a) and to a second
+// total (b: a sum, or a product when BMUL).  elem(x, xp, xn, e, n, ra, rb) is dF/dx_e (xp / xn: the neighbours, 0
+// outside the row; ra / rb: the totals).  These are not restatements of reference code (the reference has no
+// gradients); the summation order of the totals is the row's butterfly, not numpy's.
+// ---------------------------------------------------------------------------
+template <int FUN>
+struct Grad;
+
+template <>
+struct Grad<SX_FUN_ACKLEY> {  // F = 20 + e - 20 exp(-0.2 sqrt(S1/n)) - exp(S2/n)
+    static constexpr bool REDUCE = true, BMUL = false;
+    static __device__ __forceinline__ void pre(double x, int, double &a, double &b) {
+        a = x * x;
+        b = cos(kTwoPi * x);
+    }
+    static __device__ __forceinline__ double elem(double x, double, double, int, int n, double ra, double rb) {
+        const double inv = 1.0 / (double)n;
+        const double r = sqrt(inv * ra);
+        const double g1 = r > 0.0 ? 4.0 * exp(-0.2 * r) * (x * inv / r) : 0.0;  // (the origin: the one-sided limits differ, 0 is their mean)
+        return g1 + exp(inv * rb) * (kTwoPi * inv) * sin(kTwoPi * x);
+    }
+};
+
+template <>
+struct Grad<SX_FUN_GRIEWANK> {  // F = 1 + S1/4000 - prod_j cos(x_j / sqrt(j+1))
+    static constexpr bool REDUCE = true, BMUL = true;
+    static __device__ __forceinline__ void pre(double x, int e, double &a, double &b) {
+        a = 0.0;
+        b = cos(x / sqrt((double)(e + 1)));
+    }
+    static __device__ __forceinline__ double elem(double x, double, double, int e, int, double, double rb) {
+        // the product without factor e is rb / cos(t) (a factor that is exactly zero is not handled: 0 * inf)
+        const double s = sqrt((double)(e + 1)), t = x / s;
+        return x / 2000.0 + (rb / cos(t)) * sin(t) / s;
+    }
+};
+
+template <>
+struct Grad<SX_FUN_QUARTIC> {
+    static constexpr bool REDUCE = false, BMUL = false;
+    static __device__ __forceinline__ void pre(double, int, double &a, double &b) { a = b = 0.0; }
+    static __device__ __forceinline__ double elem(double x, double, double, int e, int, double, double) {
+        return 4.0 * (double)(e + 1) * (x * x * x);
+    }
+};
+
+template <>
+struct Grad<SX_FUN_RASTRIGIN> {
+    static constexpr bool REDUCE = false, BMUL = false;
+    static __device__ __forceinline__ void pre(double, int, double &a, double &b) { a = b = 0.0; }
+    static __device__ __forceinline__ double elem(double x, double, double, int, int, double, double) {
+        return 2.0 * x + (10.0 * kTwoPi) * sin(kTwoPi * x);
+    }
+};
+
+template <>
+struct Grad<SX_FUN_ROSENBROCK> {  // F = sum_{e < n-1} 100 (x_{e+1} - x_e^2)^2 + (1 - x_e)^2
+    static constexpr bool REDUCE = false, BMUL = false;
+    static __device__ __forceinline__ void pre(double, int, double &a, double &b) { a = b = 0.0; }
+    static __device__ __forceinline__ double elem(double x, double xp, double xn, int e, int n, double, double) {
+        double g = 0.0;
+        if (e < n - 1) g = -400.0 * x * (xn - x * x) - 2.0 * (1.0 - x);
+        if (e > 0) g = g + 200.0 * (x - xp * xp);
+        return g;
+    }
+};
+
+template <>
+struct Grad<SX_FUN_SPHERE> {
+    static constexpr bool REDUCE = false, BMUL = false;
+    static __device__ __forceinline__ void pre(double, int, double &a, double &b) { a = b = 0.0; }
+    static __device__ __forceinline__ double elem(double x, double, double, int, int, double, double) { return 2.0 * x; }
+};
+
+template <>
+struct Grad<SX_FUN_STYBLINSKI_TANG> {
+    static constexpr bool REDUCE = false, BMUL = false;
+    static __device__ __forceinline__ void pre(double, int, double &a, double &b) { a = b = 0.0; }
+    static __device__ __forceinline__ double elem(double x, double, double, int, int, double, double) {
+        return 0.5 * ((4.0 * (x * x * x) - 32.0 * x) + 5.0);
     }
 };
 

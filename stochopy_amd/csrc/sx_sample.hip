@@ -1,0 +1,455 @@
+// Samplers (stochopy/sample): Metropolis-Hastings and Hamiltonian Monte-Carlo with many independent chains.
+//
+// A Markov chain is sequential, independent chains never talk to each other: one row group (lanes_per_row(n) lanes)
+// carries ONE chain for the whole launch.  The chain's rows -- current sample, proposal / position, momentum and the two
+// finite-difference copies -- live in that row group's slice of LDS, its scalars (current value, best values, counts)
+// in registers; there is no workgroup barrier, no grid barrier and no exchange.  A launch advances every chain by
+// `it1 - it0` samples and writes row i of xall / funall with streaming stores as it goes.  State that has to survive
+// from launch to launch (a run with a callback is one launch per sample) round-trips through sx_sample_args' per-chain
+// arrays unchanged, so cutting a run into launches does not change a bit of it.
+//
+// Draws: SX_RNG_HOST reads the reference's own stream from memory (normals, log of the acceptance uniform: the order
+// does not depend on the data as long as nothing is rejected for feasibility); SX_RNG_PHILOX keys every draw by
+// (slot, chain, sample, purpose) -- sx_device.hpp kPurposeSample* -- so a chain depends on its index and the key only.
+#include "sx_host.hpp"
+#include "sx_rowops.hpp"
+
+namespace sx {
+int make_plan_arg(int fun_id, int n, PlanArg *out);
+
+namespace {
+
+enum { kMcmc = 0, kHmcFd = 1, kHmcAnalytic = 2 };  // kernel variants
+
+// doubles of LDS one chain needs
+__host__ __device__ inline int sample_row_doubles(int variant, int n) {
+    const int S = gen_row_stride(n);
+    return variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S;
+}
+// waves per workgroup: the largest power of two with <= 16 chains and <= 64 KiB of LDS; one wave may need more than that
+// (hmc with finite differences on rows of ~2 048 elements: the launch then raises the kernel's dynamic-LDS limit)
+inline int sample_waves(int variant, int n) {
+    const int rpw = kWave / lanes_per_row(n);
+    const int fit = (64 * 1024) / (8 * sample_row_doubles(variant, n) * rpw);
+    int w = 1;
+    while (2 * w <= fit && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w <= kMaxWavesPerBlock) w *= 2;
+    return w;
+}
+
+template <int LPR>
+__device__ __forceinline__ double row_prod(double v) {
+#pragma unroll
+    for (int off = 1; off < LPR; off <<= 1) v *= __shfl_xor(v, off, kWave);
+    return v;
+}
+template <int LPR>
+__device__ __forceinline__ bool row_all(bool v) {
+    return row_min<LPR>(v ? 1.0 : 0.0) != 0.0;
+}
+
+// Standard normals of a row, in the row kernels' element layout (sx_device.hpp philox_u53, as cma_normals_kernel): element
+// e = LPR q + l belongs to call slot = (q >> 1) LPR + l and takes the cosine half (q even) or the sine half (q odd) of that
+// call's Box-Muller pair.  Elements e0 (q even) and e0 + LPR therefore share one call, one logarithm, one square root and one
+// angle -- and one lane: z0 / z1 are both of them.
+template <int LPR>
+__device__ __forceinline__ void philox_normal_pair(int e0, uint32_t chain, uint32_t gen, uint32_t purpose, uint32_t k0,
+                                                   uint32_t k1, double &z0, double &z1) {
+    const uint32_t slot = ((uint32_t)e0 / (2u * LPR)) * LPR + ((uint32_t)e0 & (LPR - 1u));
+    const U4 w = philox4x32_10(slot, chain, gen, purpose, k0, k1);
+    const double d0 = u53(w.x, w.y), d1 = u53(w.z, w.w);
+    const double rad = sqrt(-2.0 * log(1.0 - d0));
+    double sn, cs;
+    sincos_mid(kTwoPi * d1, sn, cs);
+    z0 = rad * cs;
+    z1 = rad * sn;
+}
+__device__ __forceinline__ double philox_log_accept(uint32_t chain, uint32_t gen, uint32_t k0, uint32_t k1) {
+    const U4 w = philox4x32_10(0u, chain, gen, kPurposeSampleAccept, k0, k1);
+    return log(u53(w.x, w.y));
+}
+
+// f(e, dF/dx_e) for every element this lane owns; Q complete and fenced by the caller
+template <int FUN, int LPR, class F>
+__device__ __forceinline__ void grad_apply(const double *Q, int n, int l, F &&f) {
+    using G = Grad<FUN>;
+    double ra = 0.0, rb = G::BMUL ? 1.0 : 0.0;
+    if constexpr (G::REDUCE) {
+        for (int e = l; e < n; e += LPR) {
+            double a, b;
+            G::pre(Q[e], e, a, b);
+            ra += a;
+            rb = combine<G::BMUL>(rb, b);
+        }
+        ra = row_sum<LPR>(ra);
+        rb = G::BMUL ? row_prod<LPR>(rb) : row_sum<LPR>(rb);
+    }
+    for (int e = l; e < n; e += LPR) {
+        const double x = Q[e];
+        const double xp = e > 0 ? Q[e - 1] : 0.0, xn = e < n - 1 ? Q[e + 1] : 0.0;
+        f(e, G::elem(x, xp, xn, e, n, ra, rb));
+    }
+}
+
+// the scalars of one chain (identical in every lane of its row group)
+struct ChainState {
+    double fcur, facc, fmin;
+    int64_t iacc, imin, nacc, nfeas;
+    __device__ __forceinline__ void load(const sx_sample_args &a, int64_t c) {
+        fcur = a.fcur[c], facc = a.facc[c], fmin = a.fmin[c];
+        iacc = a.iacc[c], imin = a.imin[c], nacc = a.nacc[c], nfeas = a.nfeas[c];
+    }
+    __device__ __forceinline__ void store(const sx_sample_args &a, int64_t c) const {
+        a.fcur[c] = fcur, a.facc[c] = facc, a.fmin[c] = fmin;
+        a.iacc[c] = iacc, a.imin[c] = imin, a.nacc[c] = nacc, a.nfeas[c] = nfeas;
+    }
+    __device__ __forceinline__ void start(double f0) {
+        fcur = f0, facc = __builtin_huge_val(), fmin = f0;
+        iacc = 0, imin = 0, nacc = 0, nfeas = 0;
+    }
+    // an accepted sample `it` of value f: mcmc/_mcmc.py:131-134, hmc/_hmc.py:167-172 (best ACCEPTED sample, plain <) and
+    // numpy's argmin over funall (hmc/_hmc.py:187: the first NaN wins, else the first minimum).  Returns which changed.
+    __device__ __forceinline__ void accept(double f, int64_t it, bool &acc_best, bool &arg_best) {
+        fcur = f;
+        nacc += 1;
+        acc_best = f < facc;
+        if (acc_best) facc = f, iacc = it;
+        arg_best = best_before(f, fmin);
+        if (arg_best) fmin = f, imin = it;
+    }
+};
+
+// the initial sample (mcmc/_mcmc.py:93, hmc/_hmc.py:124): the given x0, or uniform(lower, upper) = lower + (upper - lower) * u
+template <int LPR>
+__device__ __forceinline__ double initial_value(const sx_sample_args &a, int64_t c, int e) {
+    if (a.x0 != nullptr) return a.x0[c * a.x0_stride + e];
+    const double lo = a.lower[e];
+    return lo + (a.upper[e] - lo) * philox_u53(e, LPR, (uint32_t)c, 0u, kPurposeSampleInit, a.key0, a.key1);
+}
+
+template <int LPR>
+__device__ __forceinline__ bool row_in_box(const sx_sample_args &a, const double *U, int n, int l) {
+    bool in = true;
+    for (int e = l; e < n; e += LPR) {
+        const double v = U[e];
+        in = in && v >= a.lower[e] && v <= a.upper[e];
+    }
+    return row_all<LPR>(in);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Metropolis-Hastings (mcmc/_mcmc.py:104-156).  Sample i perturbs block (i-1) mod ceil(n/k) of k consecutive variables
+// (the last block is the shorter one when k does not divide n): randn(kb) * step, then rand() for the decision.
+// LDS per chain: X[n] (current sample) | U[gen_row_stride(n)] (proposal, in the objective's layout).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int FUN, int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx_sample_args a, const PlanArg plan,
+                                                                        int64_t it0, int64_t it1) {
+    extern __shared__ double lds[];
+    const RowIds<LPR> id(a.C);
+    const int n = a.n, l = id.l, k = a.k;
+    const int64_t c = id.rowc;
+    double *X = lds + (size_t)id.slot * sample_row_doubles(kMcmc, n);
+    double *U = X + n;
+    const bool host = a.rng == SX_RNG_HOST;
+    const int nblocks = (n + k - 1) / k;
+    ChainState st;
+    if (it0 > 0) {
+        st.load(a, c);
+        for (int e = l; e < n; e += LPR) X[e] = a.cur[c * n + e];
+    }
+    for (int64_t it = it0; it < it1; ++it) {
+        int j0 = 0, j1 = 0;
+        if (it == 0) {
+            for (int e = l; e < n; e += LPR) U[e] = initial_value<LPR>(a, c, e);
+        } else {
+            j0 = (int)((it - 1) % nblocks) * k;
+            j1 = j0 + k < n ? j0 + k : n;
+            for (int e0 = l; e0 < n; e0 += 2 * LPR) {  // element pairs (e0, e0 + LPR): one Box-Muller call
+                const int e1 = e0 + LPR;
+                const bool in0 = e0 >= j0 && e0 < j1, in1 = e1 >= j0 && e1 < j1;
+                double z0 = 0.0, z1 = 0.0;
+                if (host) {
+                    if (in0) z0 = a.normals[(it - 1) * k + (e0 - j0)];
+                    if (in1) z1 = a.normals[(it - 1) * k + (e1 - j0)];
+                } else if (in0 || in1) {
+                    philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
+                }
+                const double v0 = X[e0];
+                U[e0] = in0 ? v0 + z0 * a.step[e0] : v0;
+                if (e1 < n) {
+                    const double v1 = X[e1];
+                    U[e1] = in1 ? v1 + z1 * a.step[e1] : v1;
+                }
+            }
+        }
+        // (an infeasible proposal is evaluated too and its value dropped: the rows of a wave stay in step)
+        const double fU = row_objective<FUN, LPR, false, 0, 0>(U, n, plan, l);
+        bool xbest_changed = false;
+        if (it == 0) {
+            st.start(fU);
+            for (int e = l; e < n; e += LPR) X[e] = U[e];
+            xbest_changed = true;  // x = xall[0] while nothing was accepted
+        } else {
+            const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
+            bool accept = false;
+            if (feasible) {
+                st.nfeas += 1;
+                const double logu = host ? a.logu[it] : philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
+                const double d = st.fcur - fU;
+                accept = (d < 0.0 ? d : 0.0) > logu;  // Python's min(0.0, d): a NaN d gives 0.0
+            }
+            if (accept) {
+                bool arg_best;
+                st.accept(fU, it, xbest_changed, arg_best);
+                for (int e = l + ((j0 - l + LPR - 1) / LPR) * LPR; e < j1; e += LPR) X[e] = U[e];
+            }
+        }
+        if (id.active) {
+            if (a.xall != nullptr) {
+                double *dst = a.xall + (c * a.maxiter + it) * n;
+                for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
+                if (l == 0) st_stream(a.funall + c * a.maxiter + it, st.fcur);
+            }
+            if (xbest_changed)
+                for (int e = l; e < n; e += LPR) a.xbest[c * n + e] = X[e];
+        }
+    }
+    if (id.active) {
+        for (int e = l; e < n; e += LPR) a.cur[c * n + e] = X[e];
+        if (l == 0) st.store(a, c);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Hamiltonian Monte-Carlo (hmc/_hmc.py:135-185).  Per sample: momentum p = randn(n); nleap + 2 gradients and nleap + 1
+// position steps (half momentum step, position step, nleap x (momentum step, position step), half momentum step);
+// d = U0 - U + K0 - K; rand() for the decision.  U0 = fun(q0) is the current value (the reference evaluates it again).
+// ANALYTIC: sx_device.hpp Grad<FUN>.  Finite differences (numerical_gradient, :215-231): x1 / x2 are copies of q whose
+// component i is moved by -h / +h and moved BACK in place, so later components see the rounding of earlier ones.
+// LDS per chain: X[n] current sample | Q[S] position | P[n] momentum | finite differences: X1[S] | X2[S]
+// (S = gen_row_stride(n): the objective's layout).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int FUN, int LPR, bool ANALYTIC>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_sample_args a, const PlanArg plan,
+                                                                       int64_t it0, int64_t it1) {
+    extern __shared__ double lds[];
+    const RowIds<LPR> id(a.C);
+    const int n = a.n, l = id.l, S = gen_row_stride(n);
+    const int64_t c = id.rowc;
+    double *X = lds + (size_t)id.slot * sample_row_doubles(ANALYTIC ? kHmcAnalytic : kHmcFd, n);
+    double *Q = X + n;
+    double *Pm = Q + S;
+    double *X1 = Pm + n, *X2 = X1 + S;  // (finite differences only)
+    const bool host = a.rng == SX_RNG_HOST;
+    const double h = a.fd_step;
+    ChainState st;
+    if (it0 > 0) {
+        st.load(a, c);
+        for (int e = l; e < n; e += LPR) X[e] = a.cur[c * n + e];
+    }
+    for (int64_t it = it0; it < it1; ++it) {
+        double K0 = 0.0, K = 0.0;
+        if (it == 0) {
+            for (int e = l; e < n; e += LPR) Q[e] = initial_value<LPR>(a, c, e);
+        } else {
+            double s = 0.0;
+            for (int e0 = l; e0 < n; e0 += 2 * LPR) {
+                const int e1 = e0 + LPR;
+                double z0 = 0.0, z1 = 0.0;
+                if (host) {
+                    z0 = a.normals[(it - 1) * n + e0];
+                    if (e1 < n) z1 = a.normals[(it - 1) * n + e1];
+                } else {
+                    philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleMomentum, a.key0, a.key1, z0, z1);
+                }
+                Q[e0] = X[e0];
+                Pm[e0] = z0;
+                s += z0 * z0;
+                if (e1 < n) {
+                    Q[e1] = X[e1];
+                    Pm[e1] = z1;
+                    s += z1 * z1;
+                }
+            }
+            K0 = 0.5 * row_sum<LPR>(s);
+#pragma unroll 1
+            for (int g = 0; g <= a.nleap + 1; ++g) {
+                const double coef = (g == 0 || g == a.nleap + 1) ? 0.5 : 1.0;
+                lds_wave_fence();  // Q complete
+                if constexpr (ANALYTIC) {
+                    grad_apply<FUN, LPR>(Q, n, l, [&](int e, double gv) { Pm[e] = Pm[e] - (coef * a.step[e]) * gv; });
+                } else {
+                    for (int e = l; e < n; e += LPR) X1[e] = X2[e] = Q[e];
+#pragma unroll 1
+                    for (int i = 0; i < n; ++i) {
+                        const bool own = (i & (LPR - 1)) == l;
+                        if (own) {
+                            X1[i] = X1[i] - h;
+                            X2[i] = X2[i] + h;
+                        }
+                        double fv[2];
+#pragma unroll 1
+                        for (int w = 0; w < 2; ++w) fv[w] = row_objective<FUN, LPR, false, 0, 0>(w ? X1 : X2, n, plan, l);
+                        const double gv = (0.5 * (fv[0] - fv[1])) / h;
+                        if (own) {
+                            Pm[i] = Pm[i] - (coef * a.step[i]) * gv;
+                            X1[i] = X1[i] + h;
+                            X2[i] = X2[i] - h;
+                        }
+                    }
+                }
+                if (g <= a.nleap)
+                    for (int e = l; e < n; e += LPR) Q[e] = Q[e] + a.step[e] * Pm[e];
+            }
+            s = 0.0;
+            for (int e = l; e < n; e += LPR) s += Pm[e] * Pm[e];
+            K = 0.5 * row_sum<LPR>(s);
+        }
+        const double fQ = row_objective<FUN, LPR, false, 0, 0>(Q, n, plan, l);
+        bool xbest_changed = false;
+        if (it == 0) {
+            st.start(fQ);
+            for (int e = l; e < n; e += LPR) X[e] = Q[e];
+            xbest_changed = true;
+        } else {
+            const bool feasible = !a.reject || row_in_box<LPR>(a, Q, n, l);
+            bool accept = false;
+            if (feasible) {
+                st.nfeas += 1;
+                const double logu = host ? a.logu[it] : philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
+                const double d = ((st.fcur - fQ) + K0) - K;
+                accept = (d < 0.0 ? d : 0.0) > logu;
+            }
+            if (accept) {
+                bool acc_best;
+                st.accept(fQ, it, acc_best, xbest_changed);
+                for (int e = l; e < n; e += LPR) X[e] = Q[e];
+            }
+        }
+        if (id.active) {
+            if (a.xall != nullptr) {
+                double *dst = a.xall + (c * a.maxiter + it) * n;
+                for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
+                if (l == 0) st_stream(a.funall + c * a.maxiter + it, st.fcur);
+            }
+            if (xbest_changed)
+                for (int e = l; e < n; e += LPR) a.xbest[c * n + e] = X[e];
+        }
+    }
+    if (id.active) {
+        for (int e = l; e < n; e += LPR) a.cur[c * n + e] = X[e];
+        if (l == 0) st.store(a, c);
+    }
+}
+
+template <int FUN, int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void gradient_kernel(const double *__restrict__ Xg, int64_t P, int n,
+                                                                            double *__restrict__ G) {
+    extern __shared__ double lds[];
+    const RowIds<LPR> id(P);
+    const int l = id.l;
+    double *Q = lds + (size_t)id.slot * n;
+    for (int e = l; e < n; e += LPR) Q[e] = Xg[id.rowc * n + e];
+    lds_wave_fence();
+    const bool active = id.active;
+    double *g = G + id.rowc * n;
+    grad_apply<FUN, LPR>(Q, n, l, [&](int e, double gv) {
+        if (active) g[e] = gv;
+    });
+}
+
+using sample_kernel_t = void (*)(const sx_sample_args, const PlanArg, int64_t, int64_t);
+using gradient_kernel_t = void (*)(const double *, int64_t, int, double *);
+
+template <int FUN, int LPR>
+sample_kernel_t pick_variant(int variant) {
+    return variant == kMcmc ? mcmc_kernel<FUN, LPR> : variant == kHmcFd ? hmc_kernel<FUN, LPR, false> : hmc_kernel<FUN, LPR, true>;
+}
+template <int LPR>
+sample_kernel_t pick_sample(int fun_id, int variant) {
+    switch (fun_id) {
+        case SX_FUN_ACKLEY: return pick_variant<SX_FUN_ACKLEY, LPR>(variant);
+        case SX_FUN_GRIEWANK: return pick_variant<SX_FUN_GRIEWANK, LPR>(variant);
+        case SX_FUN_QUARTIC: return pick_variant<SX_FUN_QUARTIC, LPR>(variant);
+        case SX_FUN_RASTRIGIN: return pick_variant<SX_FUN_RASTRIGIN, LPR>(variant);
+        case SX_FUN_ROSENBROCK: return pick_variant<SX_FUN_ROSENBROCK, LPR>(variant);
+        case SX_FUN_SPHERE: return pick_variant<SX_FUN_SPHERE, LPR>(variant);
+        default: return pick_variant<SX_FUN_STYBLINSKI_TANG, LPR>(variant);
+    }
+}
+template <int LPR>
+gradient_kernel_t pick_gradient(int fun_id) {
+    switch (fun_id) {
+        case SX_FUN_ACKLEY: return gradient_kernel<SX_FUN_ACKLEY, LPR>;
+        case SX_FUN_GRIEWANK: return gradient_kernel<SX_FUN_GRIEWANK, LPR>;
+        case SX_FUN_QUARTIC: return gradient_kernel<SX_FUN_QUARTIC, LPR>;
+        case SX_FUN_RASTRIGIN: return gradient_kernel<SX_FUN_RASTRIGIN, LPR>;
+        case SX_FUN_ROSENBROCK: return gradient_kernel<SX_FUN_ROSENBROCK, LPR>;
+        case SX_FUN_SPHERE: return gradient_kernel<SX_FUN_SPHERE, LPR>;
+        default: return gradient_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
+    }
+}
+
+int variant_of(int method, int jac) { return method == SX_SAMPLE_MCMC ? kMcmc : jac == SX_JAC_ANALYTIC ? kHmcAnalytic : kHmcFd; }
+
+}  // namespace
+}  // namespace sx
+
+using namespace sx;
+
+extern "C" int sx_sample_chains_per_workgroup(int method, int jac, int n) {
+    if (n < 1 || n > kWideFrom) return -1;
+    return sample_waves(variant_of(method, jac), n) * (kWave / lanes_per_row(n));
+}
+
+extern "C" int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *stream) {
+    SX_REQUIRE(a != nullptr, "sx_sample_run: null args");
+    SX_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
+               "sx_sample_run: null state pointer");
+    SX_REQUIRE(a->lower && a->upper && a->step, "sx_sample_run: bounds / step missing");
+    SX_REQUIRE(a->C >= 1 && a->C < (int64_t)1 << 31 && a->n >= 1 && a->n <= kWideFrom, "sx_sample_run: bad shape");
+    SX_REQUIRE(a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT, "sx_sample_run: unknown objective");
+    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || a->method == SX_SAMPLE_HMC, "sx_sample_run: unknown method");
+    SX_REQUIRE(a->jac == SX_JAC_FINITE_DIFF || a->jac == SX_JAC_ANALYTIC, "sx_sample_run: unknown gradient mode");
+    SX_REQUIRE(a->rng == SX_RNG_HOST || a->rng == SX_RNG_PHILOX, "sx_sample_run: unknown rng mode");
+    SX_REQUIRE(a->maxiter >= 1 && a->maxiter < (int64_t)1 << 31 && it0 >= 0 && steps >= 0 && it0 + steps <= a->maxiter,
+               "sx_sample_run: samples outside [0, maxiter)");
+    SX_REQUIRE(a->rng != SX_RNG_HOST || (a->C == 1 && a->x0 && !a->reject && (a->maxiter == 1 || (a->normals && a->logu))),
+               "sx_sample_run: host draws serve one chain without feasibility rejection, and need x0, normals and logu");
+    SX_REQUIRE((a->xall == nullptr) == (a->funall == nullptr), "sx_sample_run: xall and funall go together");
+    SX_REQUIRE(a->x0 == nullptr || a->x0_stride == 0 || a->x0_stride >= a->n, "sx_sample_run: bad x0 stride");
+    if (a->method == SX_SAMPLE_MCMC)
+        SX_REQUIRE(a->k >= 1 && a->k <= a->n, "sx_sample_run: block length outside [1, n]");
+    else
+        SX_REQUIRE(a->nleap >= 1 && (a->jac == SX_JAC_ANALYTIC || a->fd_step != 0.0), "sx_sample_run: bad nleap / step");
+    if (steps == 0) return 0;
+    PlanArg plan;
+    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
+    const int variant = variant_of(a->method, a->jac);
+    sample_kernel_t kern = nullptr;
+    SX_DISPATCH_LPR(a->n, kern = pick_sample<LPR>(a->fun_id, variant))
+    const int waves = sample_waves(variant, a->n);
+    const int chains = waves * (kWave / lanes_per_row(a->n));
+    const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
+    if (lds > 64 * 1024)  // one wave's chains need more than the default limit (gfx950: 160 KiB per workgroup)
+        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, (hipStream_t)stream,
+                       *a, plan, it0, it0 + steps);
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sx_sample_gradient(int fun_id, const double *X, int64_t P, int n, double *G, void *stream) {
+    SX_REQUIRE(X && G && P >= 1 && n >= 1 && n <= kWideFrom, "sx_sample_gradient: bad arguments");
+    SX_REQUIRE(fun_id >= 0 && fun_id < SX_FUN_COUNT, "sx_sample_gradient: unknown objective");
+    gradient_kernel_t kern = nullptr;
+    SX_DISPATCH_LPR(n, kern = pick_gradient<LPR>(fun_id))
+    const int rpw = kWave / lanes_per_row(n);
+    int waves = 1;
+    while (2 * waves <= kMaxWavesPerBlock && 2 * waves * rpw <= kMaxRowsPerBlock && 2 * waves * rpw * n * 8 <= 64 * 1024) waves *= 2;
+    const int rows = waves * rpw;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((P + rows - 1) / rows)), dim3(waves * kWave), (size_t)rows * n * sizeof(double),
+                       (hipStream_t)stream, X, P, n, G);
+    SX_LAUNCH_CHECK();
+    return 0;
+}

@@ -1,0 +1,12 @@
+"""Samplers behind stochopy's ``sample`` API: Metropolis-Hastings and Hamiltonian Monte-Carlo with many independent,
+device-resident chains (reference: stochopy/sample)."""
+from ._helpers import SampleResult, sample
+from ._hmc import sample as hmc
+from ._mcmc import sample as mcmc
+
+__all__ = [
+    "SampleResult",
+    "sample",
+    "hmc",
+    "mcmc",
+]

@@ -1,0 +1,191 @@
+"""What both samplers share: argument checks (no device needed), the draws of the numpy-legacy mode, the launches of the
+chain kernels (csrc/sx_sample.hip) and the assembly of the result."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _device, _lib, _rng
+from ..factory.benchmark import Objective
+from ._helpers import SampleResult
+
+
+class Setup:
+    """The checked arguments of one run.  Raises what the reference raises, in its order (mcmc/_mcmc.py:62-88,
+    hmc/_hmc.py:83-121), then this backend's own errors -- all before the device is touched."""
+
+    k = 1
+    nleap = 1
+    jac = _lib.SX_JAC_FINITE_DIFF
+    fd_step = 1.0e-4
+
+    def __init__(self, fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
+                 backend, nleap=None):
+        if not hasattr(fun, "__call__"):
+            raise TypeError()
+        if np.ndim(bounds) != 2:
+            raise ValueError()
+        self.ndim = ndim = len(bounds)
+        lower, upper = np.transpose(bounds)
+        self.lower = np.ascontiguousarray(lower, dtype=np.float64)
+        self.upper = np.ascontiguousarray(upper, dtype=np.float64)
+        if isinstance(chains, bool) or int(chains) != chains or chains < 1:
+            raise ValueError("chains is an integer >= 1")
+        self.chains = chains = int(chains)
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if not (x0.shape == (ndim,) or (chains > 1 and x0.shape == (chains, ndim))):
+                raise ValueError()
+            x0 = np.ascontiguousarray(x0)
+        self.x0 = x0
+        if nleap is not None and nleap < 1:
+            raise ValueError()
+        if np.ndim(stepsize) == 0:
+            stepsize = np.full(ndim, stepsize, dtype=np.float64)
+        if len(stepsize) != ndim:
+            raise ValueError()
+        self.step = np.array(stepsize, dtype=np.float64) * (0.5 * (self.upper - self.lower))
+        if callback is not None and not hasattr(callback, "__call__"):
+            raise ValueError()
+        self.callback = callback
+        # -- this backend's own conditions
+        if backend != "hip":
+            raise ValueError(f'unknown backend {backend!r}: "hip" is the only one')
+        if not isinstance(fun, Objective):
+            raise TypeError("stochopy_amd.sample fuses the objective into the chain kernels: fun must be one of the "
+                            "stochopy_amd.factory objectives (factory.batched and Python callables are not supported)")
+        if args not in ((), None):
+            raise TypeError("factory objectives take no extra args")
+        self.fun_id = fun.sx_id
+        # (csrc/sx_device.hpp kWideFrom: the longest row the kernels with one row per wavefront take)
+        if ndim < 1 or ndim > _lib.wide_from():
+            raise ValueError(f"stochopy_amd.sample serves rows of 1 to {_lib.wide_from()} elements, not {ndim}")
+        if isinstance(maxiter, bool) or int(maxiter) != maxiter or maxiter < 1:
+            raise ValueError("maxiter is an integer >= 1")
+        self.maxiter = int(maxiter)
+        if constraints not in (None, "Reject"):
+            raise ValueError(f"unknown constraints {constraints!r}: None or 'Reject'")
+        self.reject = constraints == "Reject"
+        if rng not in ("numpy-legacy", "philox"):
+            raise ValueError(f'unknown rng {rng!r}: "numpy-legacy" or "philox"')
+        self.rng = rng
+        if rng == "numpy-legacy":
+            if chains != 1:
+                raise ValueError('rng="numpy-legacy" replays the one stream of the reference and serves one chain; '
+                                 'use rng="philox" for chains > 1')
+            if self.reject:
+                raise ValueError('with constraints="Reject" the draw sequence depends on the data; use rng="philox"')
+            self.key = (0, 0)
+        else:
+            self.key = _rng.philox_key(seed)
+        self.seed = seed
+        self.return_all = bool(return_all)
+
+
+def _legacy_draws(s):
+    """The whole run's draws from the reference's stream, in its order: the initial point when none is given, then per
+    sample the normals (mcmc: the block's, hmc: ndim momenta) and the acceptance uniform.  With constraints=None the
+    sequence does not depend on the data."""
+    stream = _rng.LegacyHostStream(s.seed)
+    n, m = s.ndim, s.maxiter
+    x0 = s.x0 if s.x0 is not None else stream.uniform_rows(s.lower, s.upper, 1)[0]
+    width = s.k if s.method == _lib.SX_SAMPLE_MCMC else n
+    normals = np.zeros((max(m - 1, 1), width))
+    u = np.ones(m)
+    nblocks = -(-n // s.k)
+    for i in range(1, m):
+        if s.method == _lib.SX_SAMPLE_MCMC:
+            j0 = ((i - 1) % nblocks) * s.k
+            kb = min(s.k, n - j0)
+        else:
+            kb = n
+        stream.randn(kb, out=normals[i - 1, :kb])
+        stream.random(1, out=u[i:i + 1])
+    with np.errstate(divide="ignore"):
+        logu = np.log(u)
+    return stream, np.ascontiguousarray(x0, dtype=np.float64), normals, logu
+
+
+def run(s):
+    L = _lib.lib()
+    legacy = s.rng == "numpy-legacy"
+    Cn, n, m = s.chains, s.ndim, s.maxiter
+    stream = None
+    x0 = s.x0
+    if legacy:
+        stream, x0, normals, logu = _legacy_draws(s)
+    ctx = _device.Context()
+    t = _device.torch()
+    with t.cuda.stream(ctx.stream):
+        dev = {name: ctx.empty((Cn, n)) for name in ("cur", "xbest")}
+        dev.update({name: ctx.empty((Cn,)) for name in ("fcur", "facc", "fmin")})
+        dev.update({name: ctx.empty((Cn,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
+        on_device_all = s.return_all and s.callback is None
+        if on_device_all:
+            dev["xall"] = ctx.empty((Cn, m, n))
+            dev["funall"] = ctx.empty((Cn, m))
+        for name in ("lower", "upper", "step"):
+            dev[name] = ctx.upload(getattr(s, name))
+        if x0 is not None:
+            dev["x0"] = ctx.upload(x0)
+        if legacy:
+            dev["normals"] = ctx.upload(normals)
+            dev["logu"] = ctx.upload(logu)
+        a = _lib.SxSampleArgs()
+        for name in ("cur", "fcur", "facc", "fmin", "xbest", "iacc", "imin", "nacc", "nfeas", "x0", "xall", "funall",
+                     "lower", "upper", "step", "normals", "logu"):
+            setattr(a, name, _device.ptr(dev.get(name)))
+        a.C, a.maxiter = Cn, m
+        a.x0_stride = n if (x0 is not None and x0.ndim == 2) else 0
+        a.n, a.fun_id, a.method = n, s.fun_id, s.method
+        a.rng = _lib.SX_RNG_HOST if legacy else _lib.SX_RNG_PHILOX
+        a.reject, a.k, a.nleap, a.jac, a.fd_step = int(s.reject), s.k, s.nleap, s.jac, s.fd_step
+        a.key0, a.key1 = s.key
+
+        def host(name):
+            return dev[name].cpu().numpy()
+
+        if s.callback is None:
+            # the whole run is one launch
+            _lib.check(L.sx_sample_run(C.byref(a), 0, m, ctx.stream_ptr), "sx_sample_run")
+            xall = host("xall") if on_device_all else None
+            funall = host("funall") if on_device_all else None
+        else:
+            # one launch per sample; the state the callback sees is assembled as the reference does (mcmc/_mcmc.py:97-102
+            # and :142-153, hmc/_hmc.py:128-133 and :174-185): x / fun = the best ACCEPTED sample so far (the first one
+            # while there is none), nit and accept_ratio over the samples generated so far, xall / funall WITHOUT the newest
+            xall = np.empty((Cn, m, n))
+            funall = np.empty((Cn, m))
+            for i in range(m):
+                _lib.check(L.sx_sample_run(C.byref(a), i, 1, ctx.stream_ptr), "sx_sample_run")
+                xall[:, i] = host("cur")
+                funall[:, i] = host("fcur")
+                iacc = host("iacc")
+                facc_now = funall[np.arange(Cn), iacc]
+                b = int(np.argmin(facc_now))
+                state = SampleResult(x=xall[b, iacc[b]], fun=facc_now[b], nit=i + 1,
+                                     accept_ratio=1.0 if i == 0 else int(host("nacc").sum()) / (Cn * (i + 1)))
+                if s.return_all:
+                    upto = max(i, 1)
+                    state.update({"xall": xall[0, :upto] if Cn == 1 else xall[:, :upto],
+                                  "funall": funall[0, :upto] if Cn == 1 else funall[:, :upto]})
+                s.callback(xall[0, i] if Cn == 1 else xall[:, i], state)
+        ctx.sync()
+        nacc, nfeas = host("nacc"), host("nfeas")
+        mcmc = s.method == _lib.SX_SAMPLE_MCMC
+        fbest = host("facc" if mcmc else "fmin")
+        xbest = host("xbest")
+    if stream is not None:
+        stream.sync_back()  # numpy's global stream is where the reference would leave it
+    b = int(np.argmin(fbest))  # (numpy's rule: the first NaN, else the first minimum; all inf: chain 0)
+    res = SampleResult(x=xbest[b], fun=fbest[b], nit=m, accept_ratio=int(nacc.sum()) / (Cn * m))
+    if not mcmc:
+        grad_calls = 2 * n * (s.nleap + 2) if s.jac == _lib.SX_JAC_FINITE_DIFF else 0
+        res["nfev"] = Cn * (1 + (m - 1) * grad_calls) + 2 * int(nfeas.sum())
+    if s.reject:
+        res["nreject"] = Cn * (m - 1) - int(nfeas.sum())  # proposals that left the box
+    if Cn > 1:
+        res["accept_ratios"] = nacc / m
+    if s.return_all:
+        res["xall"] = xall[0] if Cn == 1 else xall
+        res["funall"] = funall[0] if Cn == 1 else funall
+    return res

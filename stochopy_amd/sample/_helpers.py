@@ -1,0 +1,43 @@
+"""API surface of the reference's sampling half.
+
+Reference: stochopy/sample/_helpers.py:8-88 (``SampleResult``, ``register``, ``sample``) and stochopy/_common.py
+(``BaseResult``: dict with attribute access whose repr sorts keys and hides xall / funall).
+"""
+from ..optimize._helpers import OptimizeResult
+
+__all__ = ["SampleResult", "sample", "register"]
+
+_sampler_map = {}
+
+
+class SampleResult(OptimizeResult):
+    """Sampling result: keys x, fun, nit, accept_ratio (+ nfev for hmc, xall / funall with ``return_all``, and
+    accept_ratios with more than one chain)."""
+
+
+def register(name, sample):
+    """Register a sampler under ``method=name`` (reference _helpers.py:36-38)."""
+    _sampler_map[name] = sample
+
+
+def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=None):
+    """Sample the variable space of ``fun`` on the GPU.
+
+    Same signature and dispatch as the reference (``_helpers.py:41-88``): ``options`` is splatted into the
+    per-method function, ``method`` is ``"mcmc"`` or ``"hmc"``.  ``fun`` is one of the ``stochopy_amd.factory``
+    handles (fused into the chain kernels); anything else raises ``TypeError``.  Options added by this backend:
+
+    - ``chains`` (int >= 1, default 1): independent chains, each resident in one kernel for the whole run.  With
+      ``chains = C > 1`` the result's ``xall`` is ``(C, maxiter, ndim)``, ``funall`` ``(C, maxiter)``, ``x`` / ``fun``
+      the best over all chains by the method's own rule applied per chain, ``accept_ratio`` the overall ratio and
+      ``accept_ratios`` one per chain; ``x0`` may be ``(ndim,)`` (shared) or ``(C, ndim)``; the callback's ``xk`` is
+      ``(C, ndim)``.
+    - ``rng``: ``"numpy-legacy"`` (default) replays the reference's own global MT19937 stream and needs
+      ``chains == 1``; ``"philox"`` makes every draw inside the kernel and serves any ``chains``.
+    - ``backend="hip"``: accepted, the only backend.
+
+    See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
+    """
+    options = options if options else {}
+
+    return _sampler_map[method](fun=fun, bounds=bounds, x0=x0, args=args, callback=callback, **options)

@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""Throughput of the samplers' chain kernels (csrc/sx_sample.hip) on one MI355X, next to the same sampler on one CPU core.
+
+Configurations (chains = 16 384, rosenbrock, Philox draws; xall stays on the device while timed):
+    mcmc           ndim 128, maxiter 1000, return_all off
+    mcmc+xall      ndim 128, maxiter 200,  return_all on  (xall is 3.4 GB: the run is bound by writing it -- the bytes stored
+                   per second are given as a share of the HBM peak DESIGN.md uses, 8 TB/s)
+    hmc analytic   ndim 64,  maxiter 100,  nleap 10, jac="analytic"
+    hmc fd         ndim 64,  maxiter 10,   nleap 10, finite differences (1 536 objective calls per sample and chain)
+Every configuration is warmed up once, then the configurations take turns for --rounds rounds; the line of a configuration
+gives the median and the spread (min .. max) of its rounds.  Time = device events around a round's launches of sx_sample_run
+(each a whole run from sample 0, repeated back to back for ~0.25 s), divided by their number.
+CPU side: the reference package when it is importable, else its numpy restatement (tests/_sample_oracle.py) -- the same numpy
+calls per sample -- with the same settings and ONE chain, on one core.
+
+    python tools/bench_sample.py [--rounds 5] [--chains 16384] [--window 0.25] [--no-cpu] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_PEAK = 8.0e12  # bytes/s, as in DESIGN.md
+
+CONFIGS = [
+    ("mcmc", "mcmc", 128, {"maxiter": 1000, "stepsize": 0.05, "perc": 1.0, "return_all": False}),
+    ("mcmc+xall", "mcmc", 128, {"maxiter": 200, "stepsize": 0.05, "perc": 1.0, "return_all": True}),
+    ("hmc analytic", "hmc", 64, {"maxiter": 100, "nleap": 10, "stepsize": 0.001, "jac": "analytic", "return_all": False}),
+    ("hmc fd", "hmc", 64, {"maxiter": 10, "nleap": 10, "stepsize": 0.001, "jac": None, "return_all": False}),
+]
+
+
+class DeviceRun:
+    """The buffers and arguments of one configuration, launched as stochopy_amd.sample does without a callback."""
+
+    def __init__(self, ctx, method, ndim, chains, o, seed=3):
+        from stochopy_amd import _device, _lib
+
+        t = _device.torch()
+        self.ctx, self.L, self.m = ctx, ctx.L, o["maxiter"]
+        lower, upper = np.full(ndim, -5.12), np.full(ndim, 5.12)
+        self.dev = dev = {name: ctx.empty((chains, ndim)) for name in ("cur", "xbest")}
+        dev.update({name: ctx.empty((chains,)) for name in ("fcur", "facc", "fmin")})
+        dev.update({name: ctx.empty((chains,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
+        if o["return_all"]:
+            dev["xall"], dev["funall"] = ctx.empty((chains, self.m, ndim)), ctx.empty((chains, self.m))
+        dev["lower"], dev["upper"] = ctx.upload(lower), ctx.upload(upper)
+        dev["step"] = ctx.upload(np.full(ndim, o["stepsize"]) * (0.5 * (upper - lower)))
+        self.a = a = _lib.SxSampleArgs()
+        for name in dev:
+            setattr(a, name, _device.ptr(dev[name]))
+        a.C, a.maxiter, a.x0_stride, a.n = chains, self.m, 0, ndim
+        a.fun_id, a.method = _lib.FUN_IDS["rosenbrock"], (_lib.SX_SAMPLE_MCMC if method == "mcmc" else _lib.SX_SAMPLE_HMC)
+        a.rng, a.reject, a.k, a.nleap = _lib.SX_RNG_PHILOX, 0, max(1, int(o.get("perc", 1.0) * ndim)), o.get("nleap", 1)
+        a.jac = _lib.SX_JAC_ANALYTIC if o.get("jac") == "analytic" else _lib.SX_JAC_FINITE_DIFF
+        a.fd_step, a.key0, a.key1 = 1.0e-4, seed, 0
+        self.samples = chains * self.m
+        self.stored = chains * self.m * (ndim + 1) * 8 if o["return_all"] else 0
+
+    def timed(self, launches=1):
+        """Seconds per launch (a whole run from sample 0), over `launches` launches back to back."""
+        from stochopy_amd import _lib
+
+        t = __import__("torch")
+        with t.cuda.stream(self.ctx.stream):
+            e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):
+                _lib.check(self.L.sx_sample_run(C.byref(self.a), 0, self.m, self.ctx.stream_ptr), "sx_sample_run")
+            e1.record()
+            e1.synchronize()
+        return e0.elapsed_time(e1) * 1e-3 / launches
+
+
+def cpu_rate(method, ndim, o):
+    """Samples per second of one chain on one core, and what ran."""
+    o = dict(o, seed=3)
+    o["maxiter"] = {"mcmc": 2000, "hmc": 100 if o.get("jac") == "analytic" else 8}[method]
+    bounds = [[-5.12, 5.12]] * ndim
+    try:
+        np.Inf = np.inf
+        from stochopy import factory
+        from stochopy.sample import sample
+
+        if o.get("jac") == "analytic":
+            raise ImportError  # (the reference has no working jac: its numbers are the finite-difference ones)
+        what, call = "reference", lambda: sample(factory.rosenbrock, bounds, method=method, options=o)
+    except ImportError:
+        import _sample_oracle
+
+        what = "numpy restatement"
+        call = lambda: _sample_oracle.sample("rosenbrock", bounds, method=method, options=dict(o, rng="numpy-legacy"))  # noqa: E731
+    with np.errstate(all="ignore"):
+        t0 = time.perf_counter()
+        call()
+        dt = time.perf_counter() - t0
+    return o["maxiter"] / dt, what
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--chains", type=int, default=16384)
+    ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per timed round")
+    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    from stochopy_amd import _device
+
+    ctx = _device.Context()
+    runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o)) for tag, method, ndim, o in CONFIGS]
+    launches = {}
+    for tag, *_, r in runs:
+        r.timed()  # warm-up: code object load, first touch of xall
+        launches[tag] = max(1, int(round(args.window / r.timed())))  # a timed window of ~args.window seconds
+    times = {tag: [] for tag, *_ in runs}
+    for _ in range(args.rounds):
+        for tag, *_, r in runs:
+            times[tag].append(r.timed(launches[tag]))
+    lines = []
+    for tag, method, ndim, o, r in runs:
+        ts = np.array(times[tag])
+        line = {"config": tag, "method": method, "ndim": ndim, "chains": args.chains, "maxiter": o["maxiter"],
+                "seconds_median": float(np.median(ts)), "seconds_min": float(ts.min()), "seconds_max": float(ts.max()),
+                "samples_per_s": r.samples / float(np.median(ts)),
+                "samples_per_s_spread": [r.samples / float(ts.max()), r.samples / float(ts.min())], "rounds": args.rounds, "launches_per_round": launches[tag]}
+        if r.stored:
+            line["stored_bytes_per_s"] = r.stored / float(np.median(ts))
+            line["share_of_hbm_peak"] = line["stored_bytes_per_s"] / HBM_PEAK
+        if not args.no_cpu:
+            rate, what = cpu_rate(method, ndim, o)
+            line.update({"cpu_one_chain_samples_per_s": rate, "cpu_what": what, "speedup": line["samples_per_s"] / rate})
+        lines.append(line)
+        print(json.dumps(line), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
