@@ -531,7 +531,7 @@ def test_device_loop_generation_by_generation_from_the_oracles_state(sa, ctx, ob
                                  ftol=1e-30, probe=lambda it, before, after: steps.append((it, before, after))))
     assert len(steps) >= min(maxiter, 30)
     run = _CmaDeviceRun(getattr(sa.factory, objective).sx_id, bounds[:, 0].copy(), bounds[:, 1].copy(), None, maxiter, P,
-                        sigma0, 0.5, 1e-12, 1e-30, seed, run=False)
+                        sigma0, 0.5, 1e-12, 1e-30, seed)
     buf = run.buffers
     mu = int(0.5 * P)
 

@@ -276,12 +276,12 @@ def test_exchange_buffer_geometry(lib):
 
 
 def test_penalize_host_bookkeeping_follows_the_oracle():
-    """The host half of constraints="Penalize" (stochopy_amd.optimize._cmaes._BoundaryWeights) against the
+    """The host half of constraints="Penalize" (stochopy_amd.optimize._evolution._BoundaryWeights) against the
     oracle's restatement (itself pinned to the reference) over a random walk of the mean in and out of the box:
     identical boundary weights / history / flags, and the same penalised fitness."""
     import oracle
     from oracle import engine as oe
-    from stochopy_amd.optimize._cmaes import _BoundaryWeights
+    from stochopy_amd.optimize._evolution import _BoundaryWeights
 
     rs = np.random.RandomState(5)
     n, P, mueff = 7, 12, 3.4
@@ -525,3 +525,99 @@ def test_replicated_workers_says_so_once_per_method():
     with warnings.catch_warnings():
         warnings.simplefilter("error")
         assert _common.replicated_workers("unit-test", 4, "a reason") == 1
+
+
+@pytest.mark.parametrize("n,P,expected", [
+    (512, 1024, "1" + "2" * 39), (20, 48, "1" + "2" * 39),
+    (70, 10, "01" + "02" * 19), (130, 24, "01" + "02" * 19),
+    (200, 8, "000001" + "000002" * 5 + "0000"), (300, 12, "000001" + "000002" * 5 + "0000"),
+    (512, 16, "0000001" + "0000002" * 4 + "00000")])
+def test_cmaes_decomposition_schedule(n, P, expected):
+    """Which generations decompose C and how (cmaes/_cmaes.py:301; 1 = from the identity, 2 = started from the previous
+    eigenvectors, 0 = none): most GPU tests use shapes that decompose in every generation, so the sparse schedules --
+    every second, sixth, seventh generation -- are pinned here, as literals."""
+    from stochopy_amd.optimize import _cmaes
+
+    c1, cmu = _cmaes._strategy_constants(n, P, 0.5)[5:7]
+    eigeneval, got = 0, ""
+    for gen in range(1, 41):
+        due = _cmaes.decomposition_due(gen, eigeneval, P, c1, cmu, n)
+        if due:
+            eigeneval = gen * P
+        got += str(due)
+    assert got == expected
+
+
+def test_device_resident_loops_look_schedule():
+    """When the host reads the state record of a device-resident run: 1, 2, 4, ... generations apart up to a cap (CMA-ES:
+    16, 4, 2, 1 for n = 32, 128, 256, 512; VD-CMA: 16), every generation with a callback or in a sharded run, and always
+    after the last generation."""
+    from stochopy_amd.optimize import _cmaes, _evolution, _vdcma
+
+    LOOK = _cmaes._CmaDeviceRun.LOOK
+    assert [_cmaes.look_cap(n, LOOK) for n in (32, 128, 256, 512)] == [16, 4, 2, 1]
+    assert _evolution.look_generations(70, 16, False) == [1, 3, 7, 15, 31, 47, 63, 70]
+    assert _evolution.look_generations(70, 4, False) == [1, 3, 7] + list(range(11, 68, 4)) + [70]
+    assert _evolution.look_generations(70, 2, False) == list(range(1, 70, 2)) + [70]
+    assert _evolution.look_generations(70, 1, False) == list(range(1, 71))
+    for cap in (16, 4, 2, 1):  # a callback, a world
+        assert _evolution.look_generations(9, cap, True) == list(range(1, 10))
+    run = _vdcma._VdDeviceRun.__new__(_vdcma._VdDeviceRun)
+    assert run._look_cap() == 16
+    assert _evolution.look_generations(100, 16, False) == [1, 3, 7, 15, 31, 47, 63, 79, 95, 100]
+    assert _evolution.look_generations(15, 16, False) == [1, 3, 7, 15] and _evolution.look_generations(0, 16, False) == []
+
+
+def test_cmaes_sweep_allowance_after_a_look():
+    """Sweeps launched for the next warm-started decomposition, from the eigensolver's record at a look: what the last one
+    used + 1 while the host looks at every generation, + 3 between rarer looks, never more than 60; a short-fall sets it
+    to 60 and warns -- "60 sweeps" when 60 had been launched, "ran out of its %d launched sweeps" the first time
+    otherwise, nothing later."""
+    from stochopy_amd.optimize._cmaes import sweep_allowance
+
+    # (used, ok, fails, fails_seen, launched, look_cap, warned_short)
+    assert sweep_allowance(11, True, 0, 0, 16, 1, False) == (12, 0, None)
+    assert sweep_allowance(11, True, 0, 0, 16, 4, False) == (14, 0, None)
+    assert sweep_allowance(60, True, 2, 2, 60, 1, True) == (60, 2, None)
+    assert sweep_allowance(59, True, 0, 0, 60, 16, False) == (60, 0, None)
+    sweeps, seen, warning = sweep_allowance(60, False, 1, 0, 60, 1, False)
+    assert (sweeps, seen) == (60, 1) and "did not reach its tolerance in 60 sweeps" in warning
+    sweeps, seen, warning = sweep_allowance(11, False, 1, 0, 11, 1, False)
+    assert (sweeps, seen) == (60, 1) and "ran out of its 11 launched sweeps" in warning
+    assert sweep_allowance(12, False, 2, 1, 12, 1, True) == (60, 2, None)
+    # a converged record next to a short-fall the host has not seen yet (between rarer looks) is a short-fall
+    sweeps, seen, warning = sweep_allowance(9, True, 3, 2, 13, 4, False)
+    assert (sweeps, seen) == (60, 3) and "ran out of its 13 launched sweeps" in warning
+    assert "60 sweeps" in sweep_allowance(60, True, 3, 2, 60, 4, True)[2]
+
+
+@pytest.mark.parametrize("module,cls,how,gathered", [("_cmaes", "_CmaDeviceRun", (2,), ["arx", "fit"]),
+                                                     ("_vdcma", "_VdDeviceRun", (), ["ary", "arx", "fit"])])
+def test_sharded_generation_enqueue_order(module, cls, how, gathered):
+    """One sharded generation through the shared enqueue (_DeviceRun._generation): stage 0 on this rank's rows, the gathers
+    in the method's order, stage 1; one call on one GPU."""
+    import importlib
+    import types
+
+    Run = getattr(importlib.import_module("stochopy_amd.optimize." + module), cls)
+    events = []
+    run = Run.__new__(Run)  # the host logic only: the library calls are stand-ins
+    entry, stage = Run.ENTRY, Run.ENTRY + "_stage"
+
+    def record(name):
+        return lambda a, *args: events.append((name,) + tuple(getattr(x, "value", x) for x in args)) or 0
+
+    run.ctx = types.SimpleNamespace(L=types.SimpleNamespace(**{entry: record(entry), stage: record(stage)}), stream_ptr="s")
+    run.args = Run.Args()
+    run.buffers = {k: "full " + k for k in gathered}
+    run._local = [types.SimpleNamespace(data_ptr=lambda k=k: 1000 + len(k)) for k in gathered]
+    run.world = types.SimpleNamespace(all_gather_rows=lambda loc, full: events.append(("gather", run._local.index(loc), full)))
+    run.row0, run.Pl = 24, 8
+    run._generation(5, *how)
+    assert events == ([(stage, 5, *how, 0, 24, 8, *(1000 + len(k) for k in gathered), "s")]
+                      + [("gather", i, "full " + k) for i, k in enumerate(gathered)]
+                      + [(stage, 5, *how, 1, 0, 0, *(None for _ in gathered), "s")])
+    del events[:]
+    run.world = None
+    run._generation(6, *how)
+    assert events == [(entry, 6, *how, "s")]

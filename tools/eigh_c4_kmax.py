@@ -10,13 +10,12 @@ from stochopy_amd.optimize import _cmaes
 
 n, P, gens = (int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (512, 1024, 30)
 lo, up = np.full(n, -5.12), np.full(n, 5.12)
-run = _cmaes._CmaDeviceRun(sa.factory.rosenbrock.sx_id, lo, up, None, gens + 1, P, 0.1, 0.5, 0.0, -1.0, 0, run=False)
+run = _cmaes._CmaDeviceRun(sa.factory.rosenbrock.sx_id, lo, up, None, gens + 1, P, 0.1, 0.5, 0.0, -1.0, 0)
 run.args.eig_sweeps = 24
 eigeneval = 0
 for gen in range(1, gens + 1):
-    due = gen * P - eigeneval > run.eig_every
+    due = _cmaes.decomposition_due(gen, eigeneval, P, run.c1, run.cmu, n)
     if due:
-        due = 2 if eigeneval else 1
         eigeneval = gen * P
     with torch.cuda.stream(run.ctx.stream):
         run.step(gen, int(due))

@@ -11,13 +11,12 @@ from stochopy_amd.optimize import _cmaes
 n, P, gens = (int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (512, 1024, 40)
 ms = int(sys.argv[4]) if len(sys.argv) > 4 else 24
 lo, up = np.full(n, -5.12), np.full(n, 5.12)
-run = _cmaes._CmaDeviceRun(sa.factory.rosenbrock.sx_id, lo, up, None, gens + 1, P, 0.1, 0.5, 0.0, -1.0, 0, run=False)
+run = _cmaes._CmaDeviceRun(sa.factory.rosenbrock.sx_id, lo, up, None, gens + 1, P, 0.1, 0.5, 0.0, -1.0, 0)
 run.args.eig_sweeps = ms
 eigeneval, tot = 0, []
 for gen in range(1, gens + 1):
-    due = gen * P - eigeneval > run.eig_every
+    due = _cmaes.decomposition_due(gen, eigeneval, P, run.c1, run.cmu, n)
     if due:
-        due = 2 if eigeneval else 1
         eigeneval = gen * P
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(run.ctx.stream):

@@ -1,14 +1,15 @@
-"""Line-level host timeline of _VdDeviceRun.__init__ (wide VD-CMA): which source lines take more than 1 ms?"""
-import sys, time
-sys.path.insert(0, "/root/repo")
+"""Line-level host timeline of the device-resident loop (_DeviceRun.run) in a wide VD-CMA call: which source lines take
+more than 1 ms?"""
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import stochopy_amd as sa
-from stochopy_amd.optimize import _vdcma
+from stochopy_amd.optimize import _evolution
 n, P, G = 16384, 1024, 200
 o = dict(seed=0, rng="philox", ftol=-1.0, xtol=0.0, backend="hip", popsize=P, sigma=0.3)
 run = lambda m: sa.optimize.minimize(sa.factory.rosenbrock, [[-5.12, 5.12]] * n, method="vdcma", options=dict(o, maxiter=m))
 run(10); run(G)
-code = _vdcma._VdDeviceRun.__init__.__code__
+code = _evolution._DeviceRun.run.__code__
 last = [None, 0.0]
 slow = {}
 def tracer(frame, event, arg):
