@@ -326,21 +326,6 @@ typedef struct sx_pso_args {
 
 int sx_pso_generation(const sx_pso_args *a, int finalize, void *stream);
 
-/* PSO with ONE kernel per generation (round 3; the pattern of sx_de_chain_launch): the best / termination step of
- * _common.py:131-158 for generation g runs in the prologue of the launch that produces generation g+1 -- every
- * workgroup reduces the per-workgroup records (two levels) and derives the same best row and status.  Because the
- * swarm is updated in place, each workgroup keeps a copy of its best row in best_rows (double-buffered; the record
- * says which copy is current), which is where the next generation reads gbest from.
- * Supported (sx_pso_chain_supported != 0): one GPU, SX_RNG_PHILOX, constraints none, no pending restart, whole-batch
- * rows (n = 64, 128 or 256), sx_num_partials(P,n) <= 8 x the workgroup size.
- * a->state: 3 sx_state words ([0], [1] ping-pong by launch parity, [2] written by finalize_only launches = the
- * host's view; reserved[0] / reserved[1] = record of the previous / current best); a->part_f / a->part_i:
- * 2 x npart records, record = 2 * row + q; best_rows DEVICE (2, npart, n); a->gbest unused.  status 1 is reported
- * for `fun <= ftol`; whether it is 0 (best moved by <= xtol) the host settles from the two resident rows. */
-int sx_pso_chain_supported(const sx_pso_args *a);
-int sx_pso_chain_launch(const sx_pso_args *a, double *best_rows, int parity, int finalize_only, void *stream);
-int sx_pso_chain_graph_create(const sx_pso_args *a, double *best_rows, int ngen, int start_parity, sx_graph **out);
-
 /* Competitive restart, cpso/_cpso.py:405-426.
  * sx_pso_radius: part_r[b] = max over the rows of workgroup b of ||X_i - gbest||_2 (:410)
  *   part_r DEVICE (sx_num_partials(P,n)).
@@ -547,31 +532,21 @@ int sx_cmaes_generation_phased(const sx_cma_args *a, int64_t gen, int do_eigh, i
  * Asynchronous on `stream`; the host never waits: launches after convergence are no-ops.
  * sx_eigh_info (synchronises): sweeps carried out, whether the rule was met, off-diagonal mass / |C|_F left
  * behind by the last sweep.
- * sx_eigh_set_refine(mode): the last sweep of a run may be replaced by the first-order refinement step
+ * The refinement step: the last sweep of a run may be replaced by the first-order refinement step
  * V <- V (I + K + K K / 2), K_ij = M_ij / (M_jj - M_ii), once what the sweeps left is small against every gap
  * (off(M) <= 1e-7 |C|_F and max |K_ij| <= 1e-3, both measured on the device; csrc/sx_eigh.hip kRefineOff).
- * mode 1: always allowed; 0: never; -1 (initial): allowed inside the CMA-ES generation loops (sx_cmaes_generation*),
- * not in sx_eigh itself; the environment variable SX_EIGH_REFINE = 0 / 1 sets the initial mode.  Returns the
- * previous mode.  Process-wide, not thread-safe.
- * sx_eigh_set_flow(mode): how the rounds of a run are enqueued (n > 32).  0 (the default): one launch per round.
- * 1: ONE resident launch works through all rounds -- pair workgroups hand their rotations to their two successors through
- * agent-scope words, tile workgroups follow behind counters; every wait is bounded (SX_EIGH_FLOW_TIMEOUT_MS, default 2000: a
- * run whose wait ran out is reported like one that did not converge).  Identical results, bit for bit; measured on MI355X it
- * is no faster (profiles/r6_eigh_flow.txt), hence not the default.  The resident form needs its whole grid (at most one
- * workgroup per CU) on the chip at once: PROCESSES THAT SHARE ONE GPU MUST NOT USE IT.  -1: back to the initial mode
- * (environment variable SX_EIGH_FLOW = 0 / 1, else 0).  Returns the previous mode; -2 changes nothing and returns the mode in
- * effect (0 / 1).  Process-wide, not thread-safe.
+ * It is allowed inside the CMA-ES generation loops (sx_cmaes_generation*) and not in sx_eigh itself; the environment
+ * variable SX_EIGH_REFINE = 0 / 1, read once, forbids / allows it in both.  sx_eigh_refined decides it per call.
+ * (Removed after commit c68e4cc: the process-wide setters sx_eigh_set_refine / sx_eigh_set_flow, and with the latter the
+ * resident one-launch form of the rounds -- bit-identical to the launch per round and no faster, profiles/r6_eigh_flow.txt.)
  * ------------------------------------------------------------------------- */
 int64_t sx_eigh_workspace_bytes(int n);
 int sx_eigh(const double *C, int n, const double *V0, double *w, double *B, void *ws, int64_t ws_bytes, int max_sweeps,
             double tol, void *stream);
-/* sx_eigh with the refinement step allowed (refine > 0) / forbidden (0) for THIS call only (< 0: the process-wide mode):
- * what a multi-threaded host uses instead of flipping sx_eigh_set_refine around a call. */
+/* sx_eigh with the refinement step allowed (refine > 0) / forbidden (0) for THIS call (< 0: the library's default, as sx_eigh) */
 int sx_eigh_refined(const double *C, int n, const double *V0, double *w, double *B, void *ws, int64_t ws_bytes,
                     int max_sweeps, double tol, int refine, void *stream);
 int sx_eigh_info(const void *ws, int *sweeps, int *converged, double *off_rel, void *stream);
-int sx_eigh_set_refine(int mode);
-int sx_eigh_set_flow(int mode);
 
 /* VD-CMA: everything of the model update that is O(mu n), on the device.
  * replaces vdcma/_vdcma.py:289-295 (w . arx[arindex[:mu]]), :317 (w . ary[arindex[:mu]]) and :331-339 with :428-444 (the

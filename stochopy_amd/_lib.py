@@ -168,9 +168,6 @@ PROTOTYPES = {
     "sx_graph_launch": (C.c_int, [vp, vp]),
     "sx_graph_destroy": (C.c_int, [vp]),
     "sx_pso_generation": (C.c_int, [C.POINTER(SxPsoArgs), C.c_int, vp]),
-    "sx_pso_chain_supported": (C.c_int, [C.POINTER(SxPsoArgs)]),
-    "sx_pso_chain_launch": (C.c_int, [C.POINTER(SxPsoArgs), vp, C.c_int, C.c_int, vp]),
-    "sx_pso_chain_graph_create": (C.c_int, [C.POINTER(SxPsoArgs), vp, C.c_int, C.c_int, C.POINTER(vp)]),
     "sx_pso_radius": (C.c_int, [C.POINTER(SxPsoArgs), vp, vp]),
     "sx_pso_restart_select": (C.c_int, [C.POINTER(SxPsoArgs), vp, f64, f64, vp, vp]),
     "sx_pso_restart_apply": (C.c_int, [C.POINTER(SxPsoArgs), vp, vp, vp, i64, vp]),
@@ -205,8 +202,6 @@ PROTOTYPES = {
     "sx_eigh": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, i64, C.c_int, f64, vp]),
     "sx_eigh_refined": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, i64, C.c_int, f64, C.c_int, vp]),
     "sx_eigh_info": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(f64), vp]),
-    "sx_eigh_set_refine": (C.c_int, [C.c_int]),
-    "sx_eigh_set_flow": (C.c_int, [C.c_int]),
     "sx_sample_run": (C.c_int, [C.POINTER(SxSampleArgs), i64, i64, vp]),
     "sx_sample_chains_per_workgroup": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sx_sample_gradient": (C.c_int, [C.c_int, vp, i64, C.c_int, vp, vp]),

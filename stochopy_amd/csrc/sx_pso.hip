@@ -36,51 +36,34 @@ __device__ __forceinline__ unsigned long long sort_key(double f) {
 // one batch, and every bound check and loop over the row folds away.
 // PLAIN (round 5: with or without FULL): constraints=None and no restart pending (plain PSO, or the first generation of a CPSO graph): neither
 // the Shrink pass nor the re-seeding test is compiled in.
-// CHAIN (with PLAIN; round 3): ONE kernel per generation, the way DE runs (sx_de_kernel.hpp).  Launch L (parity
-// chain_p = L & 1) first finalises the generation its predecessor produced -- every workgroup reduces the per-workgroup
-// records of parity chain_p (two levels: a slice per thread, DPP over the wave, the waves through LDS), derives the same
-// best / status, workgroup 0 publishes it in state[1 - chain_p] -- and then produces the next generation, writing its
-// record of parity 1 - chain_p.  The swarm is updated in place, so the best row cannot be read from pbest while other
-// workgroups overwrite theirs: every workgroup keeps a copy of ITS best row in best_rows[q][block] and its record says
-// which q (rec = 2 * row + q); the copy is rewritten -- into the buffer the current record does NOT point to -- only
-// when the workgroup's best row changed.  mode 1: one workgroup, finalise only, into state[2] (the host's view).
-constexpr int kChainRecPerThread = 8;
-
 // ONEB (round 5): a whole-wave kernel instantiated for rows of 129 ... 256 elements of run-time length: one batch, the objective's
 // run-time register chain only -- the general whole-wave kernel carries the long rows' summation plans in its register budget
 // (111 VGPRs with Ackley: two workgroups per CU, where the n = 256 kernel runs four)
 #ifndef SX_PSO_RAD_WAVES
 #define SX_PSO_RAD_WAVES 6
 #endif
-template <int FUN, int RNG, int LPR, bool FULL, bool PLAIN = false, bool CHAIN = false, bool ONEB = false>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && !CHAIN && LPR == kWave) ? SX_PSO_RAD_WAVES : 1) void pso_generation_kernel(const sx_pso_args a,
+template <int FUN, int RNG, int LPR, bool FULL, bool PLAIN = false, bool ONEB = false>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && LPR == kWave) ? SX_PSO_RAD_WAVES : 1) void pso_generation_kernel(const sx_pso_args a,
                                                                                 const PlanArg plan,
-                                                                                double *__restrict__ best_rows,
-                                                                                const int chain_p, const int mode,
+                                                                                double *__restrict__ part_rad,
                                                                                 const int64_t npart) {
-    static_assert(!CHAIN || (PLAIN && FULL), "the chained form exists for the whole-batch constraints=None kernel");
-    // RAD (CPSO inside a graph; best_rows then points at npart doubles, see sx_pso_graph_create): the workgroup also leaves
+    // RAD (CPSO inside a graph; part_rad then points at npart + P doubles, see sx_pso_graph_create): the workgroup also leaves
     // max_i ||X_i(new) - gbest(OLD)||_2^2 over its rows -- the (squared) swarm radius against the best the kernel was started with, in
     // pso_radius_kernel's own order of operations.  cpso_post_kernel turns that into the restart decision (radius_decision)
     // and the radius pass over X is skipped.
-    constexpr bool RAD = FULL && !PLAIN && !CHAIN;
+    constexpr bool RAD = FULL && !PLAIN;
     double racc = 0.0;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double sf[kMaxRowsPerBlock];
     __shared__ int64_t si[kMaxRowsPerBlock];
-    __shared__ int sb[kMaxRowsPerBlock];          // CHAIN: the row's pbest changed in this generation
-    __shared__ double s_wf[kMaxWavesPerBlock];    // CHAIN: the waves' partial results of the record reduction
-    __shared__ int64_t s_wi[kMaxWavesPerBlock];
     // the state word (a miss after every kernel boundary) is needed by the Philox counters and the stop test only: the
     // PLAIN kernel issues the row loads of its batch before anything waits for it.  (Not the general one: with the
     // re-seeding code behind it the late test costs 130 VGPRs instead of 80 -- 3 waves per SIMD instead of 6 -- and made
     // that kernel 31.5 -> 53 us, profiles/r2_pso_c3_variants.txt.)
-    const sx_state *st = CHAIN ? a.state + chain_p : a.state;
+    const sx_state *st = a.state;
     const int done = st->done;
     if (!PLAIN && done) return;
-    // CHAIN: st->it is the last FINALISED generation; the swarm holds st->it + 1, this launch produces st->it + 2
-    const int64_t it_held = CHAIN ? st->it + 1 : st->it;
-    const uint32_t gen = (uint32_t)(it_held + 1);
+    const uint32_t gen = (uint32_t)(st->it + 1);
     const int n = FULL ? 4 * LPR : a.n;
     const int64_t P = a.P, ld = a.ld;
     const RowIds<LPR> id(P);
@@ -101,27 +84,6 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && !CHAIN
     double *__restrict__ vr = a.V + rowc * ld;
     double *__restrict__ pb = a.pbest + rowc * ld;
     const double *__restrict__ gb = a.gbest;
-    // CHAIN: the predecessor's records, a contiguous slice per thread (first-minimum rule), and this workgroup's own
-    double pfv[kChainRecPerThread];
-    int64_t piv[kChainRecPerThread];
-    int64_t myprev = 0;
-    double *part_f_out = a.part_f;
-    int64_t *part_i_out = a.part_i;
-    if (CHAIN) {
-        const double *pf = a.part_f + (int64_t)chain_p * npart;
-        const int64_t *pi = a.part_i + (int64_t)chain_p * npart;
-        const int per = (int)((npart + blockDim.x - 1) / blockDim.x);
-        const int64_t k0 = (int64_t)threadIdx.x * per;
-#pragma unroll
-        for (int u = 0; u < kChainRecPerThread; ++u) {
-            const bool in = u < per && k0 + u < npart;
-            pfv[u] = in ? pf[k0 + u] : __builtin_huge_val();
-            piv[u] = in ? pi[k0 + u] : INT64_MAX;
-        }
-        myprev = pi[id.block];
-        part_f_out = a.part_f + (int64_t)(1 - chain_p) * npart;
-        part_i_out = a.part_i + (int64_t)(1 - chain_p) * npart;
-    }
     const uint32_t grow = (uint32_t)(a.row0 + rowc);
     const double w = a.w, c1 = a.c1, c2 = a.c2;
     const bool shrink = PLAIN ? false : a.constraints != 0;
@@ -143,61 +105,11 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && !CHAIN
             x[t] = ld_row ? xr[e] : 0.0;
             v[t] = ld_row ? vr[e] : 0.0;
             p[t] = ld_row ? pb[e] : 0.0;
-            if (!CHAIN) g[t] = in ? gb[e] : 0.0;
+            g[t] = in ? gb[e] : 0.0;
             r1[t] = (RNG == SX_RNG_HOST && in) ? r1row[e] : 0.0;
             r2[t] = (RNG == SX_RNG_HOST && in) ? r2row[e] : 0.0;
         }
-        if (PLAIN && done) {  // (uniform; nothing has been written yet)
-            if (CHAIN && mode == 1 && blockIdx.x == 0 && threadIdx.x == 0) a.state[2] = *st;
-            return;
-        }
-        if constexpr (CHAIN) {
-            // ---- finalise the generation the swarm holds: (min f, first row) over the records, two levels ----
-            double bf = pfv[0];
-            int64_t brec = piv[0];
-#pragma unroll
-            for (int u = 1; u < kChainRecPerThread; ++u)
-                if (pfv[u] < bf) bf = pfv[u], brec = piv[u];  // (slices are in row order: strict < keeps the first)
-            bool lnan = false;
-#pragma unroll
-            for (int u = 0; u < kChainRecPerThread; ++u) lnan |= is_nan(pfv[u]);
-            if (__ballot(lnan)) {  // (rare) np.argmin's order: the first NaN record wins
-                bf = pfv[0], brec = piv[0];
-#pragma unroll
-                for (int u = 1; u < kChainRecPerThread; ++u)
-                    if (best_before(pfv[u], bf)) bf = pfv[u], brec = piv[u];
-            }
-            wave_argmin_ordered(bf, brec);
-            if (id.lane == 0) s_wf[id.wave] = bf, s_wi[id.wave] = brec;
-            __syncthreads();
-            bf = s_wf[0], brec = s_wi[0];
-            const int nw = (int)(blockDim.x >> 6);
-            for (int wv = 1; wv < nw; ++wv)
-                if (best_before(s_wf[wv], bf)) bf = s_wf[wv], brec = s_wi[wv];  // (waves in row order: strict keeps the first)
-            int status = SX_STATUS_NONE;
-            if (it_held >= 2) {  // the reference does not test the initial swarm (cpso/_cpso.py:219-240)
-                if (bf <= a.ftol)
-                    status = 1;  // (0 if the best moved by <= xtol: settled by the host from the two resident rows)
-                else if (it_held >= a.maxiter)
-                    status = -1;
-            }
-            if (blockIdx.x == 0 && threadIdx.x == 0) {
-                sx_state *so = a.state + (mode == 1 ? 2 : 1 - chain_p);
-                so->it = it_held;
-                so->gbidx = brec >> 1;
-                so->gfit = bf;
-                so->dx = 0.0;
-                so->status = status;
-                so->done = status != SX_STATUS_NONE;
-                so->reserved[0] = st->reserved[1];  // the record of the best of the generation before
-                so->reserved[1] = brec;
-            }
-            if (status != SX_STATUS_NONE || mode == 1) return;
-            const int rows_in_block = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
-            const double *__restrict__ gbc = best_rows + ((brec & 1) * npart + (brec >> 1) / rows_in_block) * (int64_t)n;
-#pragma unroll
-            for (int t = 0; t < kStep; ++t) g[t] = gbc[(q0 + t) * LPR + l];
-        }
+        if (PLAIN && done) return;  // (uniform; nothing has been written yet)
         if (RNG == SX_RNG_PHILOX) {
             // 53-bit r1 and r2, as the reference's two rand(P, n) blocks (cpso/_cpso.py:262-263): a call per purpose and pair
             // of steps (slot = (q>>1)*LPR + l, half = q&1).  (Rounds 1-5: 32-bit ones, one call for both -- +2.8 % at C3a / C3b
@@ -293,85 +205,47 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && !CHAIN
             if (a.candfit != nullptr) a.candfit[id.row] = fc;
         }
     }
-    if constexpr (!CHAIN) {
-        __shared__ double sr[kMaxRowsPerBlock];
-        const bool rad = RAD && best_rows != nullptr;  // (uniform) exactly pso_radius_kernel's reduction, behind the records' barrier
-        if (rad) {
-            // the SQUARED radius (the square root is monotone and correctly rounded: max sqrt = sqrt max, taken once by
-            // cpso_post_kernel); whole-wave rows add up without LDS traffic (same additions as row_sum)
-            if constexpr (LPR == kWave)
-                racc = wave_sum_butterfly(racc, id.lane);
-            else
-                racc = row_sum<LPR>(racc);
-            if (id.l == 0) {
-                sr[id.slot] = id.active ? racc : 0.0;
-                if (id.active) best_rows[npart + id.row] = racc;  // (per row, behind the npart per-workgroup maxima)
-            }
-        }
-        block_partial<LPR>(better ? fc : fold, id, sf, si, a.part_f, a.part_i);
-        if (rad && threadIdx.x < kWave) {
-            const int rows_in_block = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
-            const double m = wave_max_f64((int)threadIdx.x < rows_in_block ? sr[threadIdx.x] : 0.0);
-            if (threadIdx.x == 0) best_rows[blockIdx.x] = m;
-        }
-    } else {
-        // the workgroup's record AND, when its best row changed, the row itself (see the head of the kernel)
+    __shared__ double sr[kMaxRowsPerBlock];
+    const bool rad = RAD && part_rad != nullptr;  // (uniform) exactly pso_radius_kernel's reduction, behind the records' barrier
+    if (rad) {
+        // the SQUARED radius (the square root is monotone and correctly rounded: max sqrt = sqrt max, taken once by
+        // cpso_post_kernel); whole-wave rows add up without LDS traffic (same additions as row_sum)
+        if constexpr (LPR == kWave)
+            racc = wave_sum_butterfly(racc, id.lane);
+        else
+            racc = row_sum<LPR>(racc);
         if (id.l == 0) {
-            sf[id.slot] = id.active ? (better ? fc : fold) : __builtin_huge_val();
-            si[id.slot] = id.active ? id.row : INT64_MAX;
-            sb[id.slot] = better ? 1 : 0;
+            sr[id.slot] = id.active ? racc : 0.0;
+            if (id.active) part_rad[npart + id.row] = racc;  // (per row, behind the npart per-workgroup maxima)
         }
-        __syncthreads();
-        if (threadIdx.x < kWave) {
-            const int rows_in_block = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
-            const int k = (int)threadIdx.x;
-            double bf = k < rows_in_block ? sf[k] : __builtin_huge_val();
-            int64_t bi = k < rows_in_block ? si[k] : INT64_MAX;
-            wave_argmin_ordered(bf, bi);
-            const int ks = (int)(bi - (int64_t)id.block * rows_in_block);  // the winning slot
-            const bool changed = sb[ks] != 0 || bi != (myprev >> 1);
-            const int64_t q = changed ? 1 - (myprev & 1) : (myprev & 1);
-            if (changed) {  // the new pbest of a row that improved is its position, still in LDS
-                const double *src = sb[ks] ? lds + ks * gen_row_stride(n) : a.pbest + bi * ld;
-                double *dst = best_rows + (q * npart + id.block) * (int64_t)n;
-                for (int e = k; e < n; e += kWave) dst[e] = src[e];
-            }
-            if (k == 0) {
-                part_f_out[id.block] = bf;
-                part_i_out[id.block] = 2 * bi + q;
-            }
-        }
+    }
+    block_partial<LPR>(better ? fc : fold, id, sf, si, a.part_f, a.part_i);
+    if (rad && threadIdx.x < kWave) {
+        const int rows_in_block = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
+        const double m = wave_max_f64((int)threadIdx.x < rows_in_block ? sr[threadIdx.x] : 0.0);
+        if (threadIdx.x == 0) part_rad[blockIdx.x] = m;
     }
 }
 
-typedef void (*pso_kernel_t)(const sx_pso_args, const PlanArg, double *, int, int, int64_t);
+typedef void (*pso_kernel_t)(const sx_pso_args, const PlanArg, double *, int64_t);
 
-template <int RNG, int LPR, bool FULL, bool PLAIN = false, bool CHAIN = false, bool ONEB = false>
+template <int RNG, int LPR, bool FULL, bool PLAIN = false, bool ONEB = false>
 pso_kernel_t pick_kernel_lpr(int fun_id) {
-    constexpr bool SPECIAL = PLAIN || ONEB || CHAIN;  // (pick_kernel / sx_pso_chain_supported route the other objectives to the general form)
+    constexpr bool SPECIAL = PLAIN || ONEB;  // (pick_kernel routes the other objectives to the general form)
     switch (fun_id) {
-        case SX_FUN_ACKLEY: return pso_generation_kernel<SX_FUN_ACKLEY, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
-        case SX_FUN_RASTRIGIN: return pso_generation_kernel<SX_FUN_RASTRIGIN, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
-        case SX_FUN_ROSENBROCK: return pso_generation_kernel<SX_FUN_ROSENBROCK, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
-        case SX_FUN_SPHERE: return pso_generation_kernel<SX_FUN_SPHERE, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
+        case SX_FUN_ACKLEY: return pso_generation_kernel<SX_FUN_ACKLEY, RNG, LPR, FULL, PLAIN, ONEB>;
+        case SX_FUN_RASTRIGIN: return pso_generation_kernel<SX_FUN_RASTRIGIN, RNG, LPR, FULL, PLAIN, ONEB>;
+        case SX_FUN_ROSENBROCK: return pso_generation_kernel<SX_FUN_ROSENBROCK, RNG, LPR, FULL, PLAIN, ONEB>;
+        case SX_FUN_SPHERE: return pso_generation_kernel<SX_FUN_SPHERE, RNG, LPR, FULL, PLAIN, ONEB>;
     }
     if constexpr (!SPECIAL) {
         switch (fun_id) {
-            case SX_FUN_GRIEWANK: return pso_generation_kernel<SX_FUN_GRIEWANK, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
-            case SX_FUN_QUARTIC: return pso_generation_kernel<SX_FUN_QUARTIC, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
-            case SX_FUN_STYBLINSKI_TANG: return pso_generation_kernel<SX_FUN_STYBLINSKI_TANG, RNG, LPR, FULL, PLAIN, CHAIN, ONEB>;
+            case SX_FUN_GRIEWANK: return pso_generation_kernel<SX_FUN_GRIEWANK, RNG, LPR, FULL, PLAIN, ONEB>;
+            case SX_FUN_QUARTIC: return pso_generation_kernel<SX_FUN_QUARTIC, RNG, LPR, FULL, PLAIN, ONEB>;
+            case SX_FUN_STYBLINSKI_TANG: return pso_generation_kernel<SX_FUN_STYBLINSKI_TANG, RNG, LPR, FULL, PLAIN, ONEB>;
         }
     }
     return nullptr;
-}
-
-// the chained form: whole-batch rows (n = 64, 128, 256), in-kernel draws, constraints=None, no restart
-pso_kernel_t pick_chain_kernel(int fun_id, int n) {
-    switch (lanes_per_row(n)) {
-        case 16: return pick_kernel_lpr<SX_RNG_PHILOX, 16, true, true, true>(fun_id);
-        case 32: return pick_kernel_lpr<SX_RNG_PHILOX, 32, true, true, true>(fun_id);
-    }
-    return pick_kernel_lpr<SX_RNG_PHILOX, 64, true, true, true>(fun_id);
 }
 
 template <int RNG>
@@ -396,7 +270,7 @@ pso_kernel_t pick_kernel(int fun_id, int n, bool plain) {
     }
     if (full) return plain ? pick_kernel_lpr<RNG, 64, PH, PH>(fun_id) : pick_kernel_lpr<RNG, 64, PH>(fun_id);
     if (PH && n <= 4 * kWave && hot)  // rows of 129 ... 256 elements off the grid: the one-batch form of the whole-wave kernel
-        return pl ? pick_kernel_lpr<RNG, 64, false, PH, false, PH>(fun_id) : pick_kernel_lpr<RNG, 64, false, false, false, PH>(fun_id);
+        return pl ? pick_kernel_lpr<RNG, 64, false, PH, PH>(fun_id) : pick_kernel_lpr<RNG, 64, false, false, PH>(fun_id);
     return pl ? pick_kernel_lpr<RNG, 64, false, PH>(fun_id) : pick_kernel_lpr<RNG, 64, false>(fun_id);
 }
 
@@ -1183,7 +1057,7 @@ extern "C" int sx_pso_generation(const sx_pso_args *a, int finalize, void *strea
         const bool plain = a->constraints == 0 && a->pending_restart == nullptr;
         pso_kernel_t kern = a->rng == SX_RNG_PHILOX ? pick_kernel<SX_RNG_PHILOX>(a->fun_id, a->n, plain)
                                                      : pick_kernel<SX_RNG_HOST>(a->fun_id, a->n, plain);
-        hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.threads), g.lds, s, *a, plan, (double *)nullptr, 0, 0, (int64_t)0);
+        hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.threads), g.lds, s, *a, plan, (double *)nullptr, (int64_t)0);
         SX_LAUNCH_CHECK();
     }
     if (finalize)
@@ -1316,10 +1190,9 @@ extern "C" int sx_pso_graph_create(const sx_pso_args *a, int ngen, double *part_
     sx_pso_args args_inline = args;
     args_inline.pending_restart = sel3;
     double *no_rows_buf = nullptr;
-    int izero = 0;
     int64_t npart_gen = fused_radius ? (int64_t)g.blocks : 0;
-    void *gen_args[] = {&args, &plan, fused_radius ? &part_rold : &no_rows_buf, &izero, &izero, &npart_gen};
-    void *gen_args_inline[] = {&args_inline, &plan, fused_radius ? &part_rold : &no_rows_buf, &izero, &izero, &npart_gen};
+    void *gen_args[] = {&args, &plan, fused_radius ? &part_rold : &no_rows_buf, &npart_gen};
+    void *gen_args_inline[] = {&args_inline, &plan, fused_radius ? &part_rold : &no_rows_buf, &npart_gen};
     // restart kernels' arguments
     const double *fit = a->pbestfit;
     const double *pr = part_r;
@@ -1382,62 +1255,6 @@ extern "C" int sx_pso_graph_create(const sx_pso_args *a, int ngen, double *part_
                     return rc;
         }
     }
-    SX_HIP(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0));
-    *out = gr;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------
-// PSO, one kernel per generation ("chained": the best / termination step of generation g runs in the prologue of
-// the launch that produces g + 1; see pso_generation_kernel<..., CHAIN>).  Single GPU, in-kernel draws,
-// constraints=None, whole-batch rows (n = 64, 128, 256), no competitive restart.
-//   a->state   3 sx_state words: [0], [1] ping-pong, [2] the host's view (finalize_only launches)
-//   a->part_f / part_i   2 x npart records (rec = 2 * row + q)
-//   best_rows  2 x npart x n doubles: every workgroup's copy of its best row, double-buffered by q
-// ---------------------------------------------------------------------------
-extern "C" int sx_pso_chain_supported(const sx_pso_args *a) {
-    if (check_args(a)) return 0;
-    const Geometry g = geometry(a->P, a->n);
-    return hot_objective(a->fun_id) && a->rng == SX_RNG_PHILOX && a->constraints == 0 && a->pending_restart == nullptr &&
-                   a->n == 4 * lanes_per_row(a->n) && (int64_t)g.blocks <= (int64_t)kChainRecPerThread * g.threads
-               ? 1
-               : 0;
-}
-
-extern "C" int sx_pso_chain_launch(const sx_pso_args *a, double *best_rows, int parity, int finalize_only, void *stream) {
-    if (int rc = check_args(a)) return rc;
-    SX_REQUIRE(best_rows != nullptr && (parity == 0 || parity == 1), "sx_pso_chain_launch: bad arguments");
-    SX_REQUIRE(sx_pso_chain_supported(a), "sx_pso_chain_launch: shape / mode not supported by the chained kernel");
-    PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const Geometry g = geometry(a->P, a->n);
-    hipLaunchKernelGGL(pick_chain_kernel(a->fun_id, a->n), dim3(finalize_only ? 1u : g.blocks), dim3(g.threads), g.lds,
-                       (hipStream_t)stream, *a, plan, best_rows, parity, finalize_only ? 1 : 0, (int64_t)g.blocks);
-    SX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sx_pso_chain_graph_create(const sx_pso_args *a, double *best_rows, int ngen, int start_parity,
-                                         sx_graph **out) {
-    if (int rc = check_args(a)) return rc;
-    SX_REQUIRE(out != nullptr && ngen >= 1 && best_rows != nullptr && (start_parity == 0 || start_parity == 1),
-               "sx_pso_chain_graph_create: bad arguments");
-    SX_REQUIRE(sx_pso_chain_supported(a), "sx_pso_chain_graph_create: shape / mode not supported by the chained kernel");
-    PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const Geometry g = geometry(a->P, a->n);
-    sx_graph *gr = new sx_graph();
-    SX_HIP(hipGraphCreate(&gr->graph, 0));
-    sx_pso_args args = *a;
-    int par[2] = {0, 1}, mode = 0;
-    int64_t npart = g.blocks;
-    void *kargs[2][6] = {{&args, &plan, &best_rows, &par[0], &mode, &npart}, {&args, &plan, &best_rows, &par[1], &mode, &npart}};
-    void *fn = (void *)pick_chain_kernel(a->fun_id, a->n);
-    hipGraphNode_t prev = nullptr;
-    for (int i = 0; i < ngen; ++i)
-        if (int rc = add_kernel_node(gr->graph, &prev, fn, dim3(g.blocks), dim3(g.threads), (unsigned)g.lds,
-                                     kargs[(start_parity + i) & 1]))
-            return rc;
     SX_HIP(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0));
     *out = gr;
     return 0;

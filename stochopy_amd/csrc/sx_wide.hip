@@ -1139,9 +1139,8 @@ int wide_vd_candidates(const sx_vd_args *a, int64_t gen, int64_t row0, int64_t r
     // Always STREAMED (z parked in the y row): a resident row's 128 KB of LDS leave ONE workgroup per CU, and the generator's
     // arithmetic (Philox, log, sincos: ~65 us of VALU time chip-wide per 1 024 x 16 384 candidates), the row stores and
     // the objective of a candidate then run one after the other -- 216 us per generation at n = 16 384, P = 1 024 against
-    // SX_VD_RESIDENT=0's figure in profiles/r5_vd_wide.txt.  (z in registers -- 8 items per thread -- spills: 256 VGPRs + 1.5 KB.)
-    static const bool resident_ok = getenv("SX_VD_RESIDENT") != nullptr && getenv("SX_VD_RESIDENT")[0] == '1';
-    if (!resident_ok) g.chunk_leaves = 0, g.lds = wide_lds_bytes(a->n, false);
+    // the streamed form's figure in profiles/r5_vd_wide.txt.  (z in registers -- 8 items per thread -- spills: 256 VGPRs + 1.5 KB.)
+    g.chunk_leaves = 0, g.lds = wide_lds_bytes(a->n, false);
     sx_vd_args args = *a;
     void *kargs[] = {&args, &gen, &row0, &ary_out, &arx_out, &fit_out, &tk_out, &g.plan, &g.chunk_leaves};
     SX_HIP(hipLaunchKernel(g.fn, dim3((unsigned)rows), dim3(kGenThreads), kargs, g.lds, s));

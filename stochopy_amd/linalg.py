@@ -36,8 +36,8 @@ class Eigh:
     def __call__(self, Cmat, w=None, B=None, max_sweeps=0, tol=0.0, start=None, refine=None):
         """``start``: optional (n, n) nearly orthonormal basis to start from (the previous decomposition's B; may be
         the output buffer itself).  ``refine``: True / False allows / forbids the first-order refinement step in place of
-        the last sweep for THIS call (``sx_eigh_refined``: nothing process-wide is touched, so other host threads' runs keep
-        their mode); None: the library's current mode (``sx_eigh_set_refine`` / ``SX_EIGH_REFINE``)."""
+        the last sweep for THIS call (``sx_eigh_refined``); None: the library's default (forbidden, unless the environment
+        variable ``SX_EIGH_REFINE=1`` was set when the library was loaded)."""
         n = self.n
         if tuple(Cmat.shape) != (n, n) or not Cmat.is_contiguous():
             raise ValueError(f"expected a contiguous ({n},{n}) device matrix")

@@ -178,14 +178,7 @@ class _CmaDeviceRun(_evolution._DeviceRun):
         # enqueued in PIECES (_enqueue_phased) instead of a whole sweep of no-op launches "in case" (~30 of 3.5 us per
         # decomposition at n = 512).
         self._rps = rps = int(L.sx_eigh_rounds_per_sweep(n))
-        # Round 6: the solver's rounds run inside ONE resident launch that ends itself (sx_eigh_set_flow, csrc/sx_eigh.hip
-        # eigh_flow_kernel): nothing is launched "in case", so a decomposition gets the full allowance in one piece and
-        # the pieces are not needed.  Its grid must be on the chip at once: ranks that share a GPU (only possible
-        # without RCCL, i.e. the tests' gloo groups) take the launch-per-round form.
-        if self.world is not None and self.world.backend != "nccl":
-            L.sx_eigh_set_flow(0)
-        self._flow = rps > 0 and int(L.sx_eigh_set_flow(-2)) == 1
-        self._phased = (self.world is None and self.callback is None and self._look_cap() == 1 and rps > 0 and not self._flow
+        self._phased = (self.world is None and self.callback is None and self._look_cap() == 1 and rps > 0
                         and os.environ.get("SX_CMA_PHASED", "1") != "0")
         self._warm_rounds = None  # rounds the last phased decomposition needed
         self._cap_hit = False     # the last phased decomposition was still open when the round cap was reached
@@ -194,7 +187,7 @@ class _CmaDeviceRun(_evolution._DeviceRun):
         due = decomposition_due(gen, self._eigeneval, self.P, self.c1, self.cmu, self.n)
         if due:
             self._eigeneval = gen * self.P
-            self.args.eig_sweeps = self._launched = 60 if self._flow else (COLD_SWEEPS if due == 1 else self._warm_sweeps)
+            self.args.eig_sweeps = self._launched = COLD_SWEEPS if due == 1 else self._warm_sweeps
             self._decomposed = True
             if self._phased:
                 return self._enqueue_phased(gen, due)

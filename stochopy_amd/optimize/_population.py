@@ -1,8 +1,8 @@
 """The run driver DE (_de.py) and PSO / CPSO (_cpso.py) share: sharding prologue, exchange negotiation, graph capture,
 the chained kernels' graph cache and state reads, the views handed to callbacks and return_all, the generation loop and
-the result.  What differs between the methods is left to hooks of the subclasses (`_generation`, `_after_generation`,
-`_enqueue_external`, `_enqueue_and_look`, `_best_row`, `_settle_status`, `_chain_launch`, `_create_chain_graph`,
-`_chain_plan`)."""
+the result.  What differs between the methods is left to hooks of the subclasses: `_setup`, `_population`, `_generation`,
+`_after_generation`, `_enqueue_external`, `_enqueue_and_look`, `_best_row`, `_settle_status`; a run that sets `chain` (DE)
+also gives `_chain_launch`, `_create_chain_graph` and `_chain_plan`."""
 import os
 
 import numpy as np
@@ -19,6 +19,7 @@ _CAPTURE_FAILED = {"_rccl_graph_note": "graph capture of the rccl path failed",
 class _PopulationRun:
     MEMBERS, WHOLE = "individuals", "population"  # (words of the messages)
     CHECK_EVERY = 32  # generations between two looks at the device state when return_all keeps its history on the device
+    chain = False     # one kernel per generation (DE sets it per run; PSO has no such kernel)
 
     def __init__(self, method, fun_id, lower, upper, x0, maxiter, P, xtol, ftol, return_all, verbosity, callback, rng, seed,
                  workers, immediate):

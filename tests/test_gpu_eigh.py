@@ -201,28 +201,21 @@ def test_eigh_c4_golden_matrices(ctx):
 @pytest.mark.parametrize("kind,n", [("cma", 100), ("cma", 130), ("spd", 200), ("indefinite", 256), ("cma", 257), ("spd", 384),
                                     ("cma", 512), ("graded", 192), ("repeated", 192), ("diagonal", 96)])
 def test_eigh_with_the_refinement_step(ctx, kind, n):
-    """sx_eigh_set_refine(1): once what the sweeps left is first order against every gap (off <= 1e-7 |C|, max |K| <= 1e-3,
+    """refine=True: once what the sweeps left is first order against every gap (off <= 1e-7 |C|, max |K| <= 1e-3,
     max |K| * off <= 1e-12 |C|; measured on the device) the last sweep is replaced by V <- V (I + K + K^2/2) and the
     second-order term of the eigenvalues -- what the CMA-ES loops run with.  Never more sweeps than without it; the
     residual stays at the 1e-12 |C| level (the rule's bound), orthogonality at rounding level; eigenvectors of separated
     eigenvalues agree with LAPACK's; a multiple eigenvalue (`repeated`) does not trip the step up."""
-    from stochopy_amd import _lib
+    from stochopy_amd.linalg import Eigh
 
-    L = _lib.lib()
     rs = np.random.RandomState(77 + n)
     Cm = make(kind, n, rs)
     w0, B0, sweeps0, conv0, _ = run(ctx, Cm)
-    prev = L.sx_eigh_set_refine(1)
-    try:
-        from stochopy_amd.linalg import Eigh
-
-        eig = Eigh(ctx, n)
-        w, B = eig(ctx.upload(Cm))
-        sweeps, conv, off = eig.info()
-        refined = int(eig.ws[124:125].cpu().numpy().view(np.int32)[0])  # EighInfo.refine
-        w, B = w.cpu().numpy(), B.cpu().numpy()
-    finally:
-        L.sx_eigh_set_refine(prev)
+    eig = Eigh(ctx, n)
+    w, B = eig(ctx.upload(Cm), refine=True)
+    sweeps, conv, off = eig.info()
+    refined = int(eig.ws[124:125].cpu().numpy().view(np.int32)[0])  # EighInfo.refine
+    w, B = w.cpu().numpy(), B.cpu().numpy()
     assert sweeps <= sweeps0 and (not refined or sweeps < sweeps0 or sweeps0 == 0)
     wr, Br = check(Cm, w, B, sweeps, conv, EIG_RTOL=2e-12, RESID_TOL=2e-12, ORTH_TOL=1e-13)
     if n > 64 and kind in ("cma", "spd", "indefinite"):
@@ -236,14 +229,10 @@ def test_eigh_with_the_refinement_step(ctx, kind, n):
 @pytest.mark.parametrize("kind,n,warm", [("cma", 33, False), ("spd", 64, False), ("cma", 65, True), ("indefinite", 128, False),
                                          ("cma", 200, True), ("graded", 192, False), ("repeated", 192, False),
                                          ("cma", 512, True), ("spd", 512, False), ("cma", 1024, True)])
-def test_eigh_resident_launch_is_the_launch_per_round_run(ctx, kind, n, warm):
-    """Round 6: all rounds of a run inside ONE resident launch (sx_eigh_set_flow(1), the default: pair workgroups hand their
-    rotations on through agent-scope words, tile workgroups follow behind counters) against one launch per round
-    (sx_eigh_set_flow(0)): the same arithmetic on the same operands -- eigenvalues, eigenvectors and the run record equal
-    bit for bit, with and without a warm start and the refinement step."""
-    from stochopy_amd import _lib
-
-    L = _lib.lib()
+def test_eigh_launch_per_round_run_repeats_bit_for_bit(ctx, kind, n, warm):
+    """One launch per round, twice on the same input: the same arithmetic on the same operands -- eigenvalues, eigenvectors
+    and the run record equal bit for bit, with and without a warm start and the refinement step (passed per call).  (Until
+    the resident one-launch form of the rounds was removed this test compared that form with this one.)"""
     rs = np.random.RandomState(1000 + n)
     Cm = make(kind, n, rs)
     kw = {}
@@ -252,19 +241,10 @@ def test_eigh_resident_launch_is_the_launch_per_round_run(ctx, kind, n, warm):
         E = rs.randn(n, n) * 1e-3
         _, V = np.linalg.eigh(Cs + (E + E.T) * np.abs(Cs).max())
         kw["start"] = ctx.upload(np.ascontiguousarray(V))
-    outs = []
-    prev = L.sx_eigh_set_flow(-2)
-    try:
-        for refine in (False, True):
-            for mode in (0, 1, 1):
-                L.sx_eigh_set_flow(mode)
-                outs.append((refine, mode) + run(ctx, Cm, refine=refine, **kw))
-    finally:
-        L.sx_eigh_set_flow(prev)
-    for k in range(0, len(outs), 3):
-        ref = outs[k]
-        check(Cm, *ref[2:6])
-        for got in outs[k + 1:k + 3]:
-            assert got[4:6] == ref[4:6], (got[:2], got[4:6], ref[4:6])  # sweeps, converged
-            assert np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), (kind, n, got[:2])
-            assert abs(got[6] - ref[6]) <= 1e-12 * max(ref[6], 1e-300)  # (sums of atomics: the order of arrival)
+    for refine in (False, True):
+        ref = run(ctx, Cm, refine=refine, **kw)
+        got = run(ctx, Cm, refine=refine, **kw)
+        check(Cm, *ref[:4])
+        assert got[2:4] == ref[2:4], (refine, got[2:4], ref[2:4])  # sweeps, converged
+        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), (kind, n, refine)
+        assert abs(got[4] - ref[4]) <= 1e-12 * max(ref[4], 1e-300)  # (sums of atomics: the order of arrival)

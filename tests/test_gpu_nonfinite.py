@@ -332,13 +332,12 @@ def test_long_cpso_run_with_nonfinite_x0(sa, path, form):
 
 
 @pytest.mark.parametrize("method", ["pso", "cpso"])
-def test_chained_pso_kernel_nan_in_a_later_wave(sa, method, monkeypatch):
-    """The one-kernel PSO generation (SX_PSO_CHAIN=1, n = 4 * LPR = 64) with more than 64 workgroups, so the records
-    spread over several waves of the finalising workgroup: a NaN row in the last records (a later wave) must beat the
-    finite minimum in wave 0's records."""
+def test_pso_kernel_nan_in_a_later_wave(sa, method):
+    """The PSO generation (n = 4 * LPR = 64) with more than 64 workgroups, so the records spread over several waves of
+    the finalising workgroup: a NaN row in the last records (a later wave) must beat the finite minimum in wave 0's
+    records."""
     from stochopy_amd import _device
 
-    monkeypatch.setenv("SX_PSO_CHAIN", "1")
     L = _device.Context().L
     n, P = 64, 8192
     rpw = int(L.sx_rows_per_workgroup(n))

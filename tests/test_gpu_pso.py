@@ -226,31 +226,13 @@ def test_cpso_graph_two_launches_per_generation_all_three_forms_agree(sa, object
     ("sphere", 64, 40, 70, -1.0), ("rosenbrock", 128, 33, 45, -1.0), ("sphere", 256, 70, 301, -1.0),
     ("ackley", 256, 2048, 90, -1.0), ("sphere", 64, 512, 4000, 1e-3), ("sphere", 128, 300, 4000, 30.0),
     ("rastrigin", 256, 16384, 40, -1.0)])
-def test_pso_chained_kernel_equals_two_kernel_path_and_oracle(sa, objective, n, P, maxiter, ftol, monkeypatch):
-    """Plain PSO on whole-batch rows CAN run one kernel per generation (opt-in SX_PSO_CHAIN=1; csrc/sx_pso.hip CHAIN: best / termination in the next
-    launch's prologue, gbest read from per-workgroup best-row copies; replayed 32-generation graphs + eager tail + the
-    finalise-only looks).  Same run, bit for bit, as the generation + select_finalize pair (SX_PSO_CHAIN=0) and as the
-    oracle: fun, x, nit, status -- including stops on ftol (status 0 / 1 settled from the two resident best rows) and
-    run lengths that are no multiple of the graph length."""
-    from stochopy_amd.optimize import _cpso
-
+def test_pso_whole_batch_rows_equal_the_oracle(sa, objective, n, P, maxiter, ftol):
+    """Plain PSO on whole-batch rows (the generation + select_finalize pair; replayed graphs + eager tail): same run as the
+    oracle -- fun, x, nit, status -- including stops on ftol and run lengths that are no multiple of the graph length.
+    (Until the one-kernel-per-generation form was removed this test also compared that form with this one.)"""
     opts = {"maxiter": maxiter, "popsize": P, "seed": 31 + n, "updating": "deferred", "ftol": ftol, "xtol": 1e-9}
     bounds = [[-3.0, 2.0]] * n
-    chained = []
-    orig = _cpso._PsoRun._setup
-
-    def spy(self):
-        orig(self)
-        chained.append(self.chain)
-
-    monkeypatch.setattr(_cpso._PsoRun, "_setup", spy)
-    monkeypatch.setenv("SX_PSO_CHAIN", "1")  # (opt-in: measured slower than the two-kernel path, see _cpso.py)
     got = sa.optimize.minimize(getattr(sa.factory, objective), bounds, method="pso", options=dict(opts, backend="hip", rng="philox"))
-    monkeypatch.setenv("SX_PSO_CHAIN", "0")
-    two = sa.optimize.minimize(getattr(sa.factory, objective), bounds, method="pso", options=dict(opts, backend="hip", rng="philox"))
-    assert chained == [True, False]
-    assert (got.fun, got.nit, got.nfev, got.status, got.message) == (two.fun, two.nit, two.nfev, two.status, two.message)
-    assert np.array_equal(got.x, two.x)
     if P <= 4096:
         ref = oracle.minimize(objective, bounds, method="pso", options=dict(opts), rng="philox")
         assert (got.nit, got.status) == (ref.nit, ref.status)

@@ -460,35 +460,30 @@ def test_chained_generations_are_planned_as_few_graph_replays():
     assert all(k[1] % 2 == 0 and 10 < k[1] < 50 for k in seen)
 
 
-def test_pso_chained_generations_are_whole_graphs_then_single_launches():
-    """_PsoRun's chained plan through the shared enqueue (_PopulationRun._enqueue_chain): whole GRAPH_CHUNK-generation
-    graphs, then one launch per generation left; a graph is the one built for the launch parity it starts at, and the
-    launches carry on with the parity the generations count gives them."""
-    import types
+def test_oracle_modules_define_every_name_once():
+    """The parity anchor must say one thing: no module under oracle/ defines a top-level name, or a method within a
+    class, twice (Python silently keeps the last definition, so a stale copy above it passes every test)."""
+    import ast
+    import glob
+    import os
 
-    from stochopy_amd.optimize._cpso import _PsoRun
-
-    assert _PsoRun.plan_chain(70, 32) == [32, 32] + [0] * 6
-    assert _PsoRun.plan_chain(31, 32) == [0] * 31
-    assert _PsoRun.plan_chain(256, 32) == [32] * 8
-    events = []
-    run = _PsoRun.__new__(_PsoRun)  # the host logic only: the library calls are stand-ins
-    run.ctx = types.SimpleNamespace(L=types.SimpleNamespace(sx_graph_launch=lambda g, s: events.append(("graph",) + g) or 0),
-                                    stream_ptr=None)
-    run.launches, run._chain_graphs, run.GRAPH_CHUNK = 0, {}, 32
-    run._create_chain_graph = lambda par, size: (par, size)
-    run._chain_launch = lambda par, finalize_only: events.append(("launch", par, finalize_only))
-    expected, at = [], 0
-    for ngen in (70, 5, 64, 31, 33):
-        run._enqueue_chain(ngen)
-        for _ in range(ngen // 32):
-            expected.append(("graph", at & 1, 32))
-            at += 32
-        for _ in range(ngen % 32):
-            expected.append(("launch", at & 1, 0))
-            at += 1
-    assert events == expected and run.launches == at == 203
-    assert sorted(run._chain_graphs) == [(0, 32), (1, 32)]  # one graph per parity, built once
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    files = sorted(glob.glob(os.path.join(root, "**", "*.py"), recursive=True))
+    assert files
+    defs = (ast.FunctionDef, ast.AsyncFunctionDef, ast.ClassDef)
+    twice = []
+    for path in files:
+        with open(path) as f:
+            tree = ast.parse(f.read(), path)
+        scopes = [("", tree.body)] + [(c.name + ".", c.body) for c in ast.walk(tree) if isinstance(c, ast.ClassDef)]
+        for prefix, body in scopes:
+            seen = {}
+            for node in body:
+                if isinstance(node, defs):
+                    if node.name in seen:
+                        twice.append(f"{os.path.relpath(path, root)}: {prefix}{node.name} at lines {seen[node.name]} and {node.lineno}")
+                    seen[node.name] = node.lineno
+    assert not twice, twice
 
 
 @pytest.mark.parametrize("P,n", [(2, 3), (7, 5), (100, 70), (513, 2), (4096, 128)])

@@ -1,4 +1,4 @@
-"""The eigensolver with and without the first-order refinement step (sx_eigh_set_refine): sweeps, residual, orthogonality,
+"""The eigensolver with and without the first-order refinement step (Eigh.__call__(refine=...)): sweeps, residual, orthogonality,
 eigenvalue and eigenvector agreement with LAPACK (canonical signs) on test matrices and on the covariance matrices of a
 C4 run (warm-started from the previous generation's LAPACK eigenvectors, as the CMA-ES loop does).  usage: [n P gens]"""
 import os, sys
@@ -7,12 +7,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np
 import oracle
 from oracle import engine as oe
-from stochopy_amd import _device, _lib
+from stochopy_amd import _device
 from stochopy_amd.linalg import Eigh
 from test_gpu_eigh import make
 
 ctx = _device.Context()
-L = _lib.lib()
 
 
 def stats(Cm, w, B):
@@ -28,12 +27,11 @@ def one(tag, Cm, start=None, tol=0.0):
     n = len(Cm)
     out = []
     for mode in (0, 1):
-        L.sx_eigh_set_refine(mode)
         eig = Eigh(ctx, n)
         kw = {}
         if start is not None:
             kw["start"] = ctx.upload(start)
-        w, B = eig(ctx.upload(Cm), tol=tol, **kw)
+        w, B = eig(ctx.upload(Cm), tol=tol, refine=bool(mode), **kw)
         sw, conv, off = eig.info()
         hdr = eig.ws[:2].cpu().numpy().view(np.int32)
         raw = eig.ws[:256].cpu().numpy()
@@ -43,7 +41,6 @@ def one(tag, Cm, start=None, tol=0.0):
         e = stats(Cm, w.cpu().numpy(), B.cpu().numpy())
         out.append("mode %d: sweeps %2d conv %d refined %d | eig %.1e resid %.1e orth %.1e vec %.1e | off/maxK after the last two sweeps: %s"
                    % ((mode, sw, conv, refined) + e + (" ".join(left),)))
-    L.sx_eigh_set_refine(-1)
     print(tag, "\n   " + "\n   ".join(out), flush=True)
 
 
