@@ -58,7 +58,8 @@ const char *sx_last_error(void);
 /* number of visible HIP devices (<0 on error); used by the loader to fail loudly */
 int sx_device_count(void);
 /* sizeof(sx_state / sx_de_args / sx_pso_args / sx_xchg_args) as compiled: lets a binding check its struct
- * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args; -1 otherwise) */
+ * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args,
+ * 8 DE-runs args; -1 otherwise) */
 int sx_struct_size(int which);
 
 /* ------------------------------------------------------------------------- *
@@ -694,6 +695,47 @@ int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *str
 int sx_sample_chains_per_workgroup(int method, int jac, int n);
 /* G[i,:] = analytic gradient of objective fun_id at X[i,:] (the hmc kernel's device functions), X / G (P,n) DEVICE */
 int sx_sample_gradient(int fun_id, const double *X, int64_t P, int n, double *G, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).
+ * replaces: R calls of de/_de.py:176-301 (`de`: initial population :208-218, the generation loop :236-283) with
+ *           de_sync (:314-351), the strategies (de/_strategy.py:1-46), Random (de/_constraints.py:13-28),
+ *           selection_sync (_common.py:123-130) and the termination ladder (_common.py:131-158) -- everything a run of
+ *           `updating="deferred"` does, for R runs that differ in their Philox key (and, optionally, their x0) only.
+ * One workgroup carries one run from its initial population to its termination: both population buffers (generation g
+ * in buffer g & 1, as in sx_de_args) and the fitness values live in the workgroup's LDS, a generation is separated from
+ * the next by two workgroup barriers, and nothing is exchanged between runs.  Run r draws with keys[r]: its counters
+ * are those of the single-run kernels (row = the row within the run), so run r IS the run sx_de_chain_launch performs
+ * with that key -- same population, same best, same nit and status, bit for bit.  In-kernel draws only.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_de_runs_args {
+    const uint32_t *keys;   /* DEVICE (R,2) Philox key (key0, key1) of run r                               */
+    const double *lower;    /* DEVICE (n)                                                                  */
+    const double *upper;    /* DEVICE (n)                                                                  */
+    const double *x0;       /* DEVICE initial populations, (P,n) each, run stride x0_stride; NULL: run r draws the
+                               Latin hypercube of sx_philox_lhs with keys[r] (_common.py:109-120)          */
+    double *xs;             /* DEVICE (R,n) OUT best individual of run r                                   */
+    double *funs;           /* DEVICE (R)   OUT its value                                                  */
+    int64_t *nits;          /* DEVICE (R)   OUT generations (the reference's `it`; the initial one counts) */
+    int32_t *statuses;      /* DEVICE (R)   OUT -1 / 0 / 1 (_common.py:134-158)                            */
+    double *xfinal;         /* DEVICE (R,P,n) OUT final population of run r, or NULL                       */
+    int64_t R;
+    int64_t P;
+    int64_t x0_stride;      /* 0 (one population shared by all runs) or P*n                                */
+    int32_t n;              /* 1 ... sx_wide_from()                                                        */
+    int32_t fun_id;
+    int32_t strategy;
+    int32_t constraints;    /* 0 none, 1 Random                                                            */
+    int32_t maxiter;        /* <= 1: one generation is still run (de/_de.py:236-283)                       */
+    int32_t pad;
+    double F, CR, xtol, ftol;
+} sx_de_runs_args;
+
+/* all R runs, from the initial population to each run's own termination: one launch, R workgroups */
+int sx_de_runs_launch(const sx_de_runs_args *a, void *stream);
+/* bytes of LDS one run of popsize P and row length n needs (host only, no device touched); negative when that is more
+ * than a workgroup may declare (160 KiB on gfx950), n > sx_wide_from() or the shape is invalid */
+int64_t sx_de_runs_lds_bytes(int64_t P, int n);
 
 #ifdef __cplusplus
 }

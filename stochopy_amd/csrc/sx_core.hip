@@ -34,6 +34,7 @@ extern "C" int sx_struct_size(int which) {
         case 5: return (int)sizeof(sx_cma_args);
         case 6: return (int)sizeof(sx_vd_args);
         case 7: return (int)sizeof(sx_sample_args);
+        case 8: return (int)sizeof(sx_de_runs_args);
     }
     return -1;
 }
@@ -1179,29 +1180,7 @@ __global__ __launch_bounds__(256) void philox_lhs_kernel(double *__restrict__ X,
     if (t >= rows * n) return;
     const int64_t r = t / n;
     const int e = (int)(t % n);
-    const uint64_t gi = (uint64_t)(row0 + r);
-    // the column's permutation keys
-    const U4 ka = philox4x32_10((uint32_t)e, 0u, 0u, kPurposeInitPerm, k0, k1);
-    const U4 kb = philox4x32_10((uint32_t)e, 1u, 0u, kPurposeInitPerm, k0, k1);
-    const uint64_t m[3] = {(uint64_t)(ka.x | 1u), (uint64_t)(ka.y | 1u), (uint64_t)(ka.z | 1u)};
-    const uint64_t ad[3] = {(uint64_t)kb.x, (uint64_t)kb.y, (uint64_t)kb.z};
-    int b = 1;
-    while (((uint64_t)1 << b) < (uint64_t)P) ++b;  // P >= 2: b = bit_length(P - 1)
-    const uint64_t mask = ((uint64_t)1 << b) - 1u;
-    const int sh = (b + 1) / 2;
-    uint64_t x = gi;
-    do {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x = (x * m[k] + ad[k]) & mask;
-            x ^= x >> sh;
-        }
-    } while (x >= (uint64_t)P);
-    const double u = philox_u53(e, lanes_per_row(n), (uint32_t)gi, 0u, kPurposeInitJitter, k0, k1);
-    const double step = 2.0 / (double)P;                      // np.linspace(-1, 1, P, endpoint=False): arange * step + start
-    const double v = u / (double)P + ((double)x * step + -1.0);
-    const double lo = lower[e], hi = upper[e];
-    X[r * ld + e] = v * (0.5 * (hi - lo)) + 0.5 * (hi + lo);
+    X[r * ld + e] = philox_lhs_element((uint64_t)(row0 + r), e, P, n, lower[e], upper[e], k0, k1);
 }
 
 extern "C" int sx_philox_lhs(double *X, int64_t rows, int n, int64_t ld, int64_t row0, int64_t P, const double *lower,

@@ -526,6 +526,34 @@ __device__ __forceinline__ double pso_velocity(double w, double v, double c1, do
     return (w * v + (c1 * r1) * (p - x)) + (c2 * r2) * (g - x);
 }
 
+// Element e of row gi of the Philox-mode initial population of P rows (the Latin hypercube of _common.py:109-120, described at
+// philox_lhs_kernel in sx_core.hip): shared by that kernel and the resident DE runs (sx_de_runs.hip), which draw a run's
+// hypercube themselves -- one function, so the same bits.
+__device__ __forceinline__ double philox_lhs_element(uint64_t gi, int e, int64_t P, int n, double lo, double hi, uint32_t k0,
+                                                     uint32_t k1) {
+    // the column's permutation keys
+    const U4 ka = philox4x32_10((uint32_t)e, 0u, 0u, kPurposeInitPerm, k0, k1);
+    const U4 kb = philox4x32_10((uint32_t)e, 1u, 0u, kPurposeInitPerm, k0, k1);
+    const uint64_t m[3] = {(uint64_t)(ka.x | 1u), (uint64_t)(ka.y | 1u), (uint64_t)(ka.z | 1u)};
+    const uint64_t ad[3] = {(uint64_t)kb.x, (uint64_t)kb.y, (uint64_t)kb.z};
+    int b = 1;
+    while (((uint64_t)1 << b) < (uint64_t)P) ++b;  // P >= 2: b = bit_length(P - 1)
+    const uint64_t mask = ((uint64_t)1 << b) - 1u;
+    const int sh = (b + 1) / 2;
+    uint64_t x = gi;
+    do {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            x = (x * m[k] + ad[k]) & mask;
+            x ^= x >> sh;
+        }
+    } while (x >= (uint64_t)P);
+    const double u = philox_u53(e, lanes_per_row(n), (uint32_t)gi, 0u, kPurposeInitJitter, k0, k1);
+    const double step = 2.0 / (double)P;                      // np.linspace(-1, 1, P, endpoint=False): arange * step + start
+    const double v = u / (double)P + ((double)x * step + -1.0);
+    return v * (0.5 * (hi - lo)) + 0.5 * (hi + lo);
+}
+
 // run `body(std::integral_constant<int, LPR>)` for the LPR that lanes_per_row(n) prescribes
 #define SX_DISPATCH_LPR(n, CALL)            \
     switch (lanes_per_row(n)) {             \
