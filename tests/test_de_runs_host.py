@@ -3,10 +3,15 @@ and the argument checks of optimize.minimize(method="de", options={"runs": R}), 
 `runs` before a device is needed."""
 import ctypes as C
 import os
+import sys
 import warnings
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _de_runs_abi  # noqa: E402
 
 LDS_LIMIT = 160 * 1024  # what one workgroup may declare on gfx950
 
@@ -109,3 +114,25 @@ def test_reference_checks_still_come_first(sa):
         _call(sa, popsize=3, strategy="rand2bin")  # five donors out of two other rows
     with pytest.raises(ValueError):
         _call(sa, x0=np.zeros((P + 1, N)))
+
+
+@pytest.mark.parametrize("n", [3, 64, 256, 257, 1024, 2048])
+def test_lds_budget_at_its_limit(lib, sa, n):
+    """The largest population sx_de_runs_lds_bytes accepts for rows of n elements: within 160 KiB, one row more refused,
+    strictly increasing below it, and everywhere the bytes of the layout the kernel's header comment documents --
+    buf[2][P][stride] | fit[P] | 4 broadcast words, stride = n + 8 up to 256 elements, n + 8 + 2 (n // 64 + 2) above (the
+    broadcast words are the LAST bytes of the run's LDS: a budget short of them is a write past it).  The front end refuses
+    the first population that does not fit, before a device is needed."""
+    pmax = _de_runs_abi.largest_popsize(lib, n)
+    stride = n + 8 if n <= 256 else n + 8 + 2 * (n // 64 + 2)
+    assert _de_runs_abi.stride_doubles(n) == stride
+    top = lib.sx_de_runs_lds_bytes(pmax, n)
+    assert 0 < top <= 163840 == LDS_LIMIT
+    assert lib.sx_de_runs_lds_bytes(pmax + 1, n) < 0
+    assert 8 * (2 * (pmax + 1) * stride + (pmax + 1) + 4) > LDS_LIMIT  # pmax + 1 is refused because it does not fit
+    got = np.array([lib.sx_de_runs_lds_bytes(P, n) for P in range(2, pmax + 1)], dtype=np.int64)
+    assert (np.diff(got) > 0).all()
+    P = np.arange(2, pmax + 1, dtype=np.int64)
+    assert np.array_equal(got, 8 * (2 * P * stride + P + 4))
+    with pytest.raises(ValueError, match="runs.*LDS.*160 KiB"):  # the budget check, not an earlier refusal
+        _call(sa, runs=2, popsize=pmax + 1, n=n, strategy="rand1bin")
