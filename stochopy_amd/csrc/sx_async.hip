@@ -105,7 +105,7 @@ __device__ __forceinline__ void publish(sx_state *st, int64_t it, double gfit, i
 }
 
 // NFIX: the row length when it is exactly 4 * LPR (64, 128, 256) and the draws are made in the kernel -- a compile-time
-// constant, and with it numpy's summation plan (sx_device.hpp row_reduce_fixed / row_reduce_static); 0 otherwise.
+// constant, and with it numpy's summation plan (sx_rowops.hpp row_objective_chain); 0 otherwise.
 template <int FUN, int RNG, int LPR, int NFIX = 0>
 __global__ __launch_bounds__(sweep_waves(FUN) * kWave) void de_async_kernel(const sx_de_args a, const PlanArg plan) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(sweep_waves(FUN) * kWave) void de_async_kernel(cons
             U[e] = cand;
             }
         }
-        return row_objective<FUN, LPR, false, NFIX, 0>(U, n, plan, l);
+        return row_objective<FUN, LPR, NFIX, 0>(U, n, plan, l);
     };
 
     for (int64_t i0 = 0; i0 < P; i0 += B) {
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(sweep_waves(FUN) * kWave) void pso_async_kernel(con
                 U[e] = xr[e] + vn;
             }
         }
-        return row_objective<FUN, LPR, false, NFIX, 0>(U, n, plan, l);
+        return row_objective<FUN, LPR, NFIX, 0>(U, n, plan, l);
     };
 
     for (int64_t i0 = 0; i0 < P; i0 += B) {

@@ -167,7 +167,7 @@ int make_plan_arg(int fun_id, int n, PlanArg *out) {
 // ---------------------------------------------------------------------------
 // FULL: n is a whole number of 4-step batches and P a whole number of workgroups (no bounds test survives);
 // NFIX: FULL with n == 4 * LPR exactly (64 / 128 / 256): the row length, and with it numpy's summation plan, is a
-// compile-time constant (row_reduce_fixed / row_reduce_static, as in the one-batch DE / PSO kernels); 0 otherwise.
+// compile-time constant (row_objective_chain / row_reduce_long, as in the one-batch DE / PSO kernels); 0 otherwise.
 template <int FUN, int LPR, bool FULL = false, int NFIX = 0>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void eval_kernel(
     const double *__restrict__ X, int64_t P, int n_arg, int64_t ldx, const double *__restrict__ xm,
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void eval_kernel(
         pacc = row_sum<LPR>(pacc);
         if (id.active && id.l == 0) pen_out[id.row] = pacc;
     }
-    const double val = row_objective<FUN, LPR, FULL, NFIX>(U, n, plan, id.l);
+    const double val = row_objective<FUN, LPR, NFIX>(U, n, plan, id.l);
     if ((FULL || id.active) && id.l == 0) f[id.row] = val;
     if (part_f != nullptr) block_partial<LPR>(val, id, sf, si, part_f, part_i);
 }
@@ -319,6 +319,11 @@ __global__ __launch_bounds__(256) void eval_r8_kernel(const double *__restrict__
     if (j == (TAIL > 0 ? TAIL - 1 : 0)) f[row0 + r] = val;
 }
 
+// Loads of a leaf that eval_r8_rt_kernel / eval_r8_long_kernel keep in flight together (round 6: objectives without a
+// neighbour term take the whole leaf's 16 loads in one batch -- twice the bytes in flight per wave in front of the 16
+// cosines; batches of eight before that)
+constexpr int kEvalLeafBatch = 16;
+
 // The same mapping for one-batch rows of ANY length (n <= 256: at most three leaves of at most 16 blocks, PlanArg), straight from
 // memory: lane (r, j) of a wavefront owns accumulator j of row r, so the elements it needs -- 8k + j -- are exactly the ones it
 // loads (eight rows x 64 consecutive bytes per load instruction, consecutive blocks in consecutive instructions: every 128-byte
@@ -344,12 +349,8 @@ __global__ __launch_bounds__(256) void eval_r8_rt_kernel(const double *__restric
         if (t >= nleaf) break;  // (uniform)
         const int b0 = t > 0 ? plan.end[t - 1] : 0, cnt = plan.end[t] - b0;
         double chA = 0.0, chB = identB;
-        // (round 6: objectives without a neighbour term take the whole leaf's 16 loads in one batch -- twice the bytes in
-        //  flight per wave in front of the 16 cosines; SX_EVAL_RT_HB=8 restores the batches of eight for an A/B)
-#ifndef SX_EVAL_RT_HB
-#define SX_EVAL_RT_HB 16
-#endif
-        constexpr int HB = O::NEXT ? 8 : SX_EVAL_RT_HB;
+        // (the leaf walk below is eval_r8_long_kernel's too: two bodies on purpose, a shared helper costs registers)
+        constexpr int HB = O::NEXT ? 8 : kEvalLeafBatch;
 #pragma unroll
         for (int h0 = 0; h0 < kLeafBlocks; h0 += HB) {
             double x[HB], xn[O::NEXT ? HB : 1];
@@ -448,12 +449,8 @@ __global__ __launch_bounds__(256) void eval_r8_long_kernel(const double *__restr
     for (int t = 0; t < nleaf; ++t) {  // (uniform)
         const int b0 = t > 0 ? plan.end[t - 1] : 0, cnt = plan.end[t] - b0;
         double chA = 0.0, chB = identB;
-        // (round 6: objectives without a neighbour term take the whole leaf's 16 loads in one batch -- twice the bytes in
-        //  flight per wave in front of the 16 cosines; SX_EVAL_RT_HB=8 restores the batches of eight for an A/B)
-#ifndef SX_EVAL_RT_HB
-#define SX_EVAL_RT_HB 16
-#endif
-        constexpr int HB = O::NEXT ? 8 : SX_EVAL_RT_HB;
+        // (the leaf walk below is eval_r8_rt_kernel's too: two bodies on purpose, a shared helper costs registers)
+        constexpr int HB = O::NEXT ? 8 : kEvalLeafBatch;
 #pragma unroll
         for (int h0 = 0; h0 < kLeafBlocks; h0 += HB) {
             double x[HB], xn[O::NEXT ? HB : 1];
@@ -528,126 +525,123 @@ __global__ __launch_bounds__(256) void eval_r8_long_kernel(const double *__restr
         if (live) f[row] = O::finish(sa, sb, n);
     }
 }
-// mode 2 (measurement): also the cheap objectives at n = 512 / 1024 / 2048 and beyond 3584 elements
-static int eval_r8_long_mode() {
-    static const int mode = getenv("SX_EVAL_R8LONG") ? atoi(getenv("SX_EVAL_R8LONG")) : 1;
-    return mode;
-}
-// From which population size on (profiles/r5_eval_small_p.txt: a row is a serial walk of n / 8 blocks here, so a small population
-// is faster one wavefront per row): off the compile-time grid 8192 rows (a cosine per term: 16 384); where the alternative is a
-// compile-time plan or the workgroup per row (n = 512 / 1024 / 2048, n > 2048), measured at large P only: 32 768.
-static int64_t eval_r8_min_rows(int64_t dflt) {
-    static const int64_t forced = getenv("SX_EVAL_R8_MIN") ? atoll(getenv("SX_EVAL_R8_MIN")) : -1;
-    return forced >= 0 ? forced : dflt;
-}
-static bool eval_r8_long_ok(int64_t P, int n, const double *xm, const double *part_f, int clip, int nleaf, bool cheap) {
-    const bool has_rival = n > kWideFrom || n == 512 || n == 1024 || n == 2048;
-    return eval_r8_long_mode() != 0 && n > 256 && n <= kMaxDim && nleaf >= 1 && nleaf <= kMaxLeaf && xm == nullptr &&
-           part_f == nullptr && clip == 0 && P >= eval_r8_min_rows(has_rival ? 32768 : cheap ? 8192 : 16384);
-}
+// ---------------------------------------------------------------------------
+// Which form an evaluation takes (host).  One function: sx_eval's "wide or not" and launch_eval's kernel choice are the
+// same decision.
+// ---------------------------------------------------------------------------
+enum class EvalForm {
+    R8Long,       // eval_r8_long_kernel: eight lanes per row, rows of 257 ... kMaxDim elements straight from memory
+    LongPlan,     // eval_kernel<64, true, 512 / 1024 / 2048>: numpy's plan as constants (row_reduce_long)
+    R8Rt,         // eval_r8_rt_kernel: eight lanes per row, one-batch rows of any length straight from memory
+    R8Fixed,      // eval_r8_kernel<64 / 128 / 256>: eight lanes per row, LDS-staged, compile-time length
+    ChainFixed,   // eval_kernel<LPR, true, 4 LPR>: the compile-time register chain
+    GeneralFull,  // eval_kernel<LPR, true>: whole batches and whole workgroups, no bounds test
+    General,      // eval_kernel<LPR, false>
+    Wide,         // one workgroup per row (sx_wide.hip)
+};
+// Population sizes from which the eight-lanes-per-row kernels take over (profiles/r5_eval_small_p.txt: a row is a serial walk
+// of n / 8 blocks there, so a small population is faster one wavefront per row): off the compile-time grid 8192 rows (long
+// rows with a cosine per term: 16 384); where the alternative is a compile-time form or the workgroup per row (n = 64 / 128 /
+// 256, n = 512 / 1024 / 2048, n > 2048), measured at large P only: 32 768.
+constexpr int64_t kR8MinRows = 8192, kR8MinRowsHeavyLong = 16384, kR8MinRowsRival = 32768;
+// The cheap objectives from ~3600 elements on stay with the workgroup per row (n = 4096: 0.59-0.74 of the HBM peak against
+// 0.56-0.63: rows a power of two apart meet in the same memory channels; profiles/r5_eval_r8_rt.txt, part 4)
+constexpr int kR8LongLightMax = 3584;
 
-// mode 1: rows off the compile-time grid; 2: every one-batch row (measurement: against eval_r8_kernel at n = 64 / 128 / 256)
-static int eval_r8_rt_mode() {
-    static const int mode = getenv("SX_EVAL_R8RT") ? atoi(getenv("SX_EVAL_R8RT")) : 1;
-    return mode;
-}
-static bool eval_r8_rt_ok(int64_t P, int n, const double *xm, const double *part_f, int clip) {
+static EvalForm eval_form(int fun_id, int64_t P, int n, bool ldx_even, bool x_aligned16, bool has_xm, bool has_part,
+                          int clip, int nleaf) {
+    const bool hot = hot_objective(fun_id), light = light_objective(fun_id);
+    const bool plain = !has_xm && !has_part && clip == 0;  // the eight-lanes-per-row kernels: objective values only
+    const int lpr = lanes_per_row(n);
+    const bool whole = clip == 0 && P % rows_per_block(n) == 0;  // whole workgroups (the clip / penalty variants keep the
+                                                                 // general kernel, to keep the build small)
+    // (the compile-time row lengths -- one-batch rows, n = 512 / 1024 / 2048 -- for the four hot objectives only: hot_objective)
+    const bool fix = hot && whole && n == 4 * lpr;
+    const bool grid_long = hot && whole && (n == 512 || n == 1024 || n == 2048);
+    // Many long rows: eight lanes per row, straight from memory.  Not the cheap objectives at n = 512 / 1024 / 2048: their
+    // compile-time plan stays ahead (Rosenbrock 0.61 / 0.76 / 0.66 of the HBM peak against 0.58 / 0.54 / 0.55); the cosine
+    // objectives gain there too (Ackley 0.30 / 0.47 / 0.35 -> 0.49 / 0.50 / 0.48): profiles/r5_eval_r8_rt.txt.  Beyond
+    // kWideFrom the rival is the workgroup per row -- Rosenbrock n = 2049 / 3000 0.45 / 0.49 -> 0.56 / 0.54 of the HBM peak,
+    // Ackley n = 2049 / 4096 0.28 / 0.43 -> 0.50 / 0.48.
+    if (plain && n > 256 && n <= kMaxDim && nleaf >= 1 && nleaf <= kMaxLeaf) {
+        const bool rival = n > kWideFrom || n == 512 || n == 1024 || n == 2048;
+        const bool many = P >= (rival ? kR8MinRowsRival : light ? kR8MinRows : kR8MinRowsHeavyLong);
+        if (many && !(light && (grid_long || n > kR8LongLightMax))) return EvalForm::R8Long;
+    }
+    if (is_wide(n, kWideFrom)) return EvalForm::Wide;
+    // long rows of a compile-time length: numpy's plan as constants (row_reduce_long).  Rosenbrock n = 1024: 0.54 -> 0.84
+    // of the HBM peak, n = 512: 0.44 -> 0.76, n = 2048: 0.43 -> 0.70 (profiles/r4_eval_long_rows.txt; a resident,
+    // software-pipelined form of the same kernel stayed at 0.72 and was dropped)
+    if (grid_long) return EvalForm::LongPlan;
     const bool on_grid = n == 64 || n == 128 || n == 256;
-    return eval_r8_rt_mode() != 0 && n >= 16 && n <= 256 && xm == nullptr && part_f == nullptr && clip == 0 &&
-           P >= eval_r8_min_rows(on_grid ? 32768 : 8192);
+    const bool r8_rt_ok = plain && n >= 16 && n <= 256 && P >= (on_grid ? kR8MinRowsRival : kR8MinRows);
+    // rows of 256 elements with a cosine per term: the run-time form (no staging, 16 terms at a time) is the faster one --
+    // Ackley 0.45 -> 0.57 of the HBM peak, Rastrigin 0.46 -> 0.59; at n = 64 / 128 and for the cheap objectives the
+    // compile-time forms stay ahead (Rosenbrock 0.75-0.78 against 0.48-0.63): profiles/r5_eval_r8_rt.txt
+    if (fix && n == 256 && !light && r8_rt_ok) return EvalForm::R8Rt;
+    // plain evaluation of many one-batch rows: eight lanes per row, eight rows per wavefront -- whole wavefront loads of
+    // 16-byte aligned rows, from the population size at which the chip is full either way (below it the one-visit kernel's
+    // 16 rows per workgroup spread a small population wider).  (Sphere -- one multiplication per element, no second stream
+    // -- is the one objective the one-visit kernel streams faster: 0.81 / 0.84 against 0.78 / 0.77 of the HBM peak at
+    // n = 64 / 256, profiles/r5_eval_r8_ab.txt)
+    if (fix && fun_id != SX_FUN_SPHERE && !has_xm && !has_part && ldx_even && x_aligned16 && P % 32 == 0 &&
+        P >= kR8MinRowsRival)
+        return EvalForm::R8Fixed;
+    // many one-batch rows of a length off the compile-time grid: eight lanes per row, straight from memory
+    if (!fix && r8_rt_ok && nleaf <= 3) return EvalForm::R8Rt;
+    if (fix) return EvalForm::ChainFixed;
+    return (whole && n % (8 * lpr) == 0) ? EvalForm::GeneralFull : EvalForm::General;
 }
 
-#ifndef SX_EVAL_HEAVY_STATIC
-#define SX_EVAL_HEAVY_STATIC 1  // (0: objectives with a cosine per term keep the run-time plan on long rows)
-#endif
-static int device_cus() {
-    static const int cus = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return cus;
-}
-// eight lanes per row: plain evaluations of whole wavefront loads of 16-byte aligned one-batch rows, from the population size at
-// which the chip is full either way (below it the one-visit kernel's 16 rows per workgroup spread a small population wider)
-static bool eval_r8_ok(const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *part_f) {
-    static const int mode = getenv("SX_EVAL_R8") ? atoi(getenv("SX_EVAL_R8")) : 1;
-    static const int64_t min_rows = getenv("SX_EVAL_R8_MIN") ? atoll(getenv("SX_EVAL_R8_MIN")) : 32768;
-    return mode != 0 && (n == 64 || n == 128 || n == 256) && xm == nullptr && part_f == nullptr && (ldx & 1) == 0 &&
-           ((uintptr_t)X & 15) == 0 && P % 32 == 0 && P >= min_rows;
-}
 template <int FUN>
-static int launch_eval(const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd, double *f,
-                       const PlanArg &plan, double *part_f, int64_t *part_i, hipStream_t s, int clip = 0,
+static int launch_eval(EvalForm form, const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd,
+                       double *f, const PlanArg &plan, double *part_f, int64_t *part_i, hipStream_t s, int clip = 0,
                        const double *pen_v = nullptr, double *pen_out = nullptr) {
     const Geometry g = row_geometry(P, n, kWideFrom);
-    // whole batches and whole workgroups: the guard-free form; one batch per row on top: the compile-time plan
-    // (plain evaluation only -- the clip / penalty variants keep the general kernel, to keep the build small)
-    const int lpr = lanes_per_row(n);
-    const bool full = clip == 0 && n % (8 * lpr) == 0 && P % rows_per_block(n) == 0;
-    // (the compile-time row lengths -- one-batch rows, n = 512 / 1024 / 2048 -- for the four hot objectives only: hot_objective)
-    constexpr bool kHot = FUN == SX_FUN_ACKLEY || FUN == SX_FUN_RASTRIGIN || FUN == SX_FUN_ROSENBROCK || FUN == SX_FUN_SPHERE;
-    const bool fix = kHot && clip == 0 && n == 4 * lpr && P % rows_per_block(n) == 0;
-    size_t lds = (size_t)rows_per_block(n) * gen_row_stride(n) * sizeof(double);  // (n + 8 doubles per row up to 256 elements)
-    // (objectives with a cosine per term keep the run-time plan: eight inlined cosines side by side need more registers than
-    //  a wavefront slot has, and their arithmetic, not the plan, is their time)
-    constexpr bool kLight = light_objective<FUN>();
+    const size_t lds = (size_t)rows_per_block(n) * gen_row_stride(n) * sizeof(double);  // (n + 8 doubles per row up to 256 elements)
+    constexpr bool kHot = hot_objective(FUN);  // (the compile-time forms exist for these only)
+    const dim3 blocks8((unsigned)((P + 31) / 32));  // eight lanes per row: 32 rows per workgroup of 256 threads
 #define SX_EVAL_GO(...)                                                                                              \
     hipLaunchKernelGGL((eval_kernel<FUN, __VA_ARGS__>), dim3(g.blocks), dim3(g.threads), lds, s, X, P, n, ldx, xm, xstd, f, \
                        plan, part_f, part_i, clip, pen_v, pen_out)
-    const bool grid_long = kHot && clip == 0 && (n == 512 || n == 1024 || n == 2048) && P % rows_per_block(n) == 0;
-    if (eval_r8_long_ok(P, n, xm, part_f, clip, plan.nleaf, kLight) && (eval_r8_long_mode() == 2 || !(kLight && grid_long))) {
-        // many long rows: eight lanes per row, straight from memory.  Not the cheap objectives at n = 512 / 1024 / 2048: their
-        // compile-time plan below stays ahead (Rosenbrock 0.61 / 0.76 / 0.66 of the HBM peak against 0.58 / 0.54 / 0.55);
-        // the cosine objectives gain there too (Ackley 0.30 / 0.47 / 0.35 -> 0.49 / 0.50 / 0.48): profiles/r5_eval_r8_rt.txt
-        hipLaunchKernelGGL((eval_r8_long_kernel<FUN>), dim3((unsigned)((P + 31) / 32)), dim3(256),
-                           (size_t)32 * 2 * plan.nleaf * sizeof(double), s, X, P, n, ldx, f, plan);
-    } else if ((kLight || SX_EVAL_HEAVY_STATIC) && grid_long) {
-        // long rows of a compile-time length: numpy's plan as constants (row_reduce_long).  Rosenbrock n = 1024: 0.54 -> 0.84
-        // of the HBM peak, n = 512: 0.44 -> 0.76, n = 2048: 0.43 -> 0.70 (profiles/r4_eval_long_rows.txt; a resident,
-        // software-pipelined form of the same kernel stayed at 0.72 and was dropped)
-        if constexpr (kHot) {
-            switch (n) {
-                case 512: SX_EVAL_GO(64, true, 512); break;
-                case 1024: SX_EVAL_GO(64, true, 1024); break;
-                default: SX_EVAL_GO(64, true, 2048); break;
+    switch (form) {
+        case EvalForm::R8Long:
+            hipLaunchKernelGGL((eval_r8_long_kernel<FUN>), blocks8, dim3(256), (size_t)32 * 2 * plan.nleaf * sizeof(double), s,
+                               X, P, n, ldx, f, plan);
+            break;
+        case EvalForm::LongPlan:
+            if constexpr (kHot) {
+                switch (n) {
+                    case 512: SX_EVAL_GO(64, true, 512); break;
+                    case 1024: SX_EVAL_GO(64, true, 1024); break;
+                    default: SX_EVAL_GO(64, true, 2048); break;
+                }
             }
-        }
-    } else if (fix && (eval_r8_rt_mode() == 2 || (n == 256 && !kLight)) && eval_r8_rt_ok(P, n, xm, part_f, clip)) {
-        // rows of 256 elements with a cosine per term: the run-time form (no staging, 16 terms at a time) is the faster one --
-        // Ackley 0.45 -> 0.57 of the HBM peak, Rastrigin 0.46 -> 0.59; at n = 64 / 128 and for the cheap objectives the
-        // compile-time form below stays ahead (Rosenbrock 0.75-0.78 against 0.48-0.63): profiles/r5_eval_r8_rt.txt
-        hipLaunchKernelGGL((eval_r8_rt_kernel<FUN>), dim3((unsigned)((P + 31) / 32)), dim3(256), 0, s, X, P, n, ldx, f, plan);
-    } else if (fix && FUN != SX_FUN_SPHERE && eval_r8_ok(X, P, n, ldx, xm, part_f)) {
-        // (Sphere -- one multiplication per element, no second stream -- is the one objective the one-visit kernel streams
-        //  faster: 0.81 / 0.84 against 0.78 / 0.77 of the HBM peak at n = 64 / 256, profiles/r5_eval_r8_ab.txt)
-        // plain evaluation of many one-batch rows: eight lanes per row, eight rows per wavefront
-        const unsigned blocks8 = (unsigned)(P / 32);
-        if constexpr (kHot) {
-            switch (n) {
-                case 64: hipLaunchKernelGGL((eval_r8_kernel<FUN, 64>), dim3(blocks8), dim3(256), 32 * (64 + 8) * sizeof(double), s, X, ldx, f); break;
-                case 128: hipLaunchKernelGGL((eval_r8_kernel<FUN, 128>), dim3(blocks8), dim3(256), 32 * (128 + 8) * sizeof(double), s, X, ldx, f); break;
-                default: hipLaunchKernelGGL((eval_r8_kernel<FUN, 256>), dim3(blocks8), dim3(256), 32 * (256 + 8) * sizeof(double), s, X, ldx, f); break;
+            break;
+        case EvalForm::R8Rt:
+            hipLaunchKernelGGL((eval_r8_rt_kernel<FUN>), blocks8, dim3(256), 0, s, X, P, n, ldx, f, plan);
+            break;
+        case EvalForm::R8Fixed:
+            if constexpr (kHot) {
+                switch (n) {
+                    case 64: hipLaunchKernelGGL((eval_r8_kernel<FUN, 64>), blocks8, dim3(256), 32 * (64 + 8) * sizeof(double), s, X, ldx, f); break;
+                    case 128: hipLaunchKernelGGL((eval_r8_kernel<FUN, 128>), blocks8, dim3(256), 32 * (128 + 8) * sizeof(double), s, X, ldx, f); break;
+                    default: hipLaunchKernelGGL((eval_r8_kernel<FUN, 256>), blocks8, dim3(256), 32 * (256 + 8) * sizeof(double), s, X, ldx, f); break;
+                }
             }
-        }
-    } else if (!fix && eval_r8_rt_ok(P, n, xm, part_f, clip) && plan.nleaf <= 3) {
-        // many one-batch rows of a length off the compile-time grid: eight lanes per row, straight from memory
-        hipLaunchKernelGGL((eval_r8_rt_kernel<FUN>), dim3((unsigned)((P + 31) / 32)), dim3(256), 0, s, X, P, n, ldx, f, plan);
-    } else if (fix) {
-        // the register-chain objective reads the staged vector only: n + 8 doubles per row, not the term arrays' 3n + ...
-        if constexpr (kHot) {
-            switch (lpr) {
-                case 16: SX_EVAL_GO(16, true, 64); break;
-                case 32: SX_EVAL_GO(32, true, 128); break;
-                default: SX_EVAL_GO(64, true, 256); break;
+            break;
+        case EvalForm::ChainFixed:
+            if constexpr (kHot) {
+                switch (lanes_per_row(n)) {
+                    case 16: SX_EVAL_GO(16, true, 64); break;
+                    case 32: SX_EVAL_GO(32, true, 128); break;
+                    default: SX_EVAL_GO(64, true, 256); break;
+                }
             }
-        }
-    } else if (full) {
-        SX_DISPATCH_LPR(n, SX_EVAL_GO(LPR, true, 0))
-    } else {
-        SX_DISPATCH_LPR(n, SX_EVAL_GO(LPR, false, 0))
+            break;
+        case EvalForm::GeneralFull: SX_DISPATCH_LPR(n, SX_EVAL_GO(LPR, true, 0)) break;
+        case EvalForm::General: SX_DISPATCH_LPR(n, SX_EVAL_GO(LPR, false, 0)) break;
+        case EvalForm::Wide: set_error("internal: launch_eval was asked for a row the wide kernels serve"); return -1;
     }
 #undef SX_EVAL_GO
     SX_LAUNCH_CHECK();
@@ -662,23 +656,18 @@ extern "C" int sx_eval(int fun_id, const double *X, int64_t P, int n, int64_t ld
     SX_REQUIRE((xm == nullptr) == (xstd == nullptr), "sx_eval: xm and xstd must be given together");
     SX_REQUIRE((part_f == nullptr) == (part_i == nullptr), "sx_eval: part_f and part_i must be given together");
     hipStream_t s = (hipStream_t)stream;
-    // Large populations of rows of 2049 ... 4096 elements: the eight-lanes-per-row kernel (launch_eval) instead of one workgroup
-    // per row -- Rosenbrock n = 2049 / 3000 0.45 / 0.49 -> 0.56 / 0.54 of the HBM peak, Ackley n = 2049 / 4096 0.28 / 0.43 ->
-    // 0.50 / 0.48; the cheap objectives from ~3600 elements on stay with the workgroup per row (n = 4096: 0.59-0.74 against
-    // 0.56-0.63: rows a power of two apart meet in the same memory channels).  profiles/r5_eval_r8_rt.txt, part 4.
-    const bool cheap = fun_id == SX_FUN_ROSENBROCK || fun_id == SX_FUN_SPHERE || fun_id == SX_FUN_QUARTIC ||
-                       fun_id == SX_FUN_STYBLINSKI_TANG;  // (light_objective<FUN>())
-    const bool long_rows = n <= kMaxDim && eval_r8_long_ok(P, n, xm, part_f, 0, 1, cheap) &&
-                           (eval_r8_long_mode() == 2 || !cheap || n <= 3584);
-    if (is_wide(n, kWideFrom) && !long_rows) return wide_eval(fun_id, X, P, n, ldx, xm, xstd, f, part_f, part_i, 0, nullptr, nullptr, s);
+    PlanArg plan;
+    plan.nleaf = 0;  // (rows beyond kMaxDim have no kernel-argument plan: always the workgroup per row)
+    if (n <= kMaxDim && make_plan_arg(fun_id, n, &plan)) return -1;
+    const EvalForm form = eval_form(fun_id, P, n, (ldx & 1) == 0, ((uintptr_t)X & 15) == 0, xm != nullptr, part_f != nullptr,
+                                    0, plan.nleaf);
+    if (form == EvalForm::Wide) return wide_eval(fun_id, X, P, n, ldx, xm, xstd, f, part_f, part_i, 0, nullptr, nullptr, s);
     if (is_wide(n, kWideFrom) && n <= kWideMaxDim)
         if (int rc = wide_warm_plan(fun_id, n, s)) return rc;  // (the generations that follow are wide launches)
-    PlanArg plan;
-    if (make_plan_arg(fun_id, n, &plan)) return -1;
     switch (fun_id) {
 #define SX_CASE(ID) \
     case ID:        \
-        return launch_eval<ID>(X, P, n, ldx, xm, xstd, f, plan, part_f, part_i, s);
+        return launch_eval<ID>(form, X, P, n, ldx, xm, xstd, f, plan, part_f, part_i, s);
         SX_CASE(SX_FUN_ACKLEY)
         SX_CASE(SX_FUN_GRIEWANK)
         SX_CASE(SX_FUN_QUARTIC)
@@ -704,10 +693,11 @@ extern "C" int sx_cmaes_eval_penalized(int fun_id, const double *X, int64_t P, i
     if (is_wide(n, kWideFrom)) return wide_eval(fun_id, X, P, n, n, xm, xstd, f_raw, nullptr, nullptr, 1, v, pen, s);
     PlanArg plan;
     if (make_plan_arg(fun_id, n, &plan)) return -1;
+    const EvalForm form = eval_form(fun_id, P, n, (n & 1) == 0, ((uintptr_t)X & 15) == 0, true, false, 1, plan.nleaf);
     switch (fun_id) {
 #define SX_CASE(ID) \
     case ID:        \
-        return launch_eval<ID>(X, P, n, n, xm, xstd, f_raw, plan, nullptr, nullptr, s, 1, v, pen);
+        return launch_eval<ID>(form, X, P, n, n, xm, xstd, f_raw, plan, nullptr, nullptr, s, 1, v, pen);
         SX_CASE(SX_FUN_ACKLEY)
         SX_CASE(SX_FUN_GRIEWANK)
         SX_CASE(SX_FUN_QUARTIC)

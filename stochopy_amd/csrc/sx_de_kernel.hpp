@@ -198,7 +198,7 @@ constexpr int kStep = 4;  // row steps per batch: one Philox call, and all its l
 // FULL: n is a whole number of batches (n % (kStep*LPR) == 0) and P a whole number of workgroups, so
 // every bounds test folds away (the P = 4096, n = 128 headline shape).
 // NFIX: FULL with n == kStep * LPR exactly (64, 128 -- the headline shape -- or 256): the row length, and with it numpy's
-// summation plan, is a compile-time constant (row_reduce_fixed / row_reduce_static in sx_device.hpp); 0 otherwise.
+// summation plan, is a compile-time constant (row_objective_chain in sx_rowops.hpp); 0 otherwise.
 // STRAT: with NFIX and constraints=None, the strategy as a compile-time constant too (its donor count, the best-row
 // fetch and the mutant's formula are otherwise uniform branches inside the row's dependent chain: 9.03 -> 8.52 us per
 // generation at the headline shape), and no repair code; -1 = strategy and constraints read from the arguments.
@@ -597,7 +597,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
     }
 
     SX_TP(2);
-    const double fc = row_objective<FUN, LPR, FULL, NFIX, SX_LONG_STATIC, ONEB>(U, n, plan, l);
+    const double fc = row_objective<FUN, LPR, NFIX, 1, ONEB>(U, n, plan, l);
     SX_TP(3);
     const bool better = fc < fold;  // _common.py:127 strict <
     if (FULL || id.active) {

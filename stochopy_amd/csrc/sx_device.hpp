@@ -4,11 +4,11 @@
 // wavefront (lanes_per_row(n): 16 up to n = 64, 32 up to 128, else the whole wave), so a
 // wave carries 4, 2 or 1 rows.  Lane l of a row holds elements e = LPR*q + l: every row
 // access is a coalesced run of >= 128 bytes, and the fixed per-wave work (state, donors,
-// Philox calls, reduction control) is shared by up to 4 rows.  The trial vector U and the
-// per-element objective terms are staged in LDS; the row sum is then taken from LDS in
+// Philox calls, reduction control) is shared by up to 4 rows.  The trial vector U is staged
+// in LDS; the objective terms are formed from it inside the row sum, which is taken in
 // numpy's pairwise add.reduce order (8 running accumulators over blocks of 8, combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), recursion above 128 terms): lane
-// l&7 of the row walks chain l&7, the 8-lane tree is three DPP steps.  Fitness values
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), recursion above 128 terms): in the
+// long rows' form lane l&7 of the row walks chain l&7, the 8-lane tree is three DPP steps.  Fitness values
 // therefore reproduce the reference's `.sum()` bit for bit for +,-,* objectives.  The leaf
 // table of the recursion travels in the kernel arguments (scalar loads, uniform control flow).
 #pragma once
@@ -47,20 +47,18 @@ inline int run_wide_from(int wide_from) {
 }
 
 // Rows of more than 256 elements form their objective terms inside the reduction (row_reduce_leaves_fused:
-// one leaf of <= 128 terms per 8-lane group, so >= 3 of the 8 groups are busy); shorter rows have too few
-// leaves for that and stage the terms, computed by all lanes, in LDS first.
-#ifndef SX_FUSED_ABOVE
-#define SX_FUSED_ABOVE 256  // (a build-time knob for A/B measurements: tools/ab_fused.sh)
-#endif
-__host__ __device__ inline bool fused_terms(int n) { return n > SX_FUSED_ABOVE; }
-// doubles of LDS per row.  staged: U[n+8] | A[n] | B[n] | stack[24] | leaf sums [2][n/64+2];
-// fused: U[n+8] | leaf sums [2][n/64+2]
+// one leaf of <= 128 terms per 8-lane group, so >= 3 of the 8 groups are busy); shorter rows are register
+// chains over the staged vector (row_objective_chain / row_objective_chain_rt, sx_rowops.hpp).
+// Doubles of LDS per row above 256 elements: U[n+8] | leaf sums [2][n/64+2].  Up to 256 elements no objective
+// reads anything behind U[n+8]: 3n + 32 + 2 leaf_cap there is a SIZING CONSTANT of the immediate-sweep and
+// generic geometries (row_geometry: workgroup shapes, LDS sizes and with them the record counts), not a layout.
+// (Shrinking it would change occupancy, i.e. speed; tests/test_host_cpu.py pins the numbers that follow from it.)
 __host__ __device__ inline int leaf_cap(int n) { return n / 64 + 2; }
 __host__ __device__ inline int lds_row_stride(int n) {
-    return fused_terms(n) ? n + 8 + 2 * leaf_cap(n) : 3 * n + 8 + 24 + 2 * leaf_cap(n);
+    return n > 256 ? n + 8 + 2 * leaf_cap(n) : 3 * n + 8 + 24 + 2 * leaf_cap(n);
 }
 // the DE / PSO generation kernels' and the objective kernel's rows: up to 256 elements the objective is a register chain over the staged vector alone
-// (row_objective_chain / row_objective_chain_rt), so a row needs n + 8 doubles instead of the term arrays' 3n + ... -- at the
+// (row_objective_chain / row_objective_chain_rt), so a row needs n + 8 doubles instead of lds_row_stride's 3n + ... -- at the
 // metric's row length 17 KB per workgroup instead of 54 KB, which with <= 80 VGPRs is three resident workgroups per CU
 // instead of two (round 5: what bounds that kernel at large P is latency, profiles/r5_de_gather_probe.txt)
 __host__ __device__ inline int gen_row_stride(int n) { return n <= 256 ? n + 8 : lds_row_stride(n); }
@@ -291,8 +289,13 @@ struct Obj;
 // compile time, one-batch rows, PLAIN PSO, compile-time row length of the ordered sweeps -- exist for the four objectives the
 // BASELINE configs and the reference's tests use; Griewank, Quartic and Styblinski-Tang take the general form of the same kernel
 // (same arithmetic, same results).  Of the DE strategies only best1bin and rand1bin are specialised.
-inline bool hot_objective(int fun_id) {
+constexpr bool hot_objective(int fun_id) {
     return fun_id == SX_FUN_ACKLEY || fun_id == SX_FUN_RASTRIGIN || fun_id == SX_FUN_ROSENBROCK || fun_id == SX_FUN_SPHERE;
+}
+// objectives whose terms are a few multiplications (no cosine); light_objective<FUN>() in sx_rowops.hpp is this at compile time
+constexpr bool light_objective(int fun_id) {
+    return fun_id == SX_FUN_ROSENBROCK || fun_id == SX_FUN_SPHERE || fun_id == SX_FUN_QUARTIC ||
+           fun_id == SX_FUN_STYBLINSKI_TANG;
 }
 
 template <>
@@ -465,95 +468,9 @@ struct Grad<SX_FUN_STYBLINSKI_TANG> {
 };
 
 // ---------------------------------------------------------------------------
-// Row sum in numpy order from LDS-staged terms.  Executed by all 64 lanes: the 8
-// lane groups compute the same sum redundantly (LDS broadcasts), so every lane
-// ends with identical bits and no cross-lane broadcast is needed.
+// Row sum in numpy order, the objective terms formed from the LDS-staged vector on the way.
 // ---------------------------------------------------------------------------
 constexpr int kLeafBlocks = 16;  // a leaf of numpy's recursion has at most 128 terms
-constexpr int kStack = 12;       // leaf sums awaiting their sibling; depth <= log2(m/64)+1
-
-// Two value streams at once (A: sum, B: sum or product) so their dependent chains
-// interleave; LDS reads are issued 8 blocks ahead of the adds.  S: 2*kStack doubles of
-// LDS scratch per wave for the stack of leaf sums (only touched when the row has > 1 leaf).
-template <bool TWO, bool BMUL>
-__device__ __forceinline__ void row_reduce2(const double *A, const double *B, double *S, const PlanArg &p, int lane,
-                                            double &sa, double &sb) {
-    const int j = lane & (kGroup - 1);
-    const double identB = BMUL ? 1.0 : 0.0;
-    // tail terms (after the last leaf's tree; the whole row when m < 8), fetched up front
-    double ta[kGroup - 1], tb[kGroup - 1];
-    const int t0 = p.mb * kGroup;
-#pragma unroll
-    for (int k = 0; k < kGroup - 1; ++k) {
-        ta[k] = (k < p.tail) ? A[t0 + k] : 0.0;
-        tb[k] = (TWO && k < p.tail) ? B[t0 + k] : identB;
-    }
-    int sp = 0;
-    double curA = 0.0, curB = identB;
-    int b0 = 0;
-    for (int leaf = 0; leaf < p.nleaf; ++leaf) {
-        const int b1 = (int)p.end[leaf];
-        const int cnt = b1 - b0;
-        double chA = 0.0, chB = identB;
-#pragma unroll
-        for (int h = 0; h < kLeafBlocks; h += 8) {
-            double va[8], vb[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const bool in = h + t < cnt;
-                va[t] = in ? A[(b0 + h + t) * kGroup + j] : 0.0;
-                vb[t] = (TWO && in) ? B[(b0 + h + t) * kGroup + j] : identB;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                if (h + t == 0) {
-                    chA = va[0];
-                    chB = vb[0];
-                } else if (h + t < cnt) {  // uniform
-                    chA = chA + va[t];
-                    if (TWO) chB = combine<BMUL>(chB, vb[t]);
-                }
-            }
-        }
-        curA = group_tree<false>(chA);
-        if (TWO) curB = group_tree<BMUL>(chB);
-        if (leaf == p.nleaf - 1) {
-#pragma unroll
-            for (int k = 0; k < kGroup - 1; ++k) {
-                if (k < p.tail) {
-                    curA = curA + ta[k];
-                    if (TWO) curB = combine<BMUL>(curB, tb[k]);
-                }
-            }
-        }
-        if (p.nleaf > 1) {  // push, then merge with finished siblings; every lane stores the same bits
-            S[sp] = curA;
-            if (TWO) S[kStack + sp] = curB;
-            ++sp;
-            for (int merges = (int)p.merges[leaf]; merges > 0; --merges) {
-                S[sp - 2] = S[sp - 2] + S[sp - 1];
-                if (TWO) S[kStack + sp - 2] = combine<BMUL>(S[kStack + sp - 2], S[kStack + sp - 1]);
-                --sp;
-            }
-        }
-        b0 = b1;
-    }
-    if (p.nleaf == 0) {  // m < 8: plain left-to-right
-#pragma unroll
-        for (int k = 0; k < kGroup - 1; ++k) {
-            if (k < p.tail) {
-                curA = curA + ta[k];
-                if (TWO) curB = combine<BMUL>(curB, tb[k]);
-            }
-        }
-    }
-    if (p.nleaf > 1) {
-        curA = S[0];
-        if (TWO) curB = S[kStack];
-    }
-    sa = 0.0 + curA;  // add.reduce starts from the identity
-    sb = (TWO && !BMUL) ? 0.0 + curB : curB;
-}
 
 // value held by lane `idx` of this lane's row (idx uniform).  A whole-wave row can use v_readlane.
 template <int LPR>
@@ -562,209 +479,23 @@ __device__ __forceinline__ double row_lane_value(double v, int idx, int l) {
     return __shfl(v, (int)(threadIdx.x & 63) - l + idx, kWave);
 }
 
-// Rows of exactly M = 64, 128 or 256 terms (the PSO kernel's whole-batch rows with an objective that has one term per
-// element): numpy's plan is known when the kernel is compiled -- one leaf of M/8 blocks, or two leaves of 16 -- so
-// the chain, the tree and the leaf sum are straight-line code instead of loops over the plan arrays (scalar loads,
-// selects and bound checks per step).  Same additions in the same order as row_reduce2 / row_reduce_leaves: same bits.
-template <bool TWO, bool BMUL, int LPR, int M>
-__device__ __forceinline__ void row_reduce_fixed(const double *A, const double *B, int l, double &sa, double &sb) {
-    static_assert(M == 64 || M == 128 || M == 256, "one or two full leaves");
-    constexpr int NLEAF = M > 128 ? 2 : 1;
-    constexpr int BLK = M / NLEAF / kGroup;  // blocks per leaf: 8 or 16
-    const int j = l & (kGroup - 1), grp = l >> 3;
-    const int leaf = (NLEAF == 2 && grp == 1) ? 1 : 0;  // the other lane groups repeat leaf 0 (LDS broadcasts)
-    const double identB = BMUL ? 1.0 : 0.0;
-    const double *a = A + leaf * (BLK * kGroup) + j, *b = B + leaf * (BLK * kGroup) + j;
-    double chA = 0.0, chB = identB;
-#pragma unroll
-    for (int h = 0; h < BLK; h += 8) {
-        double va[8], vb[8];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            va[t] = a[(h + t) * kGroup];
-            vb[t] = TWO ? b[(h + t) * kGroup] : identB;
-        }
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            if (h + t == 0) {
-                chA = va[0];
-                chB = vb[0];
-            } else {
-                chA = chA + va[t];
-                if (TWO) chB = combine<BMUL>(chB, vb[t]);
-            }
-        }
-    }
-    double curA = group_tree<false>(chA);
-    double curB = TWO ? group_tree<BMUL>(chB) : identB;
-    if (NLEAF == 2) {  // leaf 0 lives in lane group 0, leaf 1 in group 1
-        curA = row_lane_value<LPR>(curA, 0, l) + row_lane_value<LPR>(curA, kGroup, l);
-        if (TWO) curB = combine<BMUL>(row_lane_value<LPR>(curB, 0, l), row_lane_value<LPR>(curB, kGroup, l));
-    }
-    sa = 0.0 + curA;  // add.reduce starts from the identity
-    sb = (TWO && !BMUL) ? 0.0 + curB : curB;
-}
-
-// Any compile-time number of terms M >= 8 (whole-batch rows of an objective with n - 1 terms: 63, 127, 255): numpy's
-// recursion (loops_utils.h.src pairwise sum: up to 128 terms = eight accumulators over the 8-blocks, the tree, then the
-// tail; above, split at n/2 rounded down to a multiple of 8) unrolled by the compiler.  Every 8-lane group walks the
-// same chain (LDS broadcasts), the leaves one after the other: a few more chain steps than the leaves-in-parallel form,
-// none of its bookkeeping.  Same additions in the same order: same bits.
-template <bool TWO, bool BMUL, int OFF, int M>
-__device__ __forceinline__ void pairwise_static(const double *A, const double *B, int j, double &ra, double &rb) {
-    static_assert(M >= 8, "shorter sums are plain loops");
-    if constexpr (M <= 128) {
-        constexpr int BLK = M / kGroup, TAIL = M % kGroup;
-        double chA = A[OFF + j], chB = TWO ? B[OFF + j] : (BMUL ? 1.0 : 0.0);
-#pragma unroll
-        for (int h0 = 1; h0 < BLK; h0 += 8) {  // reads run up to 8 blocks ahead of the adds
-            double va[8], vb[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                va[t] = h0 + t < BLK ? A[OFF + (h0 + t) * kGroup + j] : 0.0;
-                vb[t] = (TWO && h0 + t < BLK) ? B[OFF + (h0 + t) * kGroup + j] : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                if (h0 + t < BLK) {
-                    chA = chA + va[t];
-                    if (TWO) chB = combine<BMUL>(chB, vb[t]);
-                }
-            }
-        }
-        double ta[TAIL > 0 ? TAIL : 1], tb[TAIL > 0 ? TAIL : 1];
-#pragma unroll
-        for (int k = 0; k < TAIL; ++k) {
-            ta[k] = A[OFF + BLK * kGroup + k];
-            tb[k] = TWO ? B[OFF + BLK * kGroup + k] : 0.0;
-        }
-        ra = group_tree<false>(chA);
-        rb = TWO ? group_tree<BMUL>(chB) : chB;
-#pragma unroll
-        for (int k = 0; k < TAIL; ++k) {
-            ra = ra + ta[k];
-            if (TWO) rb = combine<BMUL>(rb, tb[k]);
-        }
-    } else {
-        constexpr int N2 = (M / 2) - ((M / 2) % kGroup);
-        double la, lb, qa, qb;
-        pairwise_static<TWO, BMUL, OFF, N2>(A, B, j, la, lb);
-        pairwise_static<TWO, BMUL, OFF + N2, M - N2>(A, B, j, qa, qb);
-        ra = la + qa;
-        rb = TWO ? combine<BMUL>(lb, qb) : lb;
-    }
-}
-
-template <bool TWO, bool BMUL, int M>
-__device__ __forceinline__ void row_reduce_static(const double *A, const double *B, int l, double &sa, double &sb) {
-    double ra, rb;
-    pairwise_static<TWO, BMUL, 0, M>(A, B, l & (kGroup - 1), ra, rb);
-    sa = 0.0 + ra;  // add.reduce starts from the identity
-    sb = !TWO ? (BMUL ? 1.0 : 0.0) : (BMUL ? rb : 0.0 + rb);
-}
-
-// Rows with several leaves (n > 128): the leaves of numpy's recursion are independent, so the LPR/8
-// 8-lane groups of the row take one leaf each (chain + tree [+ tail]); the leaf sums meet in LDS and are
-// then merged in recursion order.  L: 2*leaf_cap doubles of LDS scratch (leaf sums), S: the merge stack.
-template <bool TWO, bool BMUL, int LPR>
-__device__ __forceinline__ void row_reduce_leaves(const double *A, const double *B, double *S, double *L, int lcap,
-                                                  const PlanArg &p, int l, double &sa, double &sb) {
-    constexpr int NG = LPR / kGroup;
-    const int j = l & (kGroup - 1), grp = l >> 3;
-    const double identB = BMUL ? 1.0 : 0.0;
-    const int t0 = p.mb * kGroup;
-    for (int leaf0 = 0; leaf0 < p.nleaf; leaf0 += NG) {
-        // this group's leaf: block range via uniform (scalar) plan reads + selects
-        int b0 = 0, b1 = 0;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int lf = leaf0 + g;
-            const int e1 = lf < p.nleaf ? (int)p.end[lf] : 0;
-            const int e0 = (lf > 0 && lf <= p.nleaf) ? (int)p.end[lf - 1] : 0;
-            if (grp == g) {
-                b0 = e0;
-                b1 = e1;
-            }
-        }
-        const int leaf = leaf0 + grp;
-        const int cnt = b1 - b0;  // 0 for groups beyond the last leaf
-        double chA = 0.0, chB = identB;
-#pragma unroll
-        for (int h = 0; h < kLeafBlocks; h += 8) {
-            double va[8], vb[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const bool in = h + t < cnt;
-                va[t] = in ? A[(b0 + h + t) * kGroup + j] : 0.0;
-                vb[t] = (TWO && in) ? B[(b0 + h + t) * kGroup + j] : identB;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                if (h + t == 0) {
-                    chA = va[0];
-                    chB = vb[0];
-                } else if (h + t < cnt) {
-                    chA = chA + va[t];
-                    if (TWO) chB = combine<BMUL>(chB, vb[t]);
-                }
-            }
-        }
-        double curA = group_tree<false>(chA);
-        double curB = TWO ? group_tree<BMUL>(chB) : identB;
-        if (leaf == p.nleaf - 1) {
-            for (int k = 0; k < p.tail; ++k) {
-                curA = curA + A[t0 + k];
-                if (TWO) curB = combine<BMUL>(curB, B[t0 + k]);
-            }
-        }
-        if (cnt > 0 && j == 0) {
-            L[leaf] = curA;
-            if (TWO) L[lcap + leaf] = curB;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // merge in recursion order: leaf t's sums sit in lane t; the host-built program (pair[m] = left, right
-    // slot) is replayed with one readlane + one add per merge -- no LDS round trips.  Result in slot 0.
-    double vA = l < p.nleaf ? L[l] : 0.0;
-    double vB = (TWO && l < p.nleaf) ? L[lcap + l] : identB;
-    for (int m = 0; m + 1 < p.nleaf; ++m) {
-        const int left = (int)p.mleft[m], right = (int)p.mright[m];  // uniform (scalar loads)
-        const double rA = row_lane_value<LPR>(vA, right, l);
-        const double rB = TWO ? row_lane_value<LPR>(vB, right, l) : identB;
-        if (l == left) {
-            vA = vA + rA;
-            if (TWO) vB = combine<BMUL>(vB, rB);
-        }
-    }
-    sa = 0.0 + row_lane_value<LPR>(vA, 0, l);
-    const double rb = TWO ? row_lane_value<LPR>(vB, 0, l) : identB;
-    sb = (TWO && !BMUL) ? 0.0 + rb : rb;
-}
-
-// The same for whole-wave rows (n > 128), with the objective terms computed on the way: the chain lane that
-// adds term e reads U[e] (and U[e+1]) from LDS and forms the term itself -- every lane still handles m/64
-// terms, but no term array is written or staged, so a row needs n+8 doubles of LDS instead of 3n+8 (3x the
-// rows per CU at n = 1024).  Same operations on the same values: same bits as the staged form.
+// Whole-wave rows with several leaves (n > 256): the leaves of numpy's recursion are independent, so the eight 8-lane
+// groups of the row take one leaf each (chain + tree [+ tail]); the chain lane that adds term e reads U[e] (and U[e+1])
+// from LDS and forms the term itself, so no term array is staged and a row needs n+8 doubles of LDS plus its leaf sums.
+// The leaf sums meet in LDS (L: 2*lcap doubles) and are then merged in recursion order: leaf t's sums sit in lane t, the
+// host-built program (mleft / mright) is replayed with one readlane + one add per merge.  Same additions in numpy's order.
 // PAIRED: some slot of the plan holds two leaves (PlanArg::nslot < nleaf -- only when that saves a pass); otherwise slot s
 // is leaf s and nothing of the pairing survives in the code.
-#ifndef SX_FUSED_SELECT
-#define SX_FUSED_SELECT 0  // A/B switch (round 5): 1 = a select per term instead of a branch per term in the chains (what the
-                           // wide kernels do, sx_wide.hip); here measured neutral (DE Rosenbrock n=300 43.8 -> 44.6 us,
-                           // n=1500 75.2 -> 74.4: profiles/r5_narrow_ab.txt, which has both switches on): off
-#endif
 #ifndef SX_FUSED_TAIL_BY_LANE
 #define SX_FUSED_TAIL_BY_LANE 1  // A/B switch (round 5): 0 = every lane of the last leaf's group forms every tail term
                                  // (DE Rastrigin n=300 55.3 -> 52.3 us, n=700 44.7 -> 43.5: profiles/r5_narrow_ab.txt)
 #endif
 template <int FUN, int LPR, bool PAIRED>
-__device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, double *L, int lcap, int m, const PlanArg &p,
+__device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, double *L, int lcap, const PlanArg &p,
                                                              int l, double &sa, double &sb) {
     using O = Obj<FUN>;
     constexpr bool TWO = O::TWO, BMUL = O::BMUL;
     constexpr int NG = LPR / kGroup;
-    constexpr bool kSelectOnChain = SX_FUSED_SELECT && !O::TWO && FUN != SX_FUN_RASTRIGIN;  // one cheap term per element
     const int j = l & (kGroup - 1), grp = l >> 3;
     const double identB = BMUL ? 1.0 : 0.0;
     const int t0 = p.mb * kGroup;
@@ -785,30 +516,7 @@ __device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, do
         const int cntA = a1 - a0;  // 0 for groups beyond the last slot
         double chA = 0.0, chB = identB;
         // steps 0..7: the first (or only) leaf
-        if constexpr (kSelectOnChain) {
-            // cheap terms: the blocks a short leaf does not have are read all the same (inside the workgroup's LDS, or
-            // past it: zeros) and their terms dropped from the chain -- a select per term instead of a branch per term
-            double x[8], xn[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int e = (a0 + t) * kGroup + j;
-                x[t] = U[e];
-                xn[t] = O::NEXT ? U[e + 1] : 0.0;
-            }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const bool in = t < cntA;
-                double a, b;
-                O::term(x[t], xn[t], (a0 + t) * kGroup + j, a, b);
-                if (t == 0) {
-                    chA = in ? a : 0.0;
-                    chB = in ? b : identB;
-                } else {
-                    chA = in ? chA + a : chA;
-                    if (TWO) chB = in ? combine<BMUL>(chB, b) : chB;
-                }
-            }
-        } else {
+        {
             double x[8], xn[8];
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
@@ -842,28 +550,7 @@ __device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, do
         }
         // steps 8..15: the rest of the only leaf, or the second leaf of the pair from its first block
         const int base2 = two ? a1 - 8 : a0, lim2 = two ? 8 + (c1 - a1) : cntA;
-        if constexpr (kSelectOnChain) {
-            double x[8], xn[8];
-#pragma unroll
-            for (int t = 8; t < kLeafBlocks; ++t) {
-                const int e = (base2 + t) * kGroup + j;
-                x[t - 8] = U[e];
-                xn[t - 8] = O::NEXT ? U[e + 1] : 0.0;
-            }
-#pragma unroll
-            for (int t = 8; t < kLeafBlocks; ++t) {
-                const bool in = t < lim2;
-                double a, b;
-                O::term(x[t - 8], xn[t - 8], (base2 + t) * kGroup + j, a, b);
-                if (t == 8 && two) {
-                    chA = in ? a : chA;
-                    chB = in ? b : chB;
-                } else {
-                    chA = in ? chA + a : chA;
-                    if (TWO) chB = in ? combine<BMUL>(chB, b) : chB;
-                }
-            }
-        } else {
+        {
             double x[8], xn[8];
 #pragma unroll
             for (int t = 8; t < kLeafBlocks; ++t) {
@@ -920,7 +607,6 @@ __device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, do
             if (TWO) L[lcap + leaf] = curB;
         }
     }
-    (void)m;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -940,12 +626,12 @@ __device__ __forceinline__ void row_reduce_leaves_fused_impl(const double *U, do
     sb = (TWO && !BMUL) ? 0.0 + rb : rb;
 }
 template <int FUN, int LPR>
-__device__ __forceinline__ void row_reduce_leaves_fused(const double *U, double *L, int lcap, int m, const PlanArg &p,
-                                                        int l, double &sa, double &sb) {
+__device__ __forceinline__ void row_reduce_leaves_fused(const double *U, double *L, int lcap, const PlanArg &p, int l,
+                                                        double &sa, double &sb) {
     if (p.nslot != p.nleaf)  // (uniform)
-        row_reduce_leaves_fused_impl<FUN, LPR, true>(U, L, lcap, m, p, l, sa, sb);
+        row_reduce_leaves_fused_impl<FUN, LPR, true>(U, L, lcap, p, l, sa, sb);
     else
-        row_reduce_leaves_fused_impl<FUN, LPR, false>(U, L, lcap, m, p, l, sa, sb);
+        row_reduce_leaves_fused_impl<FUN, LPR, false>(U, L, lcap, p, l, sa, sb);
 }
 
 // ---------------------------------------------------------------------------

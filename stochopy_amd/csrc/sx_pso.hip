@@ -192,7 +192,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (FULL && !PLAIN && LPR ==
             }
         }
     }
-    const double fc = row_objective<FUN, LPR, FULL, FULL ? 4 * LPR : 0, SX_LONG_STATIC, ONEB>(U, n, plan, l);
+    const double fc = row_objective<FUN, LPR, FULL ? 4 * LPR : 0, 1, ONEB>(U, n, plan, l);
     const bool better = fc < fold;  // _common.py:127 strict <
     if (id.active) {
         if (better)

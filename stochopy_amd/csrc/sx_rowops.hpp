@@ -71,9 +71,8 @@ __device__ __forceinline__ double row_sum(double v) {
 // L = SEG*j + g of the row (SEG = LPR/8 lanes per accumulator) reads the four elements 8(4g+i)+j, i = 0..3, of the staged
 // vector, forms their terms in registers and adds them -- in order -- onto the running sum that arrives from lane L-1
 // (same quad: one DPP move): accumulator j's chain walks through SEG adjacent lanes and ends in lane SEG*j + SEG-1.
-// Same additions in the same order as row_reduce_static / row_reduce_fixed (same bits), but per row 2 LDS reads per term
-// instead of two staged term arrays written and read back by every 8-lane group (the objective was 0.7 us of the 6.9 us
-// generation at the metric shape).
+// Same additions in the same order as numpy (same bits) with 2 LDS reads per term and no term array staged in LDS (the
+// objective was 0.7 us of the 6.9 us generation at the metric shape).
 template <int FUN, int LPR, int NFIX>
 __device__ __forceinline__ double row_objective_chain(const double *U, int l) {
     using O = Obj<FUN>;
@@ -172,11 +171,10 @@ __device__ __forceinline__ double row_objective_chain(const double *U, int l) {
 // row's time, and long rows of the usual lengths get the plan as constants (row_reduce_long)
 template <int FUN>
 constexpr bool light_objective() {
-    return FUN == SX_FUN_ROSENBROCK || FUN == SX_FUN_SPHERE || FUN == SX_FUN_QUARTIC || FUN == SX_FUN_STYBLINSKI_TANG;
+    return light_objective(FUN);
 }
-// The same register chains for rows whose length is only known at run time (round 5: shapes off the benchmark grid -- n = 100,
-// 130, 250 ... -- used to take the staged-terms path: term arrays written to LDS, the plan walked with scalar loads).  A row
-// that fits one batch (n <= 4 LPR, i.e. EVERY row of up to 256 elements) has at most three leaves in numpy's recursion, each
+// The same register chains for rows whose length is only known at run time (shapes off the benchmark grid: n = 100, 130,
+// 250 ...).  A row that fits one batch (n <= 4 LPR, i.e. EVERY row of up to 256 elements) has at most three leaves in numpy's recursion, each
 // of at most 16 blocks, and only the last one has a tail:
 //   m <= 128: one leaf;   m in 129..256: split at n2 = (m/2) - (m/2) % 8 -- and the right part r = m - n2 once more if it
 //   is still above 128 (129..135: m = 249..255): 64 + (r - 64), two leaves of at most 8 blocks -- S0 + (S1 + S2).
@@ -235,10 +233,6 @@ __device__ __forceinline__ void leaf_chain_rt(const double (&a)[4], const double
         if (TWO) rb = combine<BMUL>(rb, dpp_f64<0x108>(rb));
     }
 }
-
-#ifndef SX_OBJ_CHAIN_RT
-#define SX_OBJ_CHAIN_RT 1  // A/B switch: 0 = one-batch rows of run-time length stage their terms (rounds 1-4)
-#endif
 
 template <int FUN, int LPR>
 __device__ __forceinline__ double row_objective_chain_rt(const double *U, int n, const PlanArg &plan, int l) {
@@ -336,109 +330,56 @@ __device__ __forceinline__ double row_objective_chain_rt(const double *U, int n,
     return O::finish(sa, sb, n);
 }
 
-// rows whose objective needs nothing but the staged vector itself (row_objective_chain): kernels that stage for nobody else
-// (sx_eval) can then give a row n + 8 doubles of LDS instead of lds_row_stride(n) and fit twice the workgroups on a CU
-#ifndef SX_OBJ_CHAIN
-#define SX_OBJ_CHAIN 1  // A/B switch: 0 = the staged-terms form for one-batch rows too
-#endif
-#ifndef SX_OBJ_CHAIN256
-#define SX_OBJ_CHAIN256 1  // A/B: 0 = rows of 256 elements stage their terms
-#endif
-#ifndef SX_LONG_STATIC
-#define SX_LONG_STATIC 1  // (0: long rows inside the generation kernels keep the run-time plan -- A/B builds)
-#endif
+// rows whose objective is the compile-time register chain (row_objective_chain): whole-batch rows of 64 / 128 elements, and of
+// 256 with one term per element (two full leaves)
 template <int FUN, int NFIX>
 constexpr bool chain_only() {
-    return SX_OBJ_CHAIN && NFIX != 0 && (NFIX <= 128 || (SX_OBJ_CHAIN256 && NFIX == 256 && !Obj<FUN>::NEXT));
+    return NFIX != 0 && (NFIX <= 128 || (NFIX == 256 && !Obj<FUN>::NEXT));
 }
 
-// Objective of the row staged in LDS at U[0..n): terms by the row's LPR lanes -> A/B (behind U),
-// then the numpy-order row sums (lanes l >= 8 repeat the chains of lanes l & 7: LDS broadcasts, same bits).
+// Objective of the row staged in LDS at U[0..n): the terms are formed from the staged vector inside the numpy-order row sum,
+// nothing else is staged (whole-wave rows of more than 256 elements keep their leaf sums behind U[n + 8]).
 // Every lane of the row returns the value.  Each row works on its own LDS slice (no workgroup barrier).
 // NFIX: the row length when it is a compile-time constant (the PSO kernel's whole-batch rows), else 0
 // LONGSTATIC = 0: no branch to the compile-time plans of n = 512 / 1024 / 2048 (the one-workgroup kernels of
 // updating="immediate", 1 024 threads at the 128-VGPR cap, would spill for them)
 // ONEBATCH: the caller guarantees n <= 4 LPR (a whole-wave kernel instantiated for rows of up to 256 elements): nothing but the
 // run-time register chain is compiled (the kernel then does not carry the long rows' plans in its register budget)
-template <int FUN, int LPR, bool FULL = false, int NFIX = 0, int LONGSTATIC = SX_LONG_STATIC, bool ONEBATCH = false>
+template <int FUN, int LPR, int NFIX = 0, int LONGSTATIC = 1, bool ONEBATCH = false>
 __device__ __forceinline__ double row_objective(double *U, int n, const PlanArg &plan, int l) {
     using O = Obj<FUN>;
-    const int m = O::NEXT ? n - 1 : n;
     lds_wave_fence();  // U complete (written and read by this wave only)
-    if constexpr (chain_only<FUN, NFIX>())
+    if constexpr (chain_only<FUN, NFIX>()) {
         return row_objective_chain<FUN, LPR, NFIX>(U, l);
-    if constexpr ((NFIX == 0 || NFIX <= 256) && SX_OBJ_CHAIN_RT) {  // one-batch rows (every n <= 256) without a compile-time chain form: the same chains, run-time block counts
-        // (NFIX = 256 with an objective that reads the next element -- m = 255: three leaves -- comes here too: no kernel stages
-        //  terms for a row of up to 256 elements any more, so such rows need n + 8 doubles of LDS, sx_device.hpp de_row_stride)
-        // (lanes_per_row gives 16 / 32 lanes to rows of up to 64 / 128 elements only: a short-row kernel never meets a longer row,
-        //  and the staged-terms code below is not even compiled for it)
-        if constexpr (LPR < kWave || ONEBATCH) return row_objective_chain_rt<FUN, LPR>(U, n, plan, l);
-        if (n <= 4 * LPR) return row_objective_chain_rt<FUN, LPR>(U, n, plan, l);
-    }
-    if constexpr (NFIX > 256) {  // a long row of compile-time length: numpy's plan as constants (row_reduce_long)
-        static_assert(LPR == kWave, "whole-wave rows");
+    } else if constexpr (LPR < kWave || ONEBATCH || (NFIX != 0 && NFIX <= 256)) {
+        // one-batch rows (every n <= 256) without a compile-time chain form: the same chains, run-time block counts.
+        // (lanes_per_row gives 16 / 32 lanes to rows of up to 64 / 128 elements only: a short-row kernel never meets a longer
+        //  row.  NFIX = 256 with an objective that reads the next element -- m = 255: three leaves -- comes here too.)
+        return row_objective_chain_rt<FUN, LPR>(U, n, plan, l);
+    } else if constexpr (NFIX > 256) {  // a long row of compile-time length: numpy's plan as constants (row_reduce_long)
         double sa, sb;
         row_reduce_long<FUN, (O::NEXT ? NFIX - 1 : NFIX), (light_objective<FUN>() ? 8 : 4)>(U, l, sa, sb);
         return O::finish(sa, sb, NFIX);
-    }
-    if constexpr (LONGSTATIC != 0 && NFIX == 0 && LPR == kWave && light_objective<FUN>()) {
-        // long rows of the usual lengths inside the generation kernels (BASELINE config 5: n = 1024): the same constants, picked by
-        // a uniform branch on the run-time length
-        if (n == 1024 || n == 512 || n == 2048) {
-            double sa, sb;
-            if (n == 1024)
-                row_reduce_long<FUN, (O::NEXT ? 1023 : 1024)>(U, l, sa, sb);
-            else if (n == 512)
-                row_reduce_long<FUN, (O::NEXT ? 511 : 512)>(U, l, sa, sb);
-            else
-                row_reduce_long<FUN, (O::NEXT ? 2047 : 2048)>(U, l, sa, sb);
-            return O::finish(sa, sb, n);
-        }
-    }
-    if (LPR == kWave && fused_terms(n)) {  // terms are formed inside the reduction, nothing else is staged
-        double sa, sb;
-        row_reduce_leaves_fused<FUN, LPR>(U, U + n + 8, leaf_cap(n), m, plan, l, sa, sb);
-        return O::finish(sa, sb, n);
-    }
-    double *A = U + n + 8;
-    double *B = A + n;
-    for (int e0 = l; e0 < m; e0 += 4 * LPR) {  // 4 steps per trip: the LDS reads of a trip are independent
-        double x[4], xn[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int e = e0 + t * LPR;
-            // FULL: rows are whole batches, U[n..n+7] is padding, so the reads need no guard
-            x[t] = (FULL || e < m) ? U[e] : 0.0;
-            xn[t] = (O::NEXT && (FULL || e < m)) ? U[e + 1] : 0.0;
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int e = e0 + t * LPR;
-            if (e < m) {
-                double a, b;
-                O::term(x[t], xn[t], e, a, b);
-                A[e] = a;
-                if (O::TWO) B[e] = b;
+    } else {  // a whole-wave row of run-time length
+        if (n <= 4 * LPR) return row_objective_chain_rt<FUN, LPR>(U, n, plan, l);
+        if constexpr (LONGSTATIC != 0 && light_objective<FUN>()) {
+            // long rows of the usual lengths inside the generation kernels (BASELINE config 5: n = 1024): the same constants,
+            // picked by a uniform branch on the run-time length
+            if (n == 1024 || n == 512 || n == 2048) {
+                double sa, sb;
+                if (n == 1024)
+                    row_reduce_long<FUN, (O::NEXT ? 1023 : 1024)>(U, l, sa, sb);
+                else if (n == 512)
+                    row_reduce_long<FUN, (O::NEXT ? 511 : 512)>(U, l, sa, sb);
+                else
+                    row_reduce_long<FUN, (O::NEXT ? 2047 : 2048)>(U, l, sa, sb);
+                return O::finish(sa, sb, n);
             }
         }
-    }
-    lds_wave_fence();  // terms complete
-    double sa, sb;
-    if constexpr (NFIX != 0 && NFIX <= 256) {  // the number of terms, and with it numpy's plan, is known at compile time
-        if constexpr (!O::NEXT)
-            row_reduce_fixed<O::TWO, O::BMUL, LPR, NFIX>(A, B, l, sa, sb);
-        else
-            row_reduce_static<O::TWO, O::BMUL, NFIX - 1>(A, B, l, sa, sb);
+        double sa, sb;  // terms are formed inside the reduction; the leaf sums sit behind the vector
+        row_reduce_leaves_fused<FUN, LPR>(U, U + n + 8, leaf_cap(n), plan, l, sa, sb);
         return O::finish(sa, sb, n);
     }
-    // uniform: n > 128, leaves reduced in parallel by the row's 8-lane groups.  (For FULL rows the choice is known at
-    // compile time, and dropping the other branch takes the two-stream PSO kernels from 106 to 81 VGPRs = 6 waves per
-    // SIMD instead of 4 -- measured SLOWER at BASELINE config 3, 48.2 vs 45.0 us: profiles/r2_pso_c3_variants.txt.)
-    if (plan.nleaf > 1)
-        row_reduce_leaves<O::TWO, O::BMUL, LPR>(A, B, B + n, B + n + 24, leaf_cap(n), plan, l, sa, sb);
-    else
-        row_reduce2<O::TWO, O::BMUL>(A, B, B + n, plan, l, sa, sb);
-    return O::finish(sa, sb, n);
 }
 
 // one (min f, first row) record per workgroup for the best-of-generation step

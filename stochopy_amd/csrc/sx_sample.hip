@@ -183,7 +183,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
             }
         }
         // (an infeasible proposal is evaluated too and its value dropped: the rows of a wave stay in step)
-        const double fU = row_objective<FUN, LPR, false, 0, 0>(U, n, plan, l);
+        const double fU = row_objective<FUN, LPR, 0, 0>(U, n, plan, l);
         bool xbest_changed = false;
         if (it == 0) {
             st.start(fU);
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
                         }
                         double fv[2];
 #pragma unroll 1
-                        for (int w = 0; w < 2; ++w) fv[w] = row_objective<FUN, LPR, false, 0, 0>(w ? X1 : X2, n, plan, l);
+                        for (int w = 0; w < 2; ++w) fv[w] = row_objective<FUN, LPR, 0, 0>(w ? X1 : X2, n, plan, l);
                         const double gv = (0.5 * (fv[0] - fv[1])) / h;
                         if (own) {
                             Pm[i] = Pm[i] - (coef * a.step[i]) * gv;
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
             for (int e = l; e < n; e += LPR) s += Pm[e] * Pm[e];
             K = 0.5 * row_sum<LPR>(s);
         }
-        const double fQ = row_objective<FUN, LPR, false, 0, 0>(Q, n, plan, l);
+        const double fQ = row_objective<FUN, LPR, 0, 0>(Q, n, plan, l);
         bool xbest_changed = false;
         if (it == 0) {
             st.start(fQ);

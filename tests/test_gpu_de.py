@@ -263,7 +263,7 @@ def test_de_graph_equals_stepwise(sa):
 def test_de_one_batch_rows_through_replayed_graphs_match_oracle(sa, objective, shape):
     """Rows of exactly 64 / 128 / 256 elements with a population that fills whole workgroups take the chained kernel in
     which the row length -- and numpy's summation plan with it -- is a compile-time constant (csrc/sx_de.hip NFIX,
-    sx_device.hpp row_reduce_fixed / pairwise_static).  No callback: the generations run as replayed graphs of that
+    sx_rowops.hpp row_objective_chain).  No callback: the generations run as replayed graphs of that
     kernel.  Bit-identical to the oracle for every strategy."""
     n, P = shape
     for strategy, constraints in (("best1bin", None), ("rand1bin", "Random"), ("best2bin", None), ("rand2bin", None)):

@@ -120,8 +120,8 @@ def test_pso_philox_matches_oracle(sa, method, constraints, shape):
 @pytest.mark.parametrize("shape", [(64, 40), (128, 33), (256, 70), (256, 2048)])
 def test_pso_whole_batch_rows_match_oracle(sa, objective, shape):
     """Rows of exactly 64 / 128 / 256 elements take the kernel in which the row length -- and with it numpy's summation
-    plan -- is a compile-time constant (csrc/sx_pso.hip FULL, sx_device.hpp row_reduce_fixed): bit-identical to the
-    oracle for the +,-,* objectives (one term per element: row_reduce_fixed; n - 1 terms: pairwise_static), PSO and CPSO
+    plan -- is a compile-time constant (csrc/sx_pso.hip FULL, sx_rowops.hpp row_objective_chain): bit-identical to the
+    oracle for the +,-,* objectives (one term per element, and Rosenbrock's n - 1 terms), PSO and CPSO
     (Shrink for the larger swarm)."""
     n, P = shape
     for method in ("pso", "cpso"):

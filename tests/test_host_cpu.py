@@ -259,6 +259,32 @@ def test_sum_plan_reproduces_numpy_pairwise(lib, m):
     assert 0.0 + stack[0] == a.sum()
 
 
+def test_row_geometry_numbers_are_pinned(lib):
+    """Rows per workgroup and record counts size LDS, grids and the (part_f, part_i) buffers of every row kernel.  The
+    expected values restate the sizing rule: a row's LDS budget is n + 8 + 2 (n/64 + 2) doubles above 256 elements and
+    3n + 32 + 2 (n/64 + 2) up to there; a workgroup is the largest power-of-two number of waves (<= 8) with <= 16 rows
+    and <= 64 KiB of such rows; rows of up to 64 / 128 elements share a wave four / two at a time; beyond the wide
+    threshold a workgroup is one row."""
+    wide_from = lib.sx_wide_from()
+    assert wide_from == 2048
+
+    def rows_per_block(n):
+        cap = n // 64 + 2
+        stride = n + 8 + 2 * cap if n > 256 else 3 * n + 8 + 24 + 2 * cap
+        rpw = 64 // (16 if n <= 64 else 32 if n <= 128 else 64)
+        fit = (64 * 1024) // (8 * stride * rpw)
+        w = 1
+        while 2 * w <= fit and 2 * w * rpw <= 16 and 2 * w <= 8:
+            w *= 2
+        return w * rpw
+
+    for n in range(1, 4097):
+        assert lib.sx_rows_per_workgroup(n) == (1 if n > wide_from else rows_per_block(n)), n
+    for P in (2, 37, 4096, 16400):
+        for n in (1, 64, 65, 128, 129, 256, 257, 512, 1024, 2048):
+            assert lib.sx_num_partials(P, n) == -(-P // rows_per_block(n)), (P, n)
+
+
 def test_exchange_buffer_geometry(lib):
     """Host side of the peer exchange: slots[2][8][w] + probe[8][w] words of 8 bytes, w = 2(n+2) rounded up to
     whole 128-byte lines; the relay holds two records + their ready lines; bad arguments are refused."""
