@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "sx_device.hpp"
-#include "sx_host.hpp"
+#include "sx_enqueue.hpp"
 #include "sx_rowops.hpp"
 #include "sx_wide.hpp"
 
@@ -880,7 +880,7 @@ __global__ __launch_bounds__(kFinalThreads) void select_finalize_kernel(
                 acc += d * d;
             }
         }
-    } else {  // (longer rows take the three-launch form below: sx_select_finalize / add_finalize_node)
+    } else {  // (longer rows take the three-launch form below: enqueue_finalize)
         acc = final_dist2(gbest, src, n);
     }
 #pragma unroll
@@ -998,25 +998,29 @@ __global__ __launch_bounds__(kWave) void wide_finalize_state_kernel(const double
 }
 static inline int wide_final_blocks(int64_t npart) { return npart < kWideFinalBlocks ? (int)npart : kWideFinalBlocks; }
 
+namespace sx {
+int enqueue_finalize(Enqueue &q, const double *part_f, const int64_t *part_i, int64_t npart, const double *rows0,
+                     const double *rows1, int64_t ld, int n, double *gbest, sx_state *state, int maxiter, double xtol,
+                     double ftol) {
+    if (n <= kMaxDim)
+        return q.kernel(select_finalize_kernel, dim3(1), dim3(kFinalThreads), 0, part_f, part_i, npart, rows0, rows1, ld, n,
+                        gbest, state, maxiter, xtol, ftol);
+    const int nb = wide_final_blocks(npart);
+    double *share = const_cast<double *>(part_f);  // (the records are consumed by the first launch: the header says so)
+    if (int rc = q.kernel(wide_finalize_best_kernel, dim3(1), dim3(kFinalThreads), 0, part_f, part_i, npart, state)) return rc;
+    if (int rc = q.kernel(wide_finalize_row_kernel, dim3(nb), dim3(kFinalThreads), 0, rows0, rows1, ld, n, gbest, state, share))
+        return rc;
+    return q.kernel(wide_finalize_state_kernel, dim3(1), dim3(kWave), 0, share, nb, state, maxiter, xtol, ftol);
+}
+}  // namespace sx
+
 extern "C" int sx_select_finalize(const double *part_f, const int64_t *part_i, int64_t npart, const double *rows0,
                                   const double *rows1, int64_t ld, int n, double *gbest, sx_state *state, int maxiter,
                                   double xtol, double ftol, void *stream) {
     SX_REQUIRE(part_f && part_i && rows0 && rows1 && gbest && state && npart >= 1 && n >= 1,
                "sx_select_finalize: bad arguments");
-    if (n > kMaxDim) {
-        hipStream_t s = (hipStream_t)stream;
-        const int nb = wide_final_blocks(npart);
-        double *share = const_cast<double *>(part_f);  // (the records are consumed by the first launch: the header says so)
-        hipLaunchKernelGGL(wide_finalize_best_kernel, dim3(1), dim3(kFinalThreads), 0, s, part_f, part_i, npart, state);
-        hipLaunchKernelGGL(wide_finalize_row_kernel, dim3(nb), dim3(kFinalThreads), 0, s, rows0, rows1, ld, n, gbest, state, share);
-        hipLaunchKernelGGL(wide_finalize_state_kernel, dim3(1), dim3(kWave), 0, s, share, nb, state, maxiter, xtol, ftol);
-        SX_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(select_finalize_kernel, dim3(1), dim3(kFinalThreads), 0, (hipStream_t)stream, part_f, part_i,
-                       npart, rows0, rows1, ld, n, gbest, state, maxiter, xtol, ftol);
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    return enqueue_finalize(q, part_f, part_i, npart, rows0, rows1, ld, n, gbest, state, maxiter, xtol, ftol);
 }
 
 // ---------------------------------------------------------------------------
@@ -1109,48 +1113,6 @@ extern "C" int sx_gather_finalize(const double *records, int world, int n, doubl
     SX_LAUNCH_CHECK();
     return 0;
 }
-
-namespace sx {
-int add_finalize_node(hipGraph_t graph, hipGraphNode_t *prev, const double *part_f, const int64_t *part_i,
-                      int64_t npart, const double *rows0, const double *rows1, int64_t ld, int n, double *gbest,
-                      sx_state *state, int maxiter, double xtol, double ftol) {
-    if (n > kMaxDim) {  // the three launches of sx_select_finalize's wide form
-        int nb = wide_final_blocks(npart);
-        double *share = const_cast<double *>(part_f);
-        auto add = [&](void *fn, unsigned grid, unsigned block, void **ka) -> int {
-            hipKernelNodeParams kq = {};
-            kq.func = fn;
-            kq.gridDim = dim3(grid);
-            kq.blockDim = dim3(block);
-            kq.sharedMemBytes = 0;
-            kq.kernelParams = ka;
-            kq.extra = nullptr;
-            hipGraphNode_t nd;
-            SX_HIP(hipGraphAddKernelNode(&nd, graph, *prev ? prev : nullptr, *prev ? 1 : 0, &kq));
-            *prev = nd;
-            return 0;
-        };
-        void *k1[] = {&part_f, &part_i, &npart, &state};
-        if (int rc = add((void *)wide_finalize_best_kernel, 1, kFinalThreads, k1)) return rc;
-        void *k2[] = {&rows0, &rows1, &ld, &n, &gbest, &state, &share};
-        if (int rc = add((void *)wide_finalize_row_kernel, (unsigned)nb, kFinalThreads, k2)) return rc;
-        void *k3[] = {&share, &nb, &state, &maxiter, &xtol, &ftol};
-        return add((void *)wide_finalize_state_kernel, 1, kWave, k3);
-    }
-    void *kargs[] = {&part_f, &part_i, &npart, &rows0, &rows1, &ld, &n, &gbest, &state, &maxiter, &xtol, &ftol};
-    hipKernelNodeParams kp = {};
-    kp.func = (void *)select_finalize_kernel;
-    kp.gridDim = dim3(1);
-    kp.blockDim = dim3(kFinalThreads);
-    kp.sharedMemBytes = 0;
-    kp.kernelParams = kargs;
-    kp.extra = nullptr;
-    hipGraphNode_t node;
-    SX_HIP(hipGraphAddKernelNode(&node, graph, *prev ? prev : nullptr, *prev ? 1 : 0, &kp));
-    *prev = node;
-    return 0;
-}
-}  // namespace sx
 
 // ---------------------------------------------------------------------------
 // Initial population in Philox mode: the reference's Latin hypercube (_common.py:109-120)

@@ -19,8 +19,8 @@
 
 namespace sx {
 // the chained (sx_de_chain.hip) and peer-exchange (sx_de_p2p.hip) kernels, as launchable function pointers
-void *de_chain_kernel(int fun_id, int n, int64_t P, int strategy, int constraints);
-void *de_p2p_kernel(int fun_id, int n, int64_t P, int strategy, int constraints);
+de_kernel_t de_chain_kernel(int fun_id, int n, int64_t P, int strategy, int constraints);
+de_kernel_t de_p2p_kernel(int fun_id, int n, int64_t P, int strategy, int constraints);
 }
 
 namespace {
@@ -53,73 +53,44 @@ Geometry geometry(const sx_de_args *a) {
     return g;
 }
 
+// One generation: the generation kernel (rows of more than the run's wide_from elements: one workgroup per row, sx_wide.hip,
+// one record per row) and, with `finalize`, the best / termination step behind it.  Every launch is identical (the
+// per-generation state is read from a.state on the device), so a graph of generations is this, ngen times.
+int enqueue_de_generation(Enqueue &q, const sx_de_args *a, int finalize) {
+    const Geometry g = geometry(a);
+    if (is_wide(a->n, de_wide_from(a))) {
+        if (int rc = wide_de_enqueue(q, a)) return rc;
+    } else {
+        PlanArg plan;
+        if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
+        if (int rc = q.kernel(kernel_for(a), dim3(g.blocks), dim3(g.threads), g.lds, nullptr, nullptr, nullptr, g.blocks, *a,
+                              plan, 0, 0, sx_xchg_args{}))
+            return rc;
+    }
+    if (!finalize) return 0;
+    SX_REQUIRE(a->gbest != nullptr, "sx_de_generation: the separate finalize kernel needs the gbest buffer");
+    return enqueue_finalize(q, a->part_f, a->part_i, g.blocks, a->buf0, a->buf1, a->ld, a->n, a->gbest, a->state, a->maxiter,
+                            a->xtol, a->ftol);
+}
+
 }  // namespace
 
 extern "C" int sx_de_generation(const sx_de_args *a, int finalize, void *stream) {
     if (int rc = check_args(a)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const Geometry g = geometry(a);
-    if (is_wide(a->n, de_wide_from(a))) {  // rows of more than the run's wide_from elements: one workgroup per row (sx_wide.hip), one record per row
-        if (int rc = wide_de_launch(a, s)) return rc;
-    } else {
-        PlanArg plan;
-        if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-        hipLaunchKernelGGL(kernel_for(a), dim3(g.blocks), dim3(g.threads), g.lds, s, (const sx_state *)nullptr,
-                           (const double *)nullptr, (const int64_t *)nullptr, (int64_t)g.blocks, *a, plan, 0, 0,
-                           sx_xchg_args{});
-        SX_LAUNCH_CHECK();
-    }
-    if (finalize) {
-        SX_REQUIRE(a->gbest != nullptr, "sx_de_generation: the separate finalize kernel needs the gbest buffer");
-        return sx_select_finalize(a->part_f, a->part_i, g.blocks, a->buf0, a->buf1, a->ld, a->n, a->gbest, a->state,
-                                  a->maxiter, a->xtol, a->ftol, stream);
-    }
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    return enqueue_de_generation(q, a, finalize);
 }
 
-// ---------------------------------------------------------------------------
-// hipGraph of ngen generations: 2*ngen kernel nodes in a chain, every node
-// identical (per-generation state is read from a.state on the device).
-// ---------------------------------------------------------------------------
+// hipGraph of ngen generations: 2*ngen kernel nodes in a chain (4*ngen for rows of more than kMaxDim elements)
 extern "C" int sx_de_graph_create(const sx_de_args *a, int ngen, sx_graph **out) {
     if (int rc = check_args(a)) return rc;
     SX_REQUIRE(out != nullptr && ngen >= 1 && a->gbest != nullptr, "sx_de_graph_create: bad arguments");
     SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_de_graph_create: graphs need in-kernel (Philox) draws");
-    PlanArg plan = {};
-    const bool wide = is_wide(a->n, de_wide_from(a));
-    if (!wide && make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const Geometry g = geometry(a);
-    sx_graph *gr = new sx_graph();
-    SX_HIP(hipGraphCreate(&gr->graph, 0));
-    sx_de_args args = *a;
-    int zero = 0;
-    int64_t npart = g.blocks;
-    sx_xchg_args nox = {};
-    const void *none = nullptr;
-    void *kargs[] = {&none, &none, &none, &npart, &args, &plan, &zero, &zero, &nox};
-    hipGraphNode_t prev = nullptr;
-    for (int i = 0; i < ngen; ++i) {
-        if (wide) {
-            if (int rc = wide_de_add_node(gr->graph, &prev, a)) return rc;
-        } else {
-            hipKernelNodeParams kp = {};
-            kp.func = (void *)kernel_for(a);
-            kp.gridDim = dim3(g.blocks);
-            kp.blockDim = dim3(g.threads);
-            kp.sharedMemBytes = (unsigned)g.lds;
-            kp.kernelParams = kargs;
-            kp.extra = nullptr;
-            hipGraphNode_t node;
-            SX_HIP(hipGraphAddKernelNode(&node, gr->graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp));
-            prev = node;
-        }
-        if (int rc = add_finalize_node(gr->graph, &prev, a->part_f, a->part_i, g.blocks, a->buf0, a->buf1, a->ld, a->n,
-                                       a->gbest, a->state, a->maxiter, a->xtol, a->ftol))
-            return rc;
-    }
-    SX_HIP(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0));
-    *out = gr;
-    return 0;
+    GraphBuild gb;
+    if (int rc = gb.begin()) return rc;
+    for (int i = 0; i < ngen; ++i)
+        if (int rc = enqueue_de_generation(gb.sink(), a, 1)) return rc;
+    return gb.finish(out);
 }
 
 // Multi-GPU: this shard's generation + its best-of-generation record, one host call (the caller then
@@ -146,58 +117,35 @@ static int check_chain(const sx_de_args *a, bool peer_exchange) {
 }
 
 // x == nullptr: single GPU (XM = 1); otherwise the peer-exchange kernel (XM = 2, one service workgroup in front)
-static int chain_launch(const sx_de_args *a, const sx_xchg_args *x, int parity, int finalize_only, void *stream) {
-    if (int rc = check_chain(a, x != nullptr)) return rc;
-    SX_REQUIRE(parity == 0 || parity == 1, "sx_de_chain_launch: parity must be 0 or 1");
+static int enqueue_de_chain(Enqueue &q, const sx_de_args *a, const sx_xchg_args *x, int parity, int finalize_only) {
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     const Geometry g = geometry(a);
-    de_kernel_t kern = (de_kernel_t)(x ? de_p2p_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints)
-                                       : de_chain_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints));
+    const de_kernel_t kern = x ? de_p2p_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints)
+                               : de_chain_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints);
     const unsigned blocks = finalize_only ? 1u : g.blocks + (x ? 1u : 0u);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(g.threads), g.lds, (hipStream_t)stream,
-                       (const sx_state *)(a->state + parity), (const double *)(a->part_f + (int64_t)parity * g.blocks),
-                       (const int64_t *)(a->part_i + (int64_t)parity * g.blocks), (int64_t)g.blocks, *a, plan, parity,
-                       finalize_only ? 1 : 0, x ? *x : sx_xchg_args{});
-    SX_LAUNCH_CHECK();
-    return 0;
+    const int64_t npart = g.blocks;
+    // (the four leading arguments are scalars of their own: the single-GPU kernel has them preloaded, sx_de_kernel.hpp)
+    return q.kernel(kern, dim3(blocks), dim3(g.threads), g.lds, a->state + parity, a->part_f + parity * npart,
+                    a->part_i + parity * npart, npart, *a, plan, parity, finalize_only ? 1 : 0, x ? *x : sx_xchg_args{});
+}
+
+static int chain_launch(const sx_de_args *a, const sx_xchg_args *x, int parity, int finalize_only, void *stream) {
+    if (int rc = check_chain(a, x != nullptr)) return rc;
+    SX_REQUIRE(parity == 0 || parity == 1, "sx_de_chain_launch: parity must be 0 or 1");
+    Enqueue q((hipStream_t)stream);
+    return enqueue_de_chain(q, a, x, parity, finalize_only);
 }
 
 static int chain_graph_create(const sx_de_args *a, const sx_xchg_args *x, int ngen, int start_parity, sx_graph **out) {
     if (int rc = check_chain(a, x != nullptr)) return rc;
     SX_REQUIRE(out != nullptr && ngen >= 1 && (start_parity == 0 || start_parity == 1),
                "sx_de_chain_graph_create: bad arguments");
-    PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const Geometry g = geometry(a);
-    sx_graph *gr = new sx_graph();
-    SX_HIP(hipGraphCreate(&gr->graph, 0));
-    sx_de_args args = *a;
-    sx_xchg_args xa = x ? *x : sx_xchg_args{};
-    int mode = 0;
-    int64_t npart = g.blocks;
-    hipGraphNode_t prev = nullptr;
-    for (int i = 0; i < ngen; ++i) {
-        int parity = (start_parity + i) & 1;
-        const sx_state *sin_pre = a->state + parity;  // preloadable leading arguments (sx_de_kernel.hpp)
-        const double *pf_pre = a->part_f + (int64_t)parity * npart;
-        const int64_t *pi_pre = a->part_i + (int64_t)parity * npart;
-        void *kargs[] = {&sin_pre, &pf_pre, &pi_pre, &npart, &args, &plan, &parity, &mode, &xa};
-        hipKernelNodeParams kp = {};
-        kp.func = x ? de_p2p_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints)
-                    : de_chain_kernel(a->fun_id, a->n, a->P, a->strategy, a->constraints);
-        kp.gridDim = dim3(g.blocks + (x ? 1u : 0u));
-        kp.blockDim = dim3(g.threads);
-        kp.sharedMemBytes = (unsigned)g.lds;
-        kp.kernelParams = kargs;
-        kp.extra = nullptr;
-        hipGraphNode_t node;
-        SX_HIP(hipGraphAddKernelNode(&node, gr->graph, prev ? &prev : nullptr, prev ? 1 : 0, &kp));
-        prev = node;
-    }
-    SX_HIP(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0));
-    *out = gr;
-    return 0;
+    GraphBuild gb;
+    if (int rc = gb.begin()) return rc;
+    for (int i = 0; i < ngen; ++i)
+        if (int rc = enqueue_de_chain(gb.sink(), a, x, (start_parity + i) & 1, 0)) return rc;
+    return gb.finish(out);
 }
 
 extern "C" int sx_de_chain_launch(const sx_de_args *a, int parity, int finalize_only, void *stream) {

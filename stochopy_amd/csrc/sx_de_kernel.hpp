@@ -9,15 +9,12 @@
 #include <vector>
 
 #include "sx_device.hpp"
-#include "sx_host.hpp"
+#include "sx_enqueue.hpp"
 #include "sx_rowops.hpp"
 #include "sx_xchg.hpp"
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out);
-int add_finalize_node(hipGraph_t graph, hipGraphNode_t *prev, const double *part_f, const int64_t *part_i,
-                      int64_t npart, const double *rows0, const double *rows1, int64_t ld, int n, double *gbest,
-                      sx_state *state, int maxiter, double xtol, double ftol);
 int check_xchg_args(const sx_xchg_args *x);
 }
 using namespace sx;

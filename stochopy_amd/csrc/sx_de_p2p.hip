@@ -4,7 +4,7 @@
 #include "sx_de_kernel.hpp"
 
 namespace sx {
-void *de_p2p_kernel(int fun_id, int n, int64_t P, int strategy, int constraints) {
-    return (void *)pick_kernel<SX_RNG_PHILOX, 2>(fun_id, n, P, strategy, constraints);
+de_kernel_t de_p2p_kernel(int fun_id, int n, int64_t P, int strategy, int constraints) {
+    return pick_kernel<SX_RNG_PHILOX, 2>(fun_id, n, P, strategy, constraints);
 }
 }  // namespace sx

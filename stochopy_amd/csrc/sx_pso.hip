@@ -14,7 +14,7 @@
 #include <cstdlib>
 
 #include "sx_device.hpp"
-#include "sx_host.hpp"
+#include "sx_enqueue.hpp"
 #include "sx_rowops.hpp"
 #include "sx_wide.hpp"
 
@@ -1043,49 +1043,76 @@ __global__ __launch_bounds__(256) void pso_restart_apply_kernel(
     if (lane == 0) a.pbestfit[row] = 1.0e30;
 }
 
+// One generation.  part_rad != NULL (CPSO inside a fused-radius graph): the general kernel, which also leaves the radius
+// by-product there (the plain one leaves none).
+int enqueue_pso_generation(Enqueue &q, const sx_pso_args *a, double *part_rad) {
+    if (is_wide(a->n, kWideFrom)) return wide_pso_enqueue(q, a);  // one workgroup per particle (sx_wide.hip)
+    const Geometry g = geometry(a->P, a->n);
+    PlanArg plan;
+    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
+    const bool plain = a->constraints == 0 && a->pending_restart == nullptr && part_rad == nullptr;
+    const pso_kernel_t kern = a->rng == SX_RNG_PHILOX ? pick_kernel<SX_RNG_PHILOX>(a->fun_id, a->n, plain)
+                                                       : pick_kernel<SX_RNG_HOST>(a->fun_id, a->n, plain);
+    return q.kernel(kern, dim3(g.blocks), dim3(g.threads), g.lds, *a, plan, part_rad, part_rad ? (int64_t)g.blocks : 0);
+}
+
+int enqueue_pso_finalize(Enqueue &q, const sx_pso_args *a) {
+    return enqueue_finalize(q, a->part_f, a->part_i, geometry(a->P, a->n).blocks, a->pbest, a->pbest, a->ld, a->n, a->gbest,
+                            a->state, a->maxiter, a->xtol, a->ftol);
+}
+
+int enqueue_pso_radius(Enqueue &q, const sx_pso_args *a, double *part_r) {
+    const Geometry g = geometry(a->P, a->n);
+    SX_DISPATCH_LPR(a->n, return q.kernel(pso_radius_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0, *a, part_r))
+}
+
+int enqueue_restart_select(Enqueue &q, const sx_pso_args *a, const double *part_r, double delta, double gamma,
+                           uint64_t *out3) {
+    return q.kernel(pso_restart_select_kernel, dim3(1), dim3(kSelThreads), 0, *a, a->pbestfit, part_r, 1, a->P,
+                    geometry(a->P, a->n).blocks, a->P, delta, gamma, (unsigned long long *)out3);
+}
+
+// rows chosen on the device (sel3) or listed by the host
+int enqueue_restart_apply(Enqueue &q, const sx_pso_args *a, const uint64_t *sel3, const int64_t *host_rows,
+                          const double *host_x, int64_t host_count) {
+    const int64_t slots = host_rows ? host_count : a->P;
+    if (slots == 0) return 0;
+    const int rpb = 4;
+    return q.kernel(pso_restart_apply_kernel, dim3((unsigned)((slots + rpb - 1) / rpb)), dim3(rpb * kWave), 0, *a,
+                    (const unsigned long long *)sel3, host_rows, host_x, host_count);
+}
+
+// CPSO with whole-batch rows inside a graph: best / termination, the radius (from the generation kernel's by-product in
+// part_rold) and the selection in one launch; hscratch != NULL: with helper workgroups
+int enqueue_cpso_post(Enqueue &q, const sx_pso_args *a, const double *part_rold, double delta, double gamma, uint64_t *sel3,
+                      int force_exact, unsigned long long *hscratch) {
+    SX_DISPATCH_LPR(a->n, return q.kernel(cpso_post_kernel<LPR>, dim3(hscratch ? kPostHelpers + 1 : 1), dim3(kSelThreads), 0,
+                                          *a, a->part_f, a->part_i, part_rold, geometry(a->P, a->n).blocks, a->xtol, delta,
+                                          gamma, (unsigned long long *)sel3, force_exact, hscratch))
+}
+
 }  // namespace
 
 extern "C" int sx_pso_generation(const sx_pso_args *a, int finalize, void *stream) {
     if (int rc = check_args(a)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const Geometry g = geometry(a->P, a->n);
-    if (is_wide(a->n, kWideFrom)) {  // rows of more than kWideFrom elements: one workgroup per particle (sx_wide.hip)
-        if (int rc = wide_pso_launch(a, s)) return rc;
-    } else {
-        PlanArg plan;
-        if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-        const bool plain = a->constraints == 0 && a->pending_restart == nullptr;
-        pso_kernel_t kern = a->rng == SX_RNG_PHILOX ? pick_kernel<SX_RNG_PHILOX>(a->fun_id, a->n, plain)
-                                                     : pick_kernel<SX_RNG_HOST>(a->fun_id, a->n, plain);
-        hipLaunchKernelGGL(kern, dim3(g.blocks), dim3(g.threads), g.lds, s, *a, plan, (double *)nullptr, (int64_t)0);
-        SX_LAUNCH_CHECK();
-    }
-    if (finalize)
-        return sx_select_finalize(a->part_f, a->part_i, g.blocks, a->pbest, a->pbest, a->ld, a->n, a->gbest, a->state,
-                                  a->maxiter, a->xtol, a->ftol, stream);
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    if (int rc = enqueue_pso_generation(q, a, nullptr)) return rc;
+    return finalize ? enqueue_pso_finalize(q, a) : 0;
 }
 
 extern "C" int sx_pso_radius(const sx_pso_args *a, double *part_r, void *stream) {
     if (int rc = check_args(a)) return rc;
     SX_REQUIRE(part_r != nullptr, "sx_pso_radius: null scratch");
-    const Geometry g = geometry(a->P, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL(pso_radius_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, part_r))
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    return enqueue_pso_radius(q, a, part_r);
 }
 
 extern "C" int sx_pso_restart_select(const sx_pso_args *a, const double *part_r, double delta, double gamma,
                                      uint64_t *out3, void *stream) {
     if (int rc = check_args(a)) return rc;
     SX_REQUIRE(part_r && out3, "sx_pso_restart_select: null pointer");
-    const Geometry g = geometry(a->P, a->n);
-    hipLaunchKernelGGL(pso_restart_select_kernel, dim3(1), dim3(kSelThreads), 0, (hipStream_t)stream, *a,
-                       (const double *)a->pbestfit, part_r, 1, a->P, (int64_t)g.blocks, a->P, delta, gamma,
-                       (unsigned long long *)out3);
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    return enqueue_restart_select(q, a, part_r, delta, gamma, out3);
 }
 
 // Sharded swarm: `gathered` = (world, P_local + npart) doubles, row r = rank r's [pbestfit | partial radii]
@@ -1107,54 +1134,18 @@ extern "C" int sx_pso_restart_apply(const sx_pso_args *a, const uint64_t *sel3, 
     SX_REQUIRE((sel3 != nullptr) != (host_rows != nullptr), "sx_pso_restart_apply: give sel3 OR host rows");
     SX_REQUIRE(host_rows == nullptr || (host_x != nullptr && host_count >= 0), "sx_pso_restart_apply: host rows");
     SX_REQUIRE(a->lower && a->upper, "sx_pso_restart_apply: bounds missing");
-    const int64_t slots = host_rows ? host_count : a->P;
-    if (slots == 0) return 0;
-    const int rpb = 4;
-    hipLaunchKernelGGL(pso_restart_apply_kernel, dim3((unsigned)((slots + rpb - 1) / rpb)), dim3(rpb * kWave), 0,
-                       (hipStream_t)stream, *a, (const unsigned long long *)sel3, host_rows, host_x, host_count);
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    return enqueue_restart_apply(q, a, sel3, host_rows, host_x, host_count);
 }
 
 // ---------------------------------------------------------------------------
 // hipGraph of `ngen` generations (single GPU, Philox draws): per generation the generation kernel, the
-// best/termination kernel and -- CPSO (part_r != NULL) -- the three restart kernels, all reading the
+// best/termination kernel and -- CPSO (part_r != NULL) -- the restart kernels, all reading the
 // generation counter and the done flag from the device, so one instantiated graph is replayed.
 // ---------------------------------------------------------------------------
-namespace {
-int add_kernel_node(hipGraph_t graph, hipGraphNode_t *prev, void *func, dim3 grid, dim3 block, unsigned lds,
-                    void **kargs) {
-    hipKernelNodeParams kp = {};
-    kp.func = func;
-    kp.gridDim = grid;
-    kp.blockDim = block;
-    kp.sharedMemBytes = lds;
-    kp.kernelParams = kargs;
-    kp.extra = nullptr;
-    hipGraphNode_t node;
-    SX_HIP(hipGraphAddKernelNode(&node, graph, *prev ? prev : nullptr, *prev ? 1 : 0, &kp));
-    *prev = node;
-    return 0;
-}
-
-bool fused_radius_off() {  // (read when a graph is created, so that one process can build both forms)
-    const char *e = getenv("SX_CPSO_FUSED_RADIUS");
-    return e != nullptr && e[0] == '0';
-}
-template <int LPR>
-void *radius_kernel_ptr() {
-    return (void *)pso_radius_kernel<LPR>;
-}
-template <int LPR>
-void *post_kernel_ptr() {
-    return (void *)cpso_post_kernel<LPR>;
-}
-}  // namespace
-
-namespace sx {
-int add_finalize_node(hipGraph_t graph, hipGraphNode_t *prev, const double *part_f, const int64_t *part_i,
-                      int64_t npart, const double *rows0, const double *rows1, int64_t ld, int n, double *gbest,
-                      sx_state *state, int maxiter, double xtol, double ftol);
+static bool env_is(const char *name, char c) {  // (read when a graph is created, so that one process can build every form)
+    const char *e = getenv(name);
+    return e != nullptr && e[0] == c;
 }
 
 extern "C" int sx_pso_graph_create(const sx_pso_args *a, int ngen, double *part_r, double delta, double gamma,
@@ -1164,98 +1155,44 @@ extern "C" int sx_pso_graph_create(const sx_pso_args *a, int ngen, double *part_
     SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_pso_graph_create: graphs need in-kernel (Philox) draws");
     SX_REQUIRE((part_r == nullptr) == (sel3 == nullptr), "sx_pso_graph_create: restart needs part_r AND sel3");
     SX_REQUIRE(part_r == nullptr || (a->lower && a->upper), "sx_pso_graph_create: bounds missing");
-    PlanArg plan = {};
-    const bool wide = is_wide(a->n, kWideFrom);
-    if (!wide && make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const Geometry g = geometry(a->P, a->n);
-    sx_graph *gr = new sx_graph();
-    SX_HIP(hipGraphCreate(&gr->graph, 0));
+    const bool restart = part_r != nullptr;  // CPSO
+    const size_t npart = geometry(a->P, a->n).blocks;
+    GraphBuild gb;
+    if (int rc = gb.begin()) return rc;
+    Enqueue &q = gb.sink();
     // CPSO with whole-batch rows: two launches per generation (generation kernel with its radius by-product, cpso_post_kernel)
-    // instead of four -- C3b 51.7 -> 46.9 us per generation (profiles/r4_cpso_fused_radius.txt).  The graph owns the scratch (npart partial radii).
+    // instead of four -- C3b 51.7 -> 46.9 us per generation (profiles/r4_cpso_fused_radius.txt).  The graph owns the scratch.
     // SX_CPSO_FUSED_RADIUS=0: best / termination, the radius pass over X and the selection as launches of their own.
-    const bool fused_radius = part_r != nullptr && a->n == 4 * lanes_per_row(a->n) && a->n <= kPostDxThreads &&
-                              !fused_radius_off();
-    double *part_rold = nullptr;
-    if (fused_radius) {
-        // (npart per-workgroup maxima, then P per-row radii against the old best: what the rare exact branch looks at first)
-        // ... and 2 + 64 + 64 words for the post kernel's helper workgroups (their word, their maxima, their tags)
-        SX_HIP(hipMalloc(&gr->scratch, ((size_t)g.blocks + (size_t)a->P + 130) * sizeof(double)));
-        SX_HIP(hipMemset(gr->scratch, 0, ((size_t)g.blocks + (size_t)a->P + 130) * sizeof(double)));
-        part_rold = (double *)gr->scratch;
-    }
-    sx_pso_args args = *a;
-    args.pending_restart = nullptr;
+    const bool fused_radius = restart && a->n == 4 * lanes_per_row(a->n) && a->n <= kPostDxThreads &&
+                              !env_is("SX_CPSO_FUSED_RADIUS", '0');
+    // (npart per-workgroup maxima, then P per-row radii against the old best: what the rare exact branch looks at first)
+    // ... and 2 + 64 + 64 words for the post kernel's helper workgroups (their word, their maxima, their tags)
+    if (fused_radius)
+        if (int rc = gb.alloc_scratch((npart + (size_t)a->P + 130) * sizeof(double))) return rc;
+    double *part_rold = fused_radius ? (double *)gb.scratch() : nullptr;
+    // (tests: 1 = every generation through the exact branch, 2 = through its all-rows form)
+    const int force_exact = getenv("SX_CPSO_FORCE_EXACT") == nullptr ? 0 : (env_is("SX_CPSO_FORCE_EXACT", '2') ? 2 : 1);
+    // (SX_CPSO_HELPERS=0: the one-workgroup launch of rounds 4-5)
+    const bool post_helpers = fused_radius && !env_is("SX_CPSO_HELPERS", '0') && a->P < (int64_t)0x7fffffff;
+    unsigned long long *hscratch = post_helpers ? (unsigned long long *)(part_rold + npart + (size_t)a->P) : nullptr;
     // generations 2..ngen of the graph carry out the previous generation's restart themselves (sx_pso_args.pending_restart);
     // the last one is followed by the apply kernel, so the state a replay leaves behind is complete
-    sx_pso_args args_inline = args;
+    sx_pso_args args = *a, args_inline = *a;
+    args.pending_restart = nullptr;
     args_inline.pending_restart = sel3;
-    double *no_rows_buf = nullptr;
-    int64_t npart_gen = fused_radius ? (int64_t)g.blocks : 0;
-    void *gen_args[] = {&args, &plan, fused_radius ? &part_rold : &no_rows_buf, &npart_gen};
-    void *gen_args_inline[] = {&args_inline, &plan, fused_radius ? &part_rold : &no_rows_buf, &npart_gen};
-    // restart kernels' arguments
-    const double *fit = a->pbestfit;
-    const double *pr = part_r;
-    int one = 1;
-    int64_t P = a->P, npart = g.blocks;
-    unsigned long long *sel = (unsigned long long *)sel3;
-    void *rad_args[] = {&args, &part_r};
-    void *sel_args[] = {&args, &fit, &pr, &one, &P, &npart, &P, &delta, &gamma, &sel};
-    const double *cpart_f = a->part_f, *cpart_rold = part_rold;
-    const int64_t *cpart_i = a->part_i;
-    double xtol = a->xtol;
-    // (tests: 1 = every generation through the exact branch, 2 = through its all-rows form)
-    const char *fe = getenv("SX_CPSO_FORCE_EXACT");
-    int force_exact = fe == nullptr ? 0 : (fe[0] == '2' ? 2 : 1);
-    // (SX_CPSO_HELPERS=0: the one-workgroup launch of rounds 4-5)
-    const char *he = getenv("SX_CPSO_HELPERS");
-    const bool post_helpers = fused_radius && !(he != nullptr && he[0] == '0') && a->P < (int64_t)0x7fffffff;
-    unsigned long long *hscratch = post_helpers ? (unsigned long long *)((double *)gr->scratch + (size_t)g.blocks + (size_t)a->P) : nullptr;
-    void *post_args[] = {&args, &cpart_f, &cpart_i, &cpart_rold, &npart, &xtol, &delta, &gamma, &sel, &force_exact, &hscratch};
-    void *post_fn = nullptr;
-    SX_DISPATCH_LPR(a->n, post_fn = post_kernel_ptr<LPR>())
-    const int64_t *no_rows = nullptr;
-    const double *no_x = nullptr;
-    int64_t zero = 0;
-    const unsigned long long *csel = sel;
-    void *app_args[] = {&args, &csel, &no_rows, &no_x, &zero};
-    void *radius_fn = nullptr;
-    SX_DISPATCH_LPR(a->n, radius_fn = radius_kernel_ptr<LPR>())
-    hipGraphNode_t prev = nullptr;
     for (int i = 0; i < ngen; ++i) {
-        const bool inl = part_r != nullptr && i > 0;  // CPSO: generations 2.. carry out the restart decided before them
-        // (the first generation of a fused-radius graph takes the general kernel too: the plain one leaves no radius)
-        if (wide) {
-            if (int rc = wide_pso_add_node(gr->graph, &prev, inl ? &args_inline : &args)) return rc;
-        } else if (int rc = add_kernel_node(gr->graph, &prev,
-                                            (void *)pick_kernel<SX_RNG_PHILOX>(a->fun_id, a->n,
-                                                                               a->constraints == 0 && !inl && !fused_radius),
-                                            dim3(g.blocks), dim3(g.threads), (unsigned)g.lds,
-                                            inl ? gen_args_inline : gen_args))
-            return rc;
+        if (int rc = enqueue_pso_generation(q, restart && i > 0 ? &args_inline : &args, part_rold)) return rc;
         if (fused_radius) {
-            if (int rc = add_kernel_node(gr->graph, &prev, post_fn, dim3(post_helpers ? kPostHelpers + 1 : 1), dim3(kSelThreads), 0,
-                                         post_args))
-                return rc;
-        } else if (int rc = add_finalize_node(gr->graph, &prev, a->part_f, a->part_i, g.blocks, a->pbest, a->pbest, a->ld,
-                                              a->n, a->gbest, a->state, a->maxiter, a->xtol, a->ftol))
-            return rc;
-        if (part_r != nullptr) {
-            if (!fused_radius) {
-                if (int rc = add_kernel_node(gr->graph, &prev, radius_fn, dim3(g.blocks), dim3(g.threads), 0, rad_args))
-                    return rc;
-                if (int rc = add_kernel_node(gr->graph, &prev, (void *)pso_restart_select_kernel, dim3(1),
-                                             dim3(kSelThreads), 0, sel_args))
-                    return rc;
+            if (int rc = enqueue_cpso_post(q, &args, part_rold, delta, gamma, sel3, force_exact, hscratch)) return rc;
+        } else {
+            if (int rc = enqueue_pso_finalize(q, &args)) return rc;
+            if (restart) {
+                if (int rc = enqueue_pso_radius(q, &args, part_r)) return rc;
+                if (int rc = enqueue_restart_select(q, &args, part_r, delta, gamma, sel3)) return rc;
             }
-            const int rpb = 4;
-            if (i == ngen - 1)
-                if (int rc = add_kernel_node(gr->graph, &prev, (void *)pso_restart_apply_kernel,
-                                             dim3((unsigned)((a->P + rpb - 1) / rpb)), dim3(rpb * kWave), 0, app_args))
-                    return rc;
         }
+        if (restart && i == ngen - 1)
+            if (int rc = enqueue_restart_apply(q, &args, sel3, nullptr, nullptr, 0)) return rc;
     }
-    SX_HIP(hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0));
-    *out = gr;
-    return 0;
+    return gb.finish(out);
 }

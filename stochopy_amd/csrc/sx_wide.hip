@@ -974,8 +974,14 @@ __global__ __launch_bounds__(T) void wide_vd_candidates_kernel(const sx_vd_args 
         if (tk_out != nullptr) tk_out[row] = tk;
     }
 }
+typedef void (*wide_eval_kernel_t)(const double *, int64_t, int, int64_t, const double *, const double *, double *,
+                                   const int32_t *, double *, int64_t *, const int, const double *, double *);
+typedef void (*wide_de_kernel_t)(const sx_de_args, const int32_t *, const int);
+typedef void (*wide_pso_kernel_t)(const sx_pso_args, const int32_t *, const int);
+typedef void (*wide_vd_kernel_t)(const sx_vd_args, const int64_t, const int64_t, double *, double *, double *, double *,
+                                 const int32_t *, const int);
 template <template <int> class K>
-void *pick_fun(int fun_id) {
+auto pick_fun(int fun_id) -> decltype(K<SX_FUN_ACKLEY>::ptr()) {
     switch (fun_id) {
         case SX_FUN_ACKLEY: return K<SX_FUN_ACKLEY>::ptr();
         case SX_FUN_GRIEWANK: return K<SX_FUN_GRIEWANK>::ptr();
@@ -988,7 +994,7 @@ void *pick_fun(int fun_id) {
     return nullptr;
 }
 template <template <int> class K>
-void *pick_fun_hot(int fun_id) {  // (specialised forms: the four hot objectives, sx_device.hpp hot_objective)
+wide_de_kernel_t pick_fun_hot(int fun_id) {  // (specialised forms: the four hot objectives, sx_device.hpp hot_objective)
     switch (fun_id) {
         case SX_FUN_ACKLEY: return K<SX_FUN_ACKLEY>::ptr();
         case SX_FUN_RASTRIGIN: return K<SX_FUN_RASTRIGIN>::ptr();
@@ -997,25 +1003,25 @@ void *pick_fun_hot(int fun_id) {  // (specialised forms: the four hot objectives
     }
     return nullptr;
 }
-template <int FUN> struct EvalK { static void *ptr() { return (void *)wide_eval_kernel<FUN, false>; } };
+template <int FUN> struct EvalK { static wide_eval_kernel_t ptr() { return wide_eval_kernel<FUN, false>; } };
 template <int FUN> struct EvalPipeK {
-    static void *ptr() { return (void *)wide_eval_kernel<FUN, light_objective<FUN>()>; }  // (heavy: the plain form again)
+    static wide_eval_kernel_t ptr() { return wide_eval_kernel<FUN, light_objective<FUN>()>; }  // (heavy: the plain form again)
 };
-template <int FUN> struct DePhK { static void *ptr() { return (void *)wide_de_kernel<FUN, SX_RNG_PHILOX>; } };
-template <int FUN> struct DeHoK { static void *ptr() { return (void *)wide_de_kernel<FUN, SX_RNG_HOST>; } };
-template <int FUN> struct DePhBestK { static void *ptr() { return (void *)wide_de_kernel<FUN, SX_RNG_PHILOX, SX_DE_BEST1BIN>; } };
-template <int FUN> struct DePhRandK { static void *ptr() { return (void *)wide_de_kernel<FUN, SX_RNG_PHILOX, SX_DE_RAND1BIN>; } };
-template <int FUN> struct PsoPhK { static void *ptr() { return (void *)wide_pso_kernel<FUN, SX_RNG_PHILOX>; } };
-template <int FUN> struct VdCandK { static void *ptr() { return (void *)wide_vd_candidates_kernel<FUN, kGenThreads>; } };
-template <int FUN> struct PsoHoK { static void *ptr() { return (void *)wide_pso_kernel<FUN, SX_RNG_HOST>; } };
-void *pick_de(const sx_de_args *a) {
+template <int FUN> struct DePhK { static wide_de_kernel_t ptr() { return wide_de_kernel<FUN, SX_RNG_PHILOX>; } };
+template <int FUN> struct DeHoK { static wide_de_kernel_t ptr() { return wide_de_kernel<FUN, SX_RNG_HOST>; } };
+template <int FUN> struct DePhBestK { static wide_de_kernel_t ptr() { return wide_de_kernel<FUN, SX_RNG_PHILOX, SX_DE_BEST1BIN>; } };
+template <int FUN> struct DePhRandK { static wide_de_kernel_t ptr() { return wide_de_kernel<FUN, SX_RNG_PHILOX, SX_DE_RAND1BIN>; } };
+template <int FUN> struct PsoPhK { static wide_pso_kernel_t ptr() { return wide_pso_kernel<FUN, SX_RNG_PHILOX>; } };
+template <int FUN> struct VdCandK { static wide_vd_kernel_t ptr() { return wide_vd_candidates_kernel<FUN, kGenThreads>; } };
+template <int FUN> struct PsoHoK { static wide_pso_kernel_t ptr() { return wide_pso_kernel<FUN, SX_RNG_HOST>; } };
+wide_de_kernel_t pick_de(const sx_de_args *a) {
     const bool ph = a->rng == SX_RNG_PHILOX;  // (host draws: the generation waits for the host's streams anyway)
     const bool hot = hot_objective(a->fun_id);
     if (hot && ph && a->constraints == 0 && a->strategy == SX_DE_BEST1BIN) return pick_fun_hot<DePhBestK>(a->fun_id);
     if (hot && ph && a->constraints == 0 && a->strategy == SX_DE_RAND1BIN) return pick_fun_hot<DePhRandK>(a->fun_id);
     return ph ? pick_fun<DePhK>(a->fun_id) : pick_fun<DeHoK>(a->fun_id);
 }
-void *pick_pso(const sx_pso_args *a) { return a->rng == SX_RNG_PHILOX ? pick_fun<PsoPhK>(a->fun_id) : pick_fun<PsoHoK>(a->fun_id); }
+wide_pso_kernel_t pick_pso(const sx_pso_args *a) { return a->rng == SX_RNG_PHILOX ? pick_fun<PsoPhK>(a->fun_id) : pick_fun<PsoHoK>(a->fun_id); }
 
 std::mutex g_attr_mutex;
 std::map<std::pair<int, void *>, size_t> g_attr;  // (device, kernel) -> the dynamic LDS limit it has been given
@@ -1051,37 +1057,23 @@ int wide_warm_plan(int fun_id, int n, hipStream_t s) {
 }
 }  // namespace sx
 namespace {
-struct GenLaunch {
-    void *fn;
+struct GenLaunch {  // what a generation kernel of wide rows is launched with, next to its own arguments
     const int32_t *plan;
     int chunk_leaves;
     size_t lds;
 };
-int gen_launch_for(void *fn, int fun_id, int n, hipStream_t s, GenLaunch *out) {
+// (s: null while a graph is built -- the plan is uploaded outside the graph)
+template <class KernelPtr>
+int gen_launch_for(KernelPtr fn, int fun_id, int n, hipStream_t s, GenLaunch *out) {
     SX_REQUIRE(fn != nullptr, "wide rows: unknown objective");
     SX_REQUIRE(n <= kWideMaxDim, "dimension above the wide-row limit (n <= 262144)");
     CachedPlan cp;
     if (int rc = get_plan(sx_fun_terms(fun_id, n), s, &cp)) return rc;
     const bool resident = wide_resident(n);
-    out->fn = fn;
     out->plan = cp.dev;
     out->chunk_leaves = resident ? cp.nleaf : 0;  // 0: streamed, chunk by chunk (the plan's chunk table)
     out->lds = wide_lds_bytes(n, resident);
-    return allow_lds(fn, out->lds);
-}
-
-int add_node(hipGraph_t graph, hipGraphNode_t *prev, void *func, dim3 grid, dim3 block, unsigned lds, void **kargs) {
-    hipKernelNodeParams kp = {};
-    kp.func = func;
-    kp.gridDim = grid;
-    kp.blockDim = block;
-    kp.sharedMemBytes = lds;
-    kp.kernelParams = kargs;
-    kp.extra = nullptr;
-    hipGraphNode_t node;
-    SX_HIP(hipGraphAddKernelNode(&node, graph, *prev ? prev : nullptr, *prev ? 1 : 0, &kp));
-    *prev = node;
-    return 0;
+    return allow_lds((void *)fn, out->lds);
 }
 
 }  // namespace
@@ -1091,42 +1083,28 @@ namespace sx {
 int wide_eval(int fun_id, const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd, double *f,
               double *part_f, int64_t *part_i, int clip, const double *pen_v, double *pen_out, hipStream_t s) {
     SX_REQUIRE(n <= kWideMaxDim, "dimension above the wide-row limit (n <= 262144)");
-    void *fn = n > SX_WIDE_EVAL_PIPE_FROM ? pick_fun<EvalPipeK>(fun_id) : pick_fun<EvalK>(fun_id);
+    const wide_eval_kernel_t fn = n > SX_WIDE_EVAL_PIPE_FROM ? pick_fun<EvalPipeK>(fun_id) : pick_fun<EvalK>(fun_id);
     SX_REQUIRE(fn != nullptr, "wide rows: unknown objective");
     CachedPlan cp;
     if (int rc = get_plan(sx_fun_terms(fun_id, n), s, &cp)) return rc;
     const size_t lds = wide_lds_bytes(n, false);
-    if (int rc = allow_lds(fn, lds)) return rc;
-    const int32_t *plan = cp.dev;
-    void *kargs[] = {&X, &P, &n, &ldx, &xm, &xstd, &f, &plan, &part_f, &part_i, &clip, &pen_v, &pen_out};
-    SX_HIP(hipLaunchKernel(fn, dim3((unsigned)P), dim3(kEvalThreads), kargs, lds, s));
-    return 0;
+    if (int rc = allow_lds((void *)fn, lds)) return rc;
+    return Enqueue(s).kernel(fn, dim3((unsigned)P), dim3(kEvalThreads), lds, X, P, n, ldx, xm, xstd, f, cp.dev, part_f, part_i,
+                             clip, pen_v, pen_out);
 }
 
-int wide_de_launch(const sx_de_args *a, hipStream_t s) {
+int wide_de_enqueue(Enqueue &q, const sx_de_args *a) {
+    const wide_de_kernel_t fn = pick_de(a);
     GenLaunch g;
-    if (int rc = gen_launch_for(pick_de(a), a->fun_id, a->n, s, &g)) return rc;
-    sx_de_args args = *a;
-    void *kargs[] = {&args, &g.plan, &g.chunk_leaves};
-    SX_HIP(hipLaunchKernel(g.fn, dim3((unsigned)a->P), dim3(kGenThreads), kargs, g.lds, s));
-    return 0;
+    if (int rc = gen_launch_for(fn, a->fun_id, a->n, q.stream(), &g)) return rc;
+    return q.kernel(fn, dim3((unsigned)a->P), dim3(kGenThreads), g.lds, *a, g.plan, g.chunk_leaves);
 }
 
-int wide_de_add_node(hipGraph_t graph, hipGraphNode_t *prev, const sx_de_args *a) {
+int wide_pso_enqueue(Enqueue &q, const sx_pso_args *a) {
+    const wide_pso_kernel_t fn = pick_pso(a);
     GenLaunch g;
-    if (int rc = gen_launch_for(pick_de(a), a->fun_id, a->n, nullptr, &g)) return rc;
-    sx_de_args args = *a;
-    void *kargs[] = {&args, &g.plan, &g.chunk_leaves};
-    return add_node(graph, prev, g.fn, dim3((unsigned)a->P), dim3(kGenThreads), (unsigned)g.lds, kargs);
-}
-
-int wide_pso_launch(const sx_pso_args *a, hipStream_t s) {
-    GenLaunch g;
-    if (int rc = gen_launch_for(pick_pso(a), a->fun_id, a->n, s, &g)) return rc;
-    sx_pso_args args = *a;
-    void *kargs[] = {&args, &g.plan, &g.chunk_leaves};
-    SX_HIP(hipLaunchKernel(g.fn, dim3((unsigned)a->P), dim3(kGenThreads), kargs, g.lds, s));
-    return 0;
+    if (int rc = gen_launch_for(fn, a->fun_id, a->n, q.stream(), &g)) return rc;
+    return q.kernel(fn, dim3((unsigned)a->P), dim3(kGenThreads), g.lds, *a, g.plan, g.chunk_leaves);
 }
 
 int wide_vd_candidates(const sx_vd_args *a, int64_t gen, int64_t row0, int64_t rows, double *ary_out, double *arx_out,
@@ -1134,25 +1112,15 @@ int wide_vd_candidates(const sx_vd_args *a, int64_t gen, int64_t row0, int64_t r
     // (Workgroups of 256 or 384 threads -- four per CU instead of three, a generation of ~1000 candidates resident at once --
     // were measured and lose: 273 / 270 against 255-260 us per generation at n = 16 384, P = 1024; 658 / 620 against 570 at
     // n = 65 536, P = 512: profiles/r5_vd_threads.txt.)
+    const wide_vd_kernel_t fn = pick_fun<VdCandK>(a->fun_id);
     GenLaunch g;
-    if (int rc = gen_launch_for(pick_fun<VdCandK>(a->fun_id), a->fun_id, a->n, s, &g)) return rc;
+    if (int rc = gen_launch_for(fn, a->fun_id, a->n, s, &g)) return rc;
     // Always STREAMED (z parked in the y row): a resident row's 128 KB of LDS leave ONE workgroup per CU, and the generator's
     // arithmetic (Philox, log, sincos: ~65 us of VALU time chip-wide per 1 024 x 16 384 candidates), the row stores and
     // the objective of a candidate then run one after the other -- 216 us per generation at n = 16 384, P = 1 024 against
     // the streamed form's figure in profiles/r5_vd_wide.txt.  (z in registers -- 8 items per thread -- spills: 256 VGPRs + 1.5 KB.)
-    g.chunk_leaves = 0, g.lds = wide_lds_bytes(a->n, false);
-    sx_vd_args args = *a;
-    void *kargs[] = {&args, &gen, &row0, &ary_out, &arx_out, &fit_out, &tk_out, &g.plan, &g.chunk_leaves};
-    SX_HIP(hipLaunchKernel(g.fn, dim3((unsigned)rows), dim3(kGenThreads), kargs, g.lds, s));
-    return 0;
-}
-
-int wide_pso_add_node(hipGraph_t graph, hipGraphNode_t *prev, const sx_pso_args *a) {
-    GenLaunch g;
-    if (int rc = gen_launch_for(pick_pso(a), a->fun_id, a->n, nullptr, &g)) return rc;
-    sx_pso_args args = *a;
-    void *kargs[] = {&args, &g.plan, &g.chunk_leaves};
-    return add_node(graph, prev, g.fn, dim3((unsigned)a->P), dim3(kGenThreads), (unsigned)g.lds, kargs);
+    return Enqueue(s).kernel(fn, dim3((unsigned)rows), dim3(kGenThreads), wide_lds_bytes(a->n, false), *a, gen, row0, ary_out,
+                             arx_out, fit_out, tk_out, g.plan, 0);
 }
 
 }  // namespace sx

@@ -8,6 +8,7 @@
 
 #include "../../include/stochopy_hip.h"
 #include "sx_device.hpp"
+#include "sx_enqueue.hpp"
 
 namespace sx {
 
@@ -20,12 +21,11 @@ inline int de_wide_from(const sx_de_args *a) { return run_wide_from(a->wide_from
 int wide_eval(int fun_id, const double *X, int64_t P, int n, int64_t ldx, const double *xm, const double *xstd, double *f,
               double *part_f, int64_t *part_i, int clip, const double *pen_v, double *pen_out, hipStream_t s);
 int wide_warm_plan(int fun_id, int n, hipStream_t s);
-int wide_de_launch(const sx_de_args *a, hipStream_t s);
-int wide_de_add_node(hipGraph_t graph, hipGraphNode_t *prev, const sx_de_args *a);
-int wide_pso_launch(const sx_pso_args *a, hipStream_t s);
+// one generation of wide rows, launched or appended as a graph node (sx_enqueue.hpp)
+int wide_de_enqueue(Enqueue &q, const sx_de_args *a);
+int wide_pso_enqueue(Enqueue &q, const sx_pso_args *a);
 // VD-CMA candidates [row0, row0 + rows) of generation `gen`: normals, steps y, candidates x, objective, t_k (tk_out may be NULL)
 int wide_vd_candidates(const sx_vd_args *a, int64_t gen, int64_t row0, int64_t rows, double *ary_out, double *arx_out,
                        double *fit_out, double *tk_out, hipStream_t s);
-int wide_pso_add_node(hipGraph_t graph, hipGraphNode_t *prev, const sx_pso_args *a);
 
 }  // namespace sx

@@ -295,6 +295,15 @@ class _DeRun(_PopulationRun):
                        "sx_de_chain_graph_create")
         return g
 
+    def _two_kernel_graph(self):
+        """The graph of GRAPH_CHUNK generations of the two-kernel path, instantiated the first time it is asked for."""
+        if self._graph is None:
+            g = C.c_void_p()
+            _lib.check(self.ctx.L.sx_de_graph_create(C.byref(self.args), self.GRAPH_CHUNK, C.byref(g)),
+                       "sx_de_graph_create")
+            self._graph = g
+        return self._graph
+
     def prepare_graphs(self):
         """Instantiate the hipGraph(s) up front (otherwise the first full chunk pays for it)."""
         if self.world is not None and not self.chain:
@@ -302,11 +311,8 @@ class _DeRun(_PopulationRun):
         if self.chain:
             self._chain_graph(0, self.GRAPH_CHUNK)  # chunk sizes are even: replays always start at parity 0 unless eager launches intervene
             self._chain_graph(0, self.TAIL_CHUNK)
-        elif self.rng == "philox" and self._graph is None:
-            g = C.c_void_p()
-            _lib.check(self.ctx.L.sx_de_graph_create(C.byref(self.args), self.GRAPH_CHUNK, C.byref(g)),
-                       "sx_de_graph_create")
-            self._graph = g
+        elif self.rng == "philox":
+            self._two_kernel_graph()
 
     @staticmethod
     def plan_chain(ngen, launches, seen, chunk, tail):
@@ -394,12 +400,7 @@ class _DeRun(_PopulationRun):
                 self._sharded_generation()
             return
         while ngen >= self.GRAPH_CHUNK:
-            if self._graph is None:
-                g = C.c_void_p()
-                _lib.check(ctx.L.sx_de_graph_create(C.byref(self.args), self.GRAPH_CHUNK, C.byref(g)),
-                           "sx_de_graph_create")
-                self._graph = g
-            _lib.check(ctx.L.sx_graph_launch(self._graph, ctx.stream_ptr), "sx_graph_launch")
+            _lib.check(ctx.L.sx_graph_launch(self._two_kernel_graph(), ctx.stream_ptr), "sx_graph_launch")
             ngen -= self.GRAPH_CHUNK
         for _ in range(ngen):
             _lib.check(ctx.L.sx_de_generation(C.byref(self.args), 1, ctx.stream_ptr), "sx_de_generation")
