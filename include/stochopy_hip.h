@@ -59,7 +59,7 @@ const char *sx_last_error(void);
 int sx_device_count(void);
 /* sizeof(sx_state / sx_de_args / sx_pso_args / sx_xchg_args) as compiled: lets a binding check its struct
  * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args,
- * 8 DE-runs args; -1 otherwise) */
+ * 8 DE-runs args, 9 PSO-runs args; -1 otherwise) */
 int sx_struct_size(int which);
 
 /* ------------------------------------------------------------------------- *
@@ -736,6 +736,56 @@ int sx_de_runs_launch(const sx_de_runs_args *a, void *stream);
 /* bytes of LDS one run of popsize P and row length n needs (host only, no device touched); negative when that is more
  * than a workgroup may declare (160 KiB on gfx950), n > sx_wide_from() or the shape is invalid */
 int64_t sx_de_runs_lds_bytes(int64_t P, int n);
+
+/* ------------------------------------------------------------------------- *
+ * PSO / CPSO, many independent runs in one launch (csrc/sx_pso_runs.hip).
+ * replaces: R calls of cpso/_cpso.py:182-321 (`cpso`: initial swarm :215-247, the generation loop :257-307) with the
+ *           mutation (:324-329), pso_sync (:332-361), NoConstraint / Shrink (cpso/_constraints.py:4-10, 44-53),
+ *           selection_sync (_common.py:123-130), the termination ladder (_common.py:131-158) and the competitive restart
+ *           (:405-426) -- everything a run of `updating="deferred"` does, for R runs that differ in their Philox key (and,
+ *           optionally, their x0) only.  pso/_pso.py:9-122 is the same with competitivity None (gamma = 0 here).
+ * One workgroup carries one run from its initial swarm to its termination: X, V, pbest, pbestfit and a copy of the best
+ * row live in the workgroup's LDS (a swarm too large for that keeps V, which only its owning lanes touch, in `vwork`), a generation is separated from the next by two workgroup barriers (CPSO: up to two
+ * more), and nothing is exchanged between runs.  Run r draws with keys[r]: its counters are those of the single-run
+ * kernels (row = the row within the run), so run r IS the run sx_pso_generation / sx_pso_graph_create perform with that
+ * key -- same swarm, same best, same nit and status, bit for bit.  In-kernel draws only.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_pso_runs_args {
+    const uint32_t *keys;   /* DEVICE (R,2) Philox key (key0, key1) of run r                               */
+    const double *lower;    /* DEVICE (n)                                                                  */
+    const double *upper;    /* DEVICE (n)                                                                  */
+    const double *x0;       /* DEVICE initial swarms, (P,n) each, run stride x0_stride; NULL: run r draws the
+                               Latin hypercube of sx_philox_lhs with keys[r] (_common.py:109-120)          */
+    double *xs;             /* DEVICE (R,n) OUT best position of run r                                     */
+    double *funs;           /* DEVICE (R)   OUT its value                                                  */
+    int64_t *nits;          /* DEVICE (R)   OUT generations (the reference's `it`; the initial one counts) */
+    int32_t *statuses;      /* DEVICE (R)   OUT -1 / 0 / 1 (_common.py:134-158)                            */
+    double *xfinal;         /* DEVICE (R,P,n) OUT final positions of run r, or NULL                        */
+    double *pbest_final;    /* DEVICE (R,P,n) OUT final personal bests, or NULL                            */
+    double *pbestfit_final; /* DEVICE (R,P)   OUT their values, or NULL                                    */
+    double *vwork;          /* DEVICE sx_pso_runs_workspace_bytes(R, P, n) bytes: the velocities of a swarm whose
+                               X, V and pbest do not fit the LDS together; may be NULL when that is 0      */
+    int64_t R;
+    int64_t P;
+    int64_t x0_stride;      /* 0 (one swarm shared by all runs) or P*n                                     */
+    int32_t n;              /* 1 ... sx_wide_from()                                                        */
+    int32_t fun_id;
+    int32_t constraints;    /* 0 none, 1 Shrink                                                            */
+    int32_t maxiter;        /* <= 1: one generation is still run (cpso/_cpso.py:257-260)                   */
+    double w, c1, c2;       /* inertia, cognitivity, sociability                                           */
+    double gamma;           /* competitivity; 0: plain PSO, no restart                                     */
+    double delta;           /* log(1 + 0.003 P) / max(0.2, log(0.01 maxiter)) (cpso/_cpso.py:215-216)      */
+    double xtol, ftol;
+} sx_pso_runs_args;
+
+/* all R runs, from the initial swarm to each run's own termination: one launch, R workgroups */
+int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream);
+/* bytes of LDS one run of popsize P and row length n needs (host only, no device touched); negative when that is more
+ * than a workgroup may declare (160 KiB on gfx950), n > sx_wide_from() or the shape is invalid */
+int64_t sx_pso_runs_lds_bytes(int64_t P, int n);
+/* bytes of device workspace (sx_pso_runs_args.vwork) R such runs need: 0 when X, V and pbest fit the LDS together, else
+ * R*P*n*8 for the velocities (host only); negative when sx_pso_runs_lds_bytes(P, n) is */
+int64_t sx_pso_runs_workspace_bytes(int64_t R, int64_t P, int n);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,16 @@ class SxDeRunsArgs(C.Structure):
     ]
 
 
+class SxPsoRunsArgs(C.Structure):
+    _fields_ = [
+        ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("xs", vp), ("funs", vp), ("nits", vp), ("statuses", vp),
+        ("xfinal", vp), ("pbest_final", vp), ("pbestfit_final", vp), ("vwork", vp),
+        ("R", i64), ("P", i64), ("x0_stride", i64),
+        ("n", i32), ("fun_id", i32), ("constraints", i32), ("maxiter", i32),
+        ("w", f64), ("c1", f64), ("c2", f64), ("gamma", f64), ("delta", f64), ("xtol", f64), ("ftol", f64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/stochopy_hip.h declares
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
@@ -217,6 +227,9 @@ PROTOTYPES = {
     "sx_sample_gradient": (C.c_int, [C.c_int, vp, i64, C.c_int, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),
+    "sx_pso_runs_launch": (C.c_int, [C.POINTER(SxPsoRunsArgs), vp]),
+    "sx_pso_runs_lds_bytes": (i64, [i64, C.c_int]),
+    "sx_pso_runs_workspace_bytes": (i64, [i64, i64, C.c_int]),
     "sx_mt_create": (vp, [C.c_uint32]),
     "sx_mt_destroy": (None, [vp]),
     "sx_mt_seed": (None, [vp, C.c_uint32]),
@@ -263,7 +276,7 @@ def lib():
     if handle.sx_abi_version() != 1:
         raise HipLibraryError("ABI version mismatch; rebuild the library")
     for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs,
-                                    SxSampleArgs, SxDeRunsArgs)):
+                                    SxSampleArgs, SxDeRunsArgs, SxPsoRunsArgs)):
         if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
             raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
                                   f"{C.sizeof(mirror)}; rebuild the library")

@@ -35,6 +35,7 @@ extern "C" int sx_struct_size(int which) {
         case 6: return (int)sizeof(sx_vd_args);
         case 7: return (int)sizeof(sx_sample_args);
         case 8: return (int)sizeof(sx_de_runs_args);
+        case 9: return (int)sizeof(sx_pso_runs_args);
     }
     return -1;
 }

@@ -827,7 +827,7 @@ __device__ __forceinline__ void row_reduce_long(const double *U, int l, double &
 }
 
 // Order of objective values for the best row, np.argmin's: any NaN (whatever its sign bit) before everything, then <,
-// then the lower index.  (Ranking -- np.argsort -- puts NaN last instead: key_less in sx_cma_loop.hip, sort_key in sx_pso.hip.)
+// then the lower index.  (Ranking -- np.argsort -- puts NaN last instead: key_less in sx_cma_loop.hip, sort_key below.)
 __device__ __forceinline__ bool is_nan(double v) { return v != v; }
 // a strictly before b, indices aside
 __device__ __forceinline__ bool best_before(double a, double b) { return a < b || (is_nan(a) && !is_nan(b)); }
@@ -837,6 +837,12 @@ __device__ __forceinline__ bool best_tie(double a, double b) { return a == b || 
 __device__ __forceinline__ double best_min(double a, double b) { return best_before(b, a) ? b : a; }
 // NaN-propagating maximum (np.max): the swarm radius
 __device__ __forceinline__ double max_nan(double a, double b) { return (b > a || is_nan(b)) ? b : a; }
+// order-preserving map double -> uint64 (larger double <=> larger key); every NaN, whatever its sign bit, is the largest
+// key, as np.argsort puts NaN last (the restart re-seeds NaN particles first, cpso/_cpso.py:420)
+__device__ __forceinline__ unsigned long long sort_key(double f) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(f);
+    return is_nan(f) ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 
 // lexicographic (value, index) minimum in that order = np.argmin's first-minimum rule, first NaN included
 __device__ __forceinline__ void argmin_combine(double &f, int64_t &i, double f2, int64_t i2) {

@@ -25,13 +25,6 @@ using namespace sx;
 
 namespace {
 
-// order-preserving map double -> uint64 (larger double <=> larger key); every NaN, whatever its sign bit, is the largest
-// key, as np.argsort puts NaN last (the restart re-seeds NaN particles first, cpso/_cpso.py:420)
-__device__ __forceinline__ unsigned long long sort_key(double f) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(f);
-    return is_nan(f) ? ~0ull : (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
 // FULL: n == 4 * LPR (64, 128 or 256 -- BASELINE config 3): the row length is a compile-time constant, a row is exactly
 // one batch, and every bound check and loop over the row folds away.
 // PLAIN (round 5: with or without FULL): constraints=None and no restart pending (plain PSO, or the first generation of a CPSO graph): neither

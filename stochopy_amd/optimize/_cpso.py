@@ -11,12 +11,13 @@ best/termination kernel; the competitive restart (:405-426) is three small kerne
 """
 import ctypes as C
 import os
+import warnings
 
 import numpy as np
 
 from .. import _device, _lib, _rng
 from . import _common
-from ._helpers import register
+from ._helpers import OptimizeResult, register
 from ._population import _PopulationRun
 
 __all__ = ["minimize"]
@@ -47,6 +48,7 @@ def minimize(
     strict_updating=None,
     host_workers=None,
     host_backend=None,
+    runs=None,
 ):
     """Minimize an objective function using Competitive PSO on MI355X.
 
@@ -57,15 +59,29 @@ def minimize(
     (``workers=1``, a factory objective; same seed, same result as the reference's default call); otherwise the
     run is deferred like with a parallel backend of the reference (cpso/_cpso.py:147-150), with a warning.
     ``updating="deferred"`` is the throughput mode; ``strict_updating=False`` forces it silently.
+    ``runs=R`` (R >= 2) performs R independent runs with these settings in ONE kernel launch, one workgroup per run
+    (csrc/sx_pso_runs.hip): run r is, bit for bit, the run of ``seed + r`` (``seed`` an integer) or of ``seed[r]``
+    (a sequence of R integers) with ``rng="philox", updating="deferred"``; ``x0`` is ``None``, one ``(P, n)`` swarm
+    for all runs or ``(R, P, n)``, and is not modified.  The result describes the best run (``np.argmin`` over the runs'
+    ``fun``; ``run`` is its index, ``nfev`` the sum over all runs) and carries ``xs``, ``funs``, ``nits``, ``statuses``
+    per run.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
+    ``sx_wide_from()`` elements and a swarm that fits one workgroup's LDS (``sx_pso_runs_lds_bytes``).
     """
+    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
+        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
+    batched_runs = runs is not None and runs > 1
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
-    if x0 is not None:
+    if batched_runs and x0 is not None and np.ndim(x0) == 3:  # a swarm per run
+        if np.shape(x0) != (runs, popsize, len(bounds)):
+            raise ValueError(f"x0 of shape {np.shape(x0)} with runs={runs}: expected ({popsize}, {len(bounds)}) for all runs "
+                             f"or ({runs}, {popsize}, {len(bounds)})")
+    elif x0 is not None:
         if np.ndim(x0) != 2 or np.shape(x0)[1] != len(bounds):
             raise ValueError()
     if popsize < 2:
         raise ValueError()
-    if x0 is not None and len(x0) != popsize:
+    if x0 is not None and np.ndim(x0) == 2 and len(x0) != popsize:
         raise ValueError()
     if not 0.0 <= inertia <= 1.0:
         raise ValueError()
@@ -83,12 +99,86 @@ def minimize(
         raise ValueError()
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
+    if batched_runs:
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(inertia),
+                              float(cognitivity), float(sociability), competitivity, constraints, float(xtol), float(ftol),
+                              seed, rng, updating, strict_updating, workers, return_all, callback)
     workers = _common.resolve_workers(workers, fun_id)
     run = _PsoRun(fun_id, lower, upper, x0, int(maxiter), int(popsize), float(inertia), float(cognitivity),
                   float(sociability), competitivity, constraints, float(xtol), float(ftol), bool(return_all),
                   float(verbosity), callback, rng, seed, workers,
                   immediate=_common.resolve_updating(updating, strict_updating, workers, fun_id, len(lower)))
     return run.result()
+
+
+def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competitivity, constraints, xtol, ftol, seed, rng,
+                   updating, strict_updating, workers, return_all, callback):
+    """``runs=R``: R independent deferred-updating runs, one workgroup each, one launch (csrc/sx_pso_runs.hip).  Everything
+    that can be refused is refused before the device is touched."""
+    n = len(lower)
+    if rng != "philox":
+        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
+    if not isinstance(fun_id, int):
+        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
+                         "(factory.batched and plain callables run between kernels)")
+    if workers not in (None, 1):
+        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
+    if callback is not None:
+        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
+    if return_all:
+        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
+    if updating == "immediate":
+        if strict_updating:
+            raise ValueError('strict_updating=True: updating="immediate" is an ordered sweep; runs > 1 are whole generations in '
+                             'parallel (updating="deferred")')
+        if strict_updating is None:
+            warnings.warn('stochopy_amd: updating="immediate" is an ordered sweep of ONE run; runs > 1 use "deferred" updating, '
+                          "as a parallel backend of the reference does (cpso/_cpso.py:147-150).", RuntimeWarning, stacklevel=3)
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        seeds = [int(seed) + r for r in range(R)]
+    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
+        seeds = [int(s) for s in seed]
+    else:
+        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+    if n > _lib.wide_from():
+        raise ValueError(f"runs > 1 serves rows of up to {_lib.wide_from()} elements (n = {n})")
+    lds = int(_lib.lib().sx_pso_runs_lds_bytes(P, n))
+    if lds < 0:
+        raise ValueError(f"runs > 1 keeps a run's swarm (X and pbest at the least) in one workgroup's LDS: popsize {P} x {n} "
+                         "variables is more than its 160 KiB hold")
+    gamma = float(competitivity) if competitivity else 0.0
+    # cpso/_cpso.py:215-216 (depends on maxiter and the swarm's size)
+    delta = float(np.log(1.0 + 0.003 * P) / np.max((0.2, np.log(0.01 * maxiter)))) if gamma else 0.0
+
+    ctx = _device.Context()
+    t = _device.torch()
+    with t.cuda.stream(ctx.stream):
+        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
+        d_keys = ctx.upload_async(keys.view(np.int32))
+        d_bounds = ctx.upload_async(np.concatenate([lower, upper]))
+        d_x0 = None if x0 is None else ctx.upload(np.array(x0, dtype=np.float64))
+        xs, funs = ctx.empty((R, n)), ctx.empty((R,))
+        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
+        a = _lib.SxPsoRunsArgs()
+        a.keys, a.lower, a.upper = d_keys.data_ptr(), d_bounds[:n].data_ptr(), d_bounds[n:].data_ptr()
+        a.x0 = None if d_x0 is None else d_x0.data_ptr()
+        a.xs, a.funs, a.nits, a.statuses = xs.data_ptr(), funs.data_ptr(), nits.data_ptr(), statuses.data_ptr()
+        a.xfinal = a.pbest_final = a.pbestfit_final = None
+        # (a swarm whose X, V and pbest do not fit the LDS together keeps its velocities here)
+        vwork = int(ctx.L.sx_pso_runs_workspace_bytes(R, P, n))
+        d_vwork = ctx.empty((vwork // 8,)) if vwork else None
+        a.vwork = None if d_vwork is None else d_vwork.data_ptr()
+        a.R, a.P, a.x0_stride = R, P, (P * n if d_x0 is not None and d_x0.dim() == 3 else 0)
+        a.n, a.fun_id = n, fun_id
+        a.constraints, a.maxiter = (1 if constraints == "Shrink" else 0), maxiter
+        a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = w, c1, c2, gamma, delta, xtol, ftol
+        _lib.check(ctx.L.sx_pso_runs_launch(C.byref(a), ctx.stream_ptr), "sx_pso_runs_launch")
+        xs, funs, nits, statuses = xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy()
+    best = int(np.argmin(funs))
+    status = int(statuses[best])
+    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
+                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
+                          xs=xs, funs=funs, nits=nits, statuses=statuses)
 
 
 class _PsoRun(_PopulationRun):

@@ -33,11 +33,13 @@ def minimize(
     strict_updating=None,
     host_workers=None,
     host_backend=None,
+    runs=None,
 ):
-    """Minimize an objective function using PSO on MI355X (reference pso/_pso.py:9-29)."""
+    """Minimize an objective function using PSO on MI355X (reference pso/_pso.py:9-29).  ``runs=R``: R independent runs in
+    one kernel launch, see ``_cpso.minimize``."""
     return _cpso.minimize(fun, bounds, x0, args, maxiter, popsize, inertia, cognitivity, sociability, None, seed,
                           xtol, ftol, constraints, updating, workers, backend, return_all, verbosity, callback, rng,
-                          strict_updating, host_workers, host_backend)
+                          strict_updating, host_workers, host_backend, runs)
 
 
 register("pso", minimize)
