@@ -59,7 +59,7 @@ const char *sx_last_error(void);
 int sx_device_count(void);
 /* sizeof(sx_state / sx_de_args / sx_pso_args / sx_xchg_args) as compiled: lets a binding check its struct
  * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args,
- * 8 DE-runs args, 9 PSO-runs args; -1 otherwise) */
+ * 8 DE-runs args, 9 PSO-runs args, 10 CMA-runs args; -1 otherwise) */
 int sx_struct_size(int which);
 
 /* ------------------------------------------------------------------------- *
@@ -786,6 +786,60 @@ int64_t sx_pso_runs_lds_bytes(int64_t P, int n);
 /* bytes of device workspace (sx_pso_runs_args.vwork) R such runs need: 0 when X, V and pbest fit the LDS together, else
  * R*P*n*8 for the velocities (host only); negative when sx_pso_runs_lds_bytes(P, n) is */
 int64_t sx_pso_runs_workspace_bytes(int64_t R, int64_t P, int n);
+
+/* ------------------------------------------------------------------------- *
+ * CMA-ES, many independent runs in one launch (csrc/sx_cma_runs.hip).
+ * replaces: R calls of cmaes/_cmaes.py:143-357 (`cmaes`: sampling :232-237, ranking and recombination :272-277, the
+ *           evolution paths :280-287, the covariance update :290-295, the step size :298, the decomposition :301-309)
+ *           and of `converge` (:360-434, the ten ordered stopping rules incl. the reads of the zero-initialised
+ *           history) -- everything a run without constraints does, for R runs that differ in their Philox key and
+ *           their initial mean only.
+ * One workgroup carries one run from its first generation to its own stopping rule: C, B, D, both paths, the mean and
+ * the candidates live in the workgroup's LDS, the steps of a generation are separated by workgroup barriers where the
+ * single run (sx_cmaes_generation) has kernel launches, the decomposition is the one-workgroup Jacobi solver of
+ * csrc/sx_eigh_small.hpp (the body of sx_eigh for n <= 32) with the same finish (eigenvalues M_jj / |v_j|^2, ascending
+ * order, largest component of every eigenvector positive), and nothing is exchanged between runs.  Run r draws with
+ * keys[r]: the counters of sx_cmaes_normals (row = the row within the run), so run r samples what the single run of
+ * that key samples.  n <= 32 (the one-workgroup solver's range); no Penalize, no history.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_cma_runs_args {
+    const uint32_t *keys;   /* DEVICE (R,2) Philox key (key0, key1) of run r                               */
+    const double *xmean0;   /* DEVICE (R,n) initial mean of run r, standardised ((x0 - xm) / xstd)         */
+    const double *xm;       /* DEVICE (n) (upper + lower) / 2                         (cmaes/_cmaes.py:167-173) */
+    const double *xstd;     /* DEVICE (n) (upper - lower) / 2                                              */
+    const double *w;        /* DEVICE (mu) recombination weights                              (:184-196)   */
+    double *work;           /* DEVICE sx_cma_runs_workspace_bytes(R, maxiter) bytes: the runs' best-fitness histories;
+                               zeroed by sx_cma_runs_launch                                                */
+    double *xs;             /* DEVICE (R,n) OUT best candidate of run r's last generation, un-standardised */
+    double *funs;           /* DEVICE (R)   OUT its value                                                  */
+    int64_t *nits;          /* DEVICE (R)   OUT generations                                                */
+    int32_t *statuses;      /* DEVICE (R)   OUT the reference's status (-8 .. 1)                           */
+    int64_t *nfevs;         /* DEVICE (R)   OUT nit * P, or NULL                                           */
+    double *sigmas;         /* DEVICE (R)   OUT final step size, or NULL                                   */
+    double *xmeans;         /* DEVICE (R,n) OUT final mean (standardised), or NULL                         */
+    int64_t R;
+    int64_t P;
+    int32_t n;              /* 1 ... 32                                                                    */
+    int32_t mu;
+    int32_t fun_id;
+    int32_t maxiter;        /* >= 1                                                                        */
+    int32_t ilim;           /* int(10 + 30 n / P): window of stopping rule -5                    (:399)    */
+    int32_t pad;
+    double mueff, cc, cs, c1, cmu, damps, chind;  /* strategy constants                       (:184-205)   */
+    double sigma;           /* initial step size                                                           */
+    double insigma;         /* the step size rules -6 and -8 compare with (the single run: the same value) */
+    double xtol, ftol;
+} sx_cma_runs_args;
+
+/* all R runs, from the first generation to each run's own stopping rule: one launch, R workgroups */
+int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream);
+/* bytes of LDS one run of popsize P and dimension n needs (host only, no device touched; the layout is written out at
+ * the head of csrc/sx_cma_runs.hip); negative when that is more than a workgroup may declare (160 KiB on gfx950),
+ * n < 1, n > 32 or P < 2 */
+int64_t sx_cma_runs_lds_bytes(int64_t P, int n);
+/* bytes of device workspace (sx_cma_runs_args.work) R runs of at most maxiter generations need: R*maxiter*8 (host
+ * only); negative for R < 1 or maxiter < 1 */
+int64_t sx_cma_runs_workspace_bytes(int64_t R, int64_t maxiter);
 
 #ifdef __cplusplus
 }

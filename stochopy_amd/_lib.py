@@ -148,6 +148,17 @@ class SxPsoRunsArgs(C.Structure):
     ]
 
 
+class SxCmaRunsArgs(C.Structure):
+    _fields_ = [
+        ("keys", vp), ("xmean0", vp), ("xm", vp), ("xstd", vp), ("w", vp), ("work", vp), ("xs", vp), ("funs", vp), ("nits", vp),
+        ("statuses", vp), ("nfevs", vp), ("sigmas", vp), ("xmeans", vp),
+        ("R", i64), ("P", i64),
+        ("n", i32), ("mu", i32), ("fun_id", i32), ("maxiter", i32), ("ilim", i32), ("pad", i32),
+        ("mueff", f64), ("cc", f64), ("cs", f64), ("c1", f64), ("cmu", f64), ("damps", f64), ("chind", f64),
+        ("sigma", f64), ("insigma", f64), ("xtol", f64), ("ftol", f64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/stochopy_hip.h declares
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
@@ -230,6 +241,9 @@ PROTOTYPES = {
     "sx_pso_runs_launch": (C.c_int, [C.POINTER(SxPsoRunsArgs), vp]),
     "sx_pso_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_pso_runs_workspace_bytes": (i64, [i64, i64, C.c_int]),
+    "sx_cma_runs_launch": (C.c_int, [C.POINTER(SxCmaRunsArgs), vp]),
+    "sx_cma_runs_lds_bytes": (i64, [i64, C.c_int]),
+    "sx_cma_runs_workspace_bytes": (i64, [i64, i64]),
     "sx_mt_create": (vp, [C.c_uint32]),
     "sx_mt_destroy": (None, [vp]),
     "sx_mt_seed": (None, [vp, C.c_uint32]),
@@ -276,7 +290,7 @@ def lib():
     if handle.sx_abi_version() != 1:
         raise HipLibraryError("ABI version mismatch; rebuild the library")
     for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs,
-                                    SxSampleArgs, SxDeRunsArgs, SxPsoRunsArgs)):
+                                    SxSampleArgs, SxDeRunsArgs, SxPsoRunsArgs, SxCmaRunsArgs)):
         if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
             raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
                                   f"{C.sizeof(mirror)}; rebuild the library")

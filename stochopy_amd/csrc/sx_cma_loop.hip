@@ -44,9 +44,6 @@ constexpr int kPathThreads = 1024;
 
 static_assert(sizeof(sx_cma_state) == 128, "sx_cma_state is 128 bytes");
 
-// numpy sorts NaN last: a < b in that order
-__device__ __forceinline__ bool key_less(double a, double b) { return a < b || (b != b && a == a); }
-
 // order = argsort(fit) (ties: lower index first); best row / value and the history entry of the generation.
 // A wavefront ranks four elements: the keys pass through LDS 4096 at a time, lane l looks at keys l, l + 64, ... and the
 // number of keys in front of an element is the population count of the wave's votes (one comparison per 64 keys and

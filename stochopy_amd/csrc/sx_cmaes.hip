@@ -405,14 +405,10 @@ __global__ __launch_bounds__(256) void cma_normals_kernel(double *__restrict__ Z
         const uint32_t k = (uint32_t)j / lpr, l = (uint32_t)j & (lpr - 1u);
         const int e0 = (int)(2u * k * lpr + l), e1 = e0 + (int)lpr;
         if (e0 >= n) continue;
-        const U4 w = philox4x32_10(k * lpr + l, grow, gen, kPurposeCmaNormal, k0, k1);
-        const double d0 = u53(w.x, w.y), d1 = u53(w.z, w.w);
-        const double rad = sqrt(-2.0 * log(1.0 - d0));
-        const double ang = 6.283185307179586 * d1;
-        double sn, cs;
-        sincos(ang, &sn, &cs);
-        zr[e0] = rad * cs;
-        if (e1 < n) zr[e1] = rad * sn;
+        double z0, z1;
+        cma_normal_pair(k * lpr + l, grow, gen, k0, k1, z0, z1);
+        zr[e0] = z0;
+        if (e1 < n) zr[e1] = z1;
     }
 }
 

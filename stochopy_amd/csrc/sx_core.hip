@@ -36,6 +36,7 @@ extern "C" int sx_struct_size(int which) {
         case 7: return (int)sizeof(sx_sample_args);
         case 8: return (int)sizeof(sx_de_runs_args);
         case 9: return (int)sizeof(sx_pso_runs_args);
+        case 10: return (int)sizeof(sx_cma_runs_args);
     }
     return -1;
 }

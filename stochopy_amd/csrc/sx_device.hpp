@@ -194,6 +194,20 @@ __device__ __forceinline__ double philox_u53(int e, int lpr, uint32_t row, uint3
 // ---------------------------------------------------------------------------
 constexpr double kTwoPi = 6.283185307179586;  // 2.0 * np.pi
 
+// The two N(0,1) values of ONE call of generation `gen`, row `grow`, slot `slot` (oracle/streams.py PhiloxStream.cma_normals):
+// Box-Muller on the call's two 53-bit uniforms, z0 the cosine half, z1 the sine half.  Shared by cma_normals_kernel
+// (sx_cmaes.hip) and the resident CMA-ES runs (sx_cma_runs.hip): one function, so the same bits.
+__device__ __forceinline__ void cma_normal_pair(uint32_t slot, uint32_t grow, uint32_t gen, uint32_t k0, uint32_t k1, double &z0,
+                                                double &z1) {
+    const U4 w = philox4x32_10(slot, grow, gen, kPurposeCmaNormal, k0, k1);
+    const double d0 = u53(w.x, w.y), d1 = u53(w.z, w.w);
+    const double rad = sqrt(-2.0 * log(1.0 - d0));
+    const double ang = 6.283185307179586 * d1;
+    double sn, cs;
+    sincos(ang, &sn, &cs);
+    z0 = rad * cs, z1 = rad * sn;
+}
+
 // cos(t) for the arguments the benchmark functions produce (t = 2 pi x, |t| < 1e6; anything else goes to the library).
 // Round 4: the library's cosine is ~75 instructions behind a magnitude branch, and the four calls of a lane (four elements
 // per batch) run one after the other; this form is ~30 straight-line operations -- Cody-Waite reduction by pi/2 in three
@@ -827,7 +841,7 @@ __device__ __forceinline__ void row_reduce_long(const double *U, int l, double &
 }
 
 // Order of objective values for the best row, np.argmin's: any NaN (whatever its sign bit) before everything, then <,
-// then the lower index.  (Ranking -- np.argsort -- puts NaN last instead: key_less in sx_cma_loop.hip, sort_key below.)
+// then the lower index.  (Ranking -- np.argsort -- puts NaN last instead: key_less and sort_key below.)
 __device__ __forceinline__ bool is_nan(double v) { return v != v; }
 // a strictly before b, indices aside
 __device__ __forceinline__ bool best_before(double a, double b) { return a < b || (is_nan(a) && !is_nan(b)); }
@@ -837,6 +851,8 @@ __device__ __forceinline__ bool best_tie(double a, double b) { return a == b || 
 __device__ __forceinline__ double best_min(double a, double b) { return best_before(b, a) ? b : a; }
 // NaN-propagating maximum (np.max): the swarm radius
 __device__ __forceinline__ double max_nan(double a, double b) { return (b > a || is_nan(b)) ? b : a; }
+// a before b in np.argsort's order, indices aside: numpy sorts NaN last (the CMA-ES ranking: sx_cma_loop.hip, sx_cma_runs.hip)
+__device__ __forceinline__ bool key_less(double a, double b) { return a < b || (b != b && a == a); }
 // order-preserving map double -> uint64 (larger double <=> larger key); every NaN, whatever its sign bit, is the largest
 // key, as np.argsort puts NaN last (the restart re-seeds NaN particles first, cpso/_cpso.py:420)
 __device__ __forceinline__ unsigned long long sort_key(double f) {

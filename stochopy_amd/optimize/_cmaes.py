@@ -13,15 +13,16 @@ candidates, the objective and the weighted squared excess run in one device kern
 (``sx_cmaes_eval_penalized``); the scalar bookkeeping of the boundary weights stays on the host.
 """
 
+import ctypes as C
 import os
 import warnings
 
 import numpy as np
 
-from .. import _device, _lib
+from .. import _device, _lib, _rng
 from ..linalg import Eigh
 from . import _common, _evolution
-from ._helpers import register
+from ._helpers import OptimizeResult, register
 
 __all__ = ["minimize"]
 
@@ -53,6 +54,7 @@ def minimize(
     eigh=None,
     host_workers=None,
     host_backend=None,
+    runs=None,
 ):
     """Minimize an objective function using CMA-ES on MI355X (reference cmaes/_cmaes.py:12-30).
 
@@ -73,12 +75,33 @@ def minimize(
     replicated on the hosts, Philox normals are keyed by the global row), one all-gather per generation
     returns all candidates and fitness values to every rank, and the O(n^2)/O(n^3) model update is replicated.
     Same result as ``workers=1`` on every rank.
+
+    ``runs=R`` (R >= 2) performs R independent runs with these settings in ONE kernel launch, one workgroup per run
+    (csrc/sx_cma_runs.hip): run r is the run of ``seed + r`` (``seed`` an integer) or of ``seed[r]`` (a sequence of R
+    integers) with ``rng="philox"`` -- the same draws, the same arithmetic up to the order of its sums; ``x0`` is ``None``
+    (every run draws its initial mean as the single run of its seed does), one ``(n,)`` point for all runs or ``(R, n)``.
+    The result describes the best run (``np.argmin`` over the runs' ``fun``; ``run`` is its index, ``nfev`` the sum over all
+    runs) and carries ``xs``, ``funs``, ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  Needs
+    ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, ``constraints=None``, the device
+    eigensolver, ``ndim <= 32`` and a population that fits one workgroup's LDS (``sx_cma_runs_lds_bytes``).
     """
+    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
+        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
+    batched_runs = runs is not None and runs > 1
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
-    _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
+    if batched_runs and x0 is not None and np.ndim(x0) == 2:  # a point per run
+        if np.shape(x0) != (runs, len(bounds)):
+            raise ValueError(f"x0 of shape {np.shape(x0)} with runs={runs}: expected ({len(bounds)},) for all runs or "
+                             f"({runs}, {len(bounds)})")
+        _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback)
+    else:
+        _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
+    if batched_runs:
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(sigma), float(muperc),
+                              float(xtol), float(ftol), seed, rng, constraints, eigh, workers, return_all, callback)
     workers = _common.resolve_workers(workers, fun_id)
     if len(lower) > _lib.NARROW_DIM:
         # the one method that keeps a dimension cap: an n x n covariance, its eigenvectors and an O(n^3) decomposition per
@@ -111,6 +134,85 @@ def _strategy_constants(n, P, muperc):
     damps = 1.0 + 2.0 * max(0.0, np.sqrt((mueff - 1.0) / (n + 1.0)) - 1.0) + cs
     chind = np.sqrt(n) * (1.0 - 1.0 / (4.0 * n) + 1.0 / (21.0 * n**2))
     return mu, w, mueff, cc, cs, c1, cmu, damps, chind
+
+
+RUNS_MAX_DIM = 32  # runs > 1: the range of the one-workgroup eigensolver (csrc/sx_eigh.hip kSmallPathMax)
+
+
+def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, seed, rng, constraints, eigh, workers,
+                   return_all, callback):
+    """``runs=R``: R independent runs, one workgroup each, one launch (csrc/sx_cma_runs.hip).  Everything that can be
+    refused is refused before the device is touched."""
+    n = len(lower)
+    if rng != "philox":
+        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
+    if not isinstance(fun_id, int):
+        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
+                         "(factory.batched and plain callables run between kernels)")
+    if workers not in (None, 1):
+        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
+    if callback is not None:
+        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
+    if return_all:
+        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
+    if constraints is not None:
+        raise ValueError(f"runs > 1 serves constraints=None (constraints={constraints!r}: the boundary-weight bookkeeping "
+                         "is not part of the run's kernel)")
+    if eigh is not None and (callable(eigh) or eigh != "device"):
+        raise ValueError('runs > 1 decomposes C inside the run\'s kernel: eigh=None or "device" '
+                         f"(eigh={'a callable' if callable(eigh) else repr(eigh)})")
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        seeds = [int(seed) + r for r in range(R)]
+    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
+        seeds = [int(s) for s in seed]
+    else:
+        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+    if maxiter < 1:
+        raise ValueError(f"runs > 1 needs maxiter >= 1 (maxiter={maxiter})")
+    if n > RUNS_MAX_DIM:
+        raise ValueError(f"runs > 1 keeps a run's covariance and its eigendecomposition in one workgroup: ndim <= "
+                         f"{RUNS_MAX_DIM} (ndim = {n}, popsize = {P})")
+    lds = int(_lib.lib().sx_cma_runs_lds_bytes(P, n)) if P >= 1 else -1
+    mu = int(muperc * P)
+    if lds < 0 or mu < 1:
+        raise ValueError(f"runs > 1 keeps a run's model and candidates in one workgroup's LDS: popsize {P} x {n} variables "
+                         f"(mu = {mu}) needs 2 <= popsize, mu >= 1 and at most 160 KiB")
+    mu, w, *constants = _strategy_constants(n, P, muperc)
+    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
+    if x0 is None:
+        # the initial mean of the single run of each seed: its private legacy stream (_rng.make_init_stream), n uniforms
+        xmean0 = np.array([np.random.RandomState(s & 0xFFFFFFFF).uniform(-1.0, 1.0, n) for s in seeds])
+    else:
+        xmean0 = np.ascontiguousarray(np.broadcast_to((np.asarray(x0, dtype=np.float64) - xm) / xstd, (R, n)))
+
+    ctx = _device.Context()
+    t = _device.torch()
+    with t.cuda.stream(ctx.stream):
+        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
+        d_keys = ctx.upload_async(keys.view(np.int32))
+        d_xmean0, d_std, d_w = ctx.upload(xmean0), ctx.upload_async(np.concatenate([xm, xstd])), ctx.upload(w)
+        d_work = ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,))
+        xs, funs, sigmas = ctx.empty((R, n)), ctx.empty((R,)), ctx.empty((R,))
+        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
+        a = _lib.SxCmaRunsArgs()
+        a.keys, a.xmean0, a.xm, a.xstd, a.w = (d_keys.data_ptr(), d_xmean0.data_ptr(), d_std[:n].data_ptr(),
+                                               d_std[n:].data_ptr(), d_w.data_ptr())
+        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
+                                                    statuses.data_ptr())
+        a.nfevs, a.sigmas, a.xmeans = None, sigmas.data_ptr(), None
+        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, fun_id, maxiter
+        a.ilim = int(10.0 + 30.0 * n / P)
+        a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
+        a.sigma = a.insigma = sigma
+        a.xtol, a.ftol = xtol, ftol
+        _lib.check(ctx.L.sx_cma_runs_launch(C.byref(a), ctx.stream_ptr), "sx_cma_runs_launch")
+        xs, funs, nits, statuses, sigmas = (xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy(),
+                                            sigmas.cpu().numpy())
+    best = int(np.argmin(funs))
+    status = int(statuses[best])
+    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
+                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
+                          xs=xs, funs=funs, nits=nits, statuses=statuses, sigmas=sigmas)
 
 
 COLD_SWEEPS = 40   # launched for a decomposition started from the identity (n=512: 11-13 are carried out)

@@ -50,11 +50,16 @@ def minimize(
     rng=None,
     host_workers=None,
     host_backend=None,
+    runs=None,
 ):
-    """Minimize an objective function using VD-CMA on MI355X (reference vdcma/_vdcma.py:12-30)."""
+    """Minimize an objective function using VD-CMA on MI355X (reference vdcma/_vdcma.py:12-30).  ``runs`` is the option of
+    ``de`` / ``pso`` / ``cpso`` / ``cmaes``; here only ``None`` or 1 (the single run) is served."""
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
+    if runs is not None and not (isinstance(runs, (int, np.integer)) and not isinstance(runs, bool) and runs == 1):
+        raise ValueError(f"runs={runs!r}: method='vdcma' has no batched-runs kernel (runs > 1 is served by de, pso, cpso and "
+                         "cmaes with ndim <= 32)")
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
     workers = _common.resolve_workers(workers, fun_id)
