@@ -1,5 +1,10 @@
-"""The batched-runs CMA-ES kernel (csrc/sx_cma_runs.hip), the host side of its C ABI restated for the tests: the LDS layout
-the kernel's header comment documents, in bytes.  A plain helper module (imported, not collected)."""
+"""The batched-runs CMA-ES kernel (csrc/sx_cma_runs.hip) through its C ABI, restated for the tests: the LDS layout the kernel's
+header comment documents, in bytes; launch_runs, one sx_cma_runs_launch filled as optimize/_cmaes.py _minimize_runs fills it
+but with real nfevs / sigmas / xmeans buffers (optimize.minimize(runs=R) passes nfevs = xmeans = NULL); generation_one, a plain
+numpy reference of a run's first generation; and the shapes the generation-1 tests share.  A plain helper module (imported,
+not collected)."""
+
+import numpy as np
 
 LDS_LIMIT = 160 * 1024
 MAX_DIM = 32
@@ -34,3 +39,154 @@ def largest_popsize(lib, n):
         else:
             hi = mid
     return lo
+
+
+def jacobi_doubles(n):
+    """The solver's storage that shares the region U with the candidates: S[2], W[2] of [M2][M2 + 1], c[M2], s[M2]."""
+    m2 = solver_size(n)
+    return 4 * m2 * (m2 + 1) + 2 * m2
+
+
+def crossover_popsize(n):
+    """The largest P whose candidates P * (n + 8) are NOT larger than the Jacobi storage: P and P + 1 are the two sides."""
+    return jacobi_doubles(n) // (n + 8)
+
+
+def largest_popsize_below(limit_bytes, n):
+    """The largest P with lds_bytes(P, n) <= limit_bytes (lds_bytes never decreases in P)."""
+    P = 2
+    while lds_bytes(P + 1, n) <= limit_bytes:
+        P += 1
+    return P
+
+
+def standardise(lower, upper):
+    """xm, xstd of cmaes/_cmaes.py:164-165."""
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    return 0.5 * (upper + lower), 0.5 * (upper - lower)
+
+
+def launch_runs(objective, lower, upper, P, seeds, x0=None, maxiter=100, sigma=0.1, muperc=0.5, xtol=1e-8, ftol=1e-8):
+    """One sx_cma_runs_launch of len(seeds) runs of `objective` (a factory name), its arguments filled exactly as
+    optimize/_cmaes.py _minimize_runs fills them, but with real nfevs / sigmas / xmeans buffers.  lower / upper: one value per
+    dimension.  x0: None (every run draws its initial mean as the single run of its seed does), (n,) or (R, n), in the caller's
+    coordinates.  Returns xs (R, n), funs (R,), nits (R,), statuses (R,), nfevs (R,), sigmas (R,), xmeans (R, n; standardised)."""
+    import ctypes as C
+
+    from stochopy_amd import _device, _lib, _rng
+    from stochopy_amd.optimize._cmaes import _strategy_constants
+
+    seeds = [int(s) for s in seeds]
+    R = len(seeds)
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    n = len(lower)
+    mu, w, *constants = _strategy_constants(n, P, muperc)
+    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
+    if x0 is None:
+        xmean0 = np.array([np.random.RandomState(s & 0xFFFFFFFF).uniform(-1.0, 1.0, n) for s in seeds])
+    else:
+        xmean0 = np.ascontiguousarray(np.broadcast_to((np.asarray(x0, dtype=np.float64) - xm) / xstd, (R, n)))
+
+    ctx = _device.Context()
+    t = _device.torch()
+    with t.cuda.stream(ctx.stream):
+        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
+        d_keys = ctx.upload_async(keys.view(np.int32))
+        d_xmean0, d_std, d_w = ctx.upload(xmean0), ctx.upload_async(np.concatenate([xm, xstd])), ctx.upload(w)
+        d_work = ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,))
+        # filled with values no run produces: an element the kernel does not write cannot pass for a result
+        fill = -12345.678
+        xs, funs, sigmas, xmeans = [t.full(shape, fill, dtype=t.float64, device=ctx.device) for shape in ((R, n), (R,), (R,), (R, n))]
+        nits, nfevs = [t.full((R,), -7, dtype=t.int64, device=ctx.device) for _ in range(2)]
+        statuses = t.full((R,), 77, dtype=t.int32, device=ctx.device)
+        a = _lib.SxCmaRunsArgs()
+        a.keys, a.xmean0, a.xm, a.xstd, a.w = (d_keys.data_ptr(), d_xmean0.data_ptr(), d_std[:n].data_ptr(),
+                                               d_std[n:].data_ptr(), d_w.data_ptr())
+        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
+                                                    statuses.data_ptr())
+        a.nfevs, a.sigmas, a.xmeans = nfevs.data_ptr(), sigmas.data_ptr(), xmeans.data_ptr()
+        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, _lib.FUN_IDS[objective], maxiter
+        a.ilim = int(10.0 + 30.0 * n / P)
+        a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
+        a.sigma = a.insigma = sigma
+        a.xtol, a.ftol = xtol, ftol
+        _lib.check(ctx.L.sx_cma_runs_launch(C.byref(a), ctx.stream_ptr), "sx_cma_runs_launch")
+        out = tuple(v.cpu().numpy() for v in (xs, funs, nits, statuses, nfevs, sigmas, xmeans))
+    assert not (out[0] == fill).any() and not (out[6] == fill).any() and not (out[5] == fill).any()
+    assert (out[2] > 0).all() and (out[4] > 0).all() and (out[3] != 77).all()
+    return out
+
+
+def generation_one(objective, lower, upper, P, seed, x0, sigma=0.1, muperc=0.5):
+    """A run with maxiter = 1, plainly: one generation from the identity model (C = B = I, D = 1, ps = 0), so
+    invsqrtC (xmean - xold) is the step itself.  The candidates are formed as the reference forms them (doubles, one product
+    and one sum per element), ranked by numpy's STABLE argsort (lower index first on ties; NaN last), and every sum -- the
+    recombination and |ps|^2 -- is accumulated in np.longdouble.  Returns a dict: arx (P, n), fit, order, xmean (standardised),
+    absum (the sum_k |w_k arx_k| the error bound of xmean is stated in), sigma (after the generation), x (the best row,
+    un-standardised), xparts (|arx xstd| + |xm| of that row: the magnitude its multiply-add works at), fun, nit, nfev, status,
+    mu, sigma_sens (d sigma / d |xmean|: |ps| is kps |xmean - xmean0| / sigma, and sigma' = sigma exp((cs / damps)(|ps| / chind - 1)))."""
+    import oracle
+    from oracle.engine import cma_constants
+
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    n = len(lower)
+    xm, xstd = standardise(lower, upper)
+    k = cma_constants(n, P, muperc)
+    mu, w = k["mu"], k["w"]
+    stream = oracle.PhiloxStream(seed)
+    xmean0 = stream.cma_initial_mean(n) if x0 is None else (np.asarray(x0, dtype=np.float64) - xm) / xstd
+    Z = stream.cma_normals(1, P, n)
+    arx = xmean0 + sigma * Z
+    with np.errstate(over="ignore", invalid="ignore"):
+        fit = oracle.evaluate(objective, arx * xstd + xm)
+    order = np.argsort(fit, kind="stable")
+    L = np.longdouble
+    sel = arx[order[:mu]].astype(L)
+    terms = w.astype(L)[:, None] * sel
+    xmean = terms.sum(axis=0)
+    absum = np.abs(terms).sum(axis=0)
+    ps = L(np.sqrt(k["cs"] * (2.0 - k["cs"]) * k["mueff"])) * (xmean - xmean0.astype(L)) / L(sigma)
+    psn = np.sqrt((ps * ps).sum())
+    sigma1 = L(sigma) * np.exp(L(k["cs"] / k["damps"]) * (psn / L(k["chind"]) - L(1.0)))
+    best = int(order[0])
+    return dict(arx=arx, fit=fit, order=order, xmean=xmean.astype(np.float64), absum=absum.astype(np.float64),
+                sigma=float(sigma1), x=arx[best] * xstd + xm, xparts=np.abs(arx[best] * xstd) + np.abs(xm), fun=float(fit[best]),
+                nit=1, nfev=P, status=-1, mu=mu,
+                sigma_sens=float(sigma1) * k["cs"] / k["damps"] / k["chind"] * np.sqrt(k["cs"] * (2.0 - k["cs"]) * k["mueff"]) / sigma)
+
+
+# ---- the generation-1 cases of tests/test_gpu_cma_runs_edges.py, shared with the host check of the reference
+# (tests/test_cma_runs_host.py).  (n, P): P at the LDS limit of n, each side of 64 KiB of LDS (where the launch raises the
+# kernel's dynamic-LDS attribute), each side of the candidates | Jacobi-storage cross-over of the shared region U.
+GEN1_LITERALS = [(1, 2), (1, 1939), (16, 46), (16, 47), (16, 290), (16, 291), (16, 772), (17, 171), (17, 172), (17, 739),
+                 (32, 107), (32, 108), (32, 135), (32, 136), (32, 432)]
+# sigma = 2^-10: sigma * z is exact, so `xmean0 + sigma * z` is ONE rounding whether or not the device contracts it to an fma;
+# and the few ulp by which the device's log / sincos differ from libm's in z arrive at a candidate scaled by 2^-10 |z| / |arx|.
+GEN1_SIGMA = 2.0 ** -10
+
+
+def gen1_shapes(lib):
+    """The shapes above from the library's own budget (largest_popsize, lds_bytes), not from the literals."""
+    shapes = [(1, 2), (1, largest_popsize(lib, 1))]
+    for n in (16, 17, 32):
+        x, k = crossover_popsize(n), largest_popsize_below(64 * 1024, n)
+        shapes += [(n, x), (n, x + 1)]
+        if n != 17:
+            shapes += [(n, k), (n, k + 1)]
+        shapes.append((n, largest_popsize(lib, n)))
+    return shapes
+
+
+def gen1_box(n):
+    """Per dimension and asymmetric: no centre is 0, no two half-widths are equal."""
+    i = np.arange(n, dtype=np.float64)
+    return -1.0 - i / 7.0, 2.0 + i / 3.0
+
+
+def gen1_x0(n, R):
+    """A point per run, inside the box, in its upper half (standardised mean 0.1 ... 0.9 per element: a candidate is not a
+    difference of nearly equal numbers)."""
+    lower, upper = gen1_box(n)
+    r, i = np.arange(R)[:, None], np.arange(n)[None, :]
+    frac = 0.55 + 0.4 * ((7 * r + 3 * i) % 11) / 11.0
+    return lower + (upper - lower) * frac

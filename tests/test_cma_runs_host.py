@@ -165,3 +165,39 @@ def test_runs_one_or_none_is_the_single_call(sa, monkeypatch):
     for r in (None, 1):
         with pytest.raises(Entered):
             _call(sa, runs=r)
+
+
+# ---- the plain generation-1 reference of tests/test_gpu_cma_runs_edges.py, validated against the oracle (no GPU)
+GEN_CASES = [(obj, n, P) for n, P in _cma_runs_abi.GEN1_LITERALS for obj in ("sphere", "rosenbrock")] + \
+            [("rosenbrock", 5, 12), ("rastrigin", 32, 64), ("sphere", 17, 172), ("sphere", 32, 432)]
+
+
+@pytest.mark.parametrize("cfg", GEN_CASES, ids=lambda c: "%s_n%d_p%d" % c)
+def test_generation_one_reference_agrees_with_the_oracle_probe(cfg):
+    """_cma_runs_abi.generation_one is the oracle's generation 1 wherever the fitness values have no ties (with ties the
+    oracle's default argsort is not the stable one): the same ranking, the mean within the bound of a mu-term sum in doubles
+    (the oracle's np.dot) against the reference's long-double sum, the step size to a few ulp plus what that bound passes
+    on through |ps| (a difference of two means, over sigma), x and
+    fun exactly."""
+    import oracle
+
+    obj, n, P = cfg
+    lower, upper = _cma_runs_abi.gen1_box(n)
+    x0 = _cma_runs_abi.gen1_x0(n, 2)
+    for r, seed in enumerate((700, 701)):
+        ref = _cma_runs_abi.generation_one(obj, lower, upper, P, seed, x0[r], sigma=_cma_runs_abi.GEN1_SIGMA)
+        if len(np.unique(ref["fit"])) < P:
+            assert (obj, n) == ("rosenbrock", 1)  # an empty sum: every row is 0.0 (the one shape with ties)
+            continue
+        seen = []
+        res = oracle.minimize(obj, np.transpose([lower, upper]), x0=x0[r], method="cmaes", rng="philox",
+                              options={"maxiter": 1, "popsize": P, "seed": seed, "sigma": _cma_runs_abi.GEN1_SIGMA,
+                                       "eigh": "canonical", "probe": lambda it, before, after: seen.append(after)})
+        after, = seen
+        assert np.array_equal(after["arx"], ref["arx"]) and np.array_equal(after["arfit"], ref["fit"])
+        assert np.array_equal(after["order"], ref["order"])
+        assert (np.abs(after["xmean"] - ref["xmean"]) <= ref["mu"] * 2.0 ** -53 * ref["absum"]).all()
+        moved = np.linalg.norm(ref["mu"] * 2.0 ** -53 * ref["absum"])  # what the two means may differ by, through |ps|:
+        assert abs(after["sigma"] - ref["sigma"]) <= ref["sigma_sens"] * moved + 8 * np.spacing(ref["sigma"])
+        assert (res.nit, res.nfev, res.status) == (ref["nit"], ref["nfev"], ref["status"]) == (1, P, -1)
+        assert np.array_equal(res.x, ref["x"]) and res.fun == ref["fun"]
