@@ -841,6 +841,63 @@ int64_t sx_cma_runs_lds_bytes(int64_t P, int n);
  * only); negative for R < 1 or maxiter < 1 */
 int64_t sx_cma_runs_workspace_bytes(int64_t R, int64_t maxiter);
 
+/* ------------------------------------------------------------------------- *
+ * VD-CMA, many independent runs in one launch (csrc/sx_vd_runs.hip).
+ * replaces: R calls of vdcma/_vdcma.py:144-425 (`vdcma`: candidates and mean-shift injection :236-248, ranking and mean
+ *           shift :289-295, rank-gap step size :298-306, evolution path and model constants :309-328, moments :331-345
+ *           and :428-444, natural gradient and the update of v and d :348-378 and :447-460) and of `converge`
+ *           (cmaes/_cmaes.py:360-434 without B and D) -- everything a run without constraints does, for R runs that
+ *           differ in their Philox key, their initial mean and their initial direction only.
+ * One workgroup carries one run from its first generation to its own stopping rule: d, v, pc, the mean and the steps'
+ * by-products live in the workgroup's LDS; neither the candidates nor the steps are stored -- a step is formed again from
+ * its normals (a function of the counter) where it is needed --, so the LDS is O(n + P) and runs of hundreds of variables
+ * fit.  Run r draws with keys[r]: the counters of sx_cmaes_normals (row = the row within the run, the injection's normals
+ * "row P"), so run r samples what the single run of that key samples.  6 <= n; no Penalize, no history.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_vd_runs_args {
+    const uint32_t *keys;   /* DEVICE (R,2) Philox key (key0, key1) of run r                               */
+    const double *xmean0;   /* DEVICE (R,n) initial mean of run r, standardised ((x0 - xm) / xstd)         */
+    const double *vvec0;    /* DEVICE (R,n) initial direction v of run r                       (:207)      */
+    const double *xm;       /* DEVICE (n) (upper + lower) / 2                         (cmaes/_cmaes.py:167-173) */
+    const double *xstd;     /* DEVICE (n) (upper - lower) / 2                                              */
+    const double *w;        /* DEVICE (mu) recombination weights                              (:185-191)   */
+    double *work;           /* DEVICE sx_vd_runs_workspace_bytes(R, maxiter) bytes: the runs' best-fitness histories;
+                               zeroed by sx_vd_runs_launch                                                 */
+    double *xs;             /* DEVICE (R,n) OUT best candidate of run r's last generation, un-standardised */
+    double *funs;           /* DEVICE (R)   OUT its value                                                  */
+    int64_t *nits;          /* DEVICE (R)   OUT generations                                                */
+    int32_t *statuses;      /* DEVICE (R)   OUT the reference's status (-8 .. 1)                           */
+    int64_t *nfevs;         /* DEVICE (R)   OUT nit * P, or NULL                                           */
+    double *sigmas;         /* DEVICE (R)   OUT final step size, or NULL                                   */
+    double *xmeans;         /* DEVICE (R,n) OUT final mean (standardised), or NULL                         */
+    double *dvecs;          /* DEVICE (R,n) OUT final d, or NULL                                           */
+    double *vvecs;          /* DEVICE (R,n) OUT final v, or NULL                                           */
+    int64_t R;
+    int64_t P;
+    int32_t n;              /* 6 ... what sx_vd_runs_lds_bytes admits                                      */
+    int32_t mu;
+    int32_t fun_id;
+    int32_t maxiter;        /* >= 1                                                                        */
+    int32_t ilim;           /* int(10 + 30 n / P): window of stopping rule -5                              */
+    int32_t pad;
+    double mueff, cc, c1, cmu, cs, ds, wsum;  /* strategy constants (:185-199); cs = 0.3, ds = sqrt(n), wsum = sum(w) */
+    double sigma;           /* initial step size                                                           */
+    double insigma;         /* the step size rules -6 and -8 compare with (the single run: the same value) */
+    double xtol, ftol;
+} sx_vd_runs_args;
+
+/* all R runs, from the first generation to each run's own stopping rule: one launch, R workgroups */
+int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream);
+/* sizeof(sx_vd_runs_args) as the library was built (sx_struct_size is not extended) */
+int sx_vd_runs_args_bytes(void);
+/* bytes of LDS one run of popsize P and dimension n needs (host only, no device touched; the layout is written out at
+ * the head of csrc/sx_vd_runs.hip); negative when that is more than a workgroup may declare (160 KiB on gfx950),
+ * n < 6, n > sx_wide_from() or P < 2 */
+int64_t sx_vd_runs_lds_bytes(int64_t P, int n);
+/* bytes of device workspace (sx_vd_runs_args.work) R runs of at most maxiter generations need: R*maxiter*8 (host
+ * only); negative for R < 1 or maxiter < 1 */
+int64_t sx_vd_runs_workspace_bytes(int64_t R, int64_t maxiter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,18 @@ class SxCmaRunsArgs(C.Structure):
     ]
 
 
+class SxVdRunsArgs(C.Structure):
+    _fields_ = [
+        ("keys", vp), ("xmean0", vp), ("vvec0", vp), ("xm", vp), ("xstd", vp), ("w", vp), ("work", vp), ("xs", vp),
+        ("funs", vp), ("nits", vp), ("statuses", vp), ("nfevs", vp), ("sigmas", vp), ("xmeans", vp), ("dvecs", vp),
+        ("vvecs", vp),
+        ("R", i64), ("P", i64),
+        ("n", i32), ("mu", i32), ("fun_id", i32), ("maxiter", i32), ("ilim", i32), ("pad", i32),
+        ("mueff", f64), ("cc", f64), ("c1", f64), ("cmu", f64), ("cs", f64), ("ds", f64), ("wsum", f64),
+        ("sigma", f64), ("insigma", f64), ("xtol", f64), ("ftol", f64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/stochopy_hip.h declares
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
@@ -244,6 +256,10 @@ PROTOTYPES = {
     "sx_cma_runs_launch": (C.c_int, [C.POINTER(SxCmaRunsArgs), vp]),
     "sx_cma_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_cma_runs_workspace_bytes": (i64, [i64, i64]),
+    "sx_vd_runs_launch": (C.c_int, [C.POINTER(SxVdRunsArgs), vp]),
+    "sx_vd_runs_args_bytes": (C.c_int, []),
+    "sx_vd_runs_lds_bytes": (i64, [i64, C.c_int]),
+    "sx_vd_runs_workspace_bytes": (i64, [i64, i64]),
     "sx_mt_create": (vp, [C.c_uint32]),
     "sx_mt_destroy": (None, [vp]),
     "sx_mt_seed": (None, [vp, C.c_uint32]),
@@ -294,6 +310,9 @@ def lib():
         if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
             raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
                                   f"{C.sizeof(mirror)}; rebuild the library")
+    if handle.sx_vd_runs_args_bytes() != C.sizeof(SxVdRunsArgs):
+        raise HipLibraryError(f"{LIB_PATH}: sx_vd_runs_args is {handle.sx_vd_runs_args_bytes()} bytes, its mirror "
+                              f"{C.sizeof(SxVdRunsArgs)}; rebuild the library")
     _lib = handle
     return _lib
 

@@ -18,13 +18,14 @@ sharded run forms t_k from the gathered y as (y / d) . vn (csrc/sx_vd_loop.hip v
 differ in the last bits of every t_k, so there the sharded run follows the one-GPU run to rounding, not bit for bit.
 """
 
+import ctypes as C
 import os
 
 import numpy as np
 
-from .. import _device, _lib
+from .. import _device, _lib, _rng
 from . import _common, _evolution
-from ._helpers import register
+from ._helpers import OptimizeResult, register
 
 __all__ = ["minimize"]
 
@@ -52,16 +53,34 @@ def minimize(
     host_backend=None,
     runs=None,
 ):
-    """Minimize an objective function using VD-CMA on MI355X (reference vdcma/_vdcma.py:12-30).  ``runs`` is the option of
-    ``de`` / ``pso`` / ``cpso`` / ``cmaes``; here only ``None`` or 1 (the single run) is served."""
+    """Minimize an objective function using VD-CMA on MI355X (reference vdcma/_vdcma.py:12-30).
+
+    ``runs=R`` (R >= 2) performs R independent runs with these settings in ONE kernel launch, one workgroup per run
+    (csrc/sx_vd_runs.hip): run r is the run of ``seed + r`` (``seed`` an integer) or of ``seed[r]`` (a sequence of R
+    integers) with ``rng="philox"`` -- the same draws, the same arithmetic up to the order of its sums; ``x0`` is ``None``
+    (every run draws its initial mean as the single run of its seed does), one ``(n,)`` point for all runs or ``(R, n)``; the
+    initial direction of run r is drawn right after its mean, as the single run draws it.  The result describes the best run
+    (``np.argmin`` over the runs' ``fun``; ``run`` is its index, ``nfev`` the sum over all runs) and carries ``xs``, ``funs``,
+    ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  Needs ``rng="philox"``, a factory objective, one
+    GPU, no callback, no ``return_all``, ``constraints=None``, ``ndim >= 6`` and a shape that fits one workgroup's LDS
+    (``sx_vd_runs_lds_bytes``: popsize 10 up to ndim 512 and beyond)."""
+    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
+        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
+    batched_runs = runs is not None and runs > 1
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
-    _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
-    if runs is not None and not (isinstance(runs, (int, np.integer)) and not isinstance(runs, bool) and runs == 1):
-        raise ValueError(f"runs={runs!r}: method='vdcma' has no batched-runs kernel (runs > 1 is served by de, pso, cpso and "
-                         "cmaes with ndim <= 32)")
+    if batched_runs and x0 is not None and np.ndim(x0) == 2:  # a point per run
+        if np.shape(x0) != (runs, len(bounds)):
+            raise ValueError(f"x0 of shape {np.shape(x0)} with runs={runs}: expected ({len(bounds)},) for all runs or "
+                             f"({runs}, {len(bounds)})")
+        _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback)
+    else:
+        _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
+    if batched_runs:
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(sigma), float(muperc),
+                              float(xtol), float(ftol), seed, rng, constraints, workers, return_all, callback)
     workers = _common.resolve_workers(workers, fun_id)
     if _evolution.device_loop_serves(fun_id, rng, len(lower), popsize, constraints):
         # the whole loop (and the history) stays on the device -- since round 3 including constraints="Penalize"
@@ -88,6 +107,91 @@ def _strategy_constants(n, P, muperc):
     c1 = cfactor * 2.0 / ((n + 1.3) ** 2 + mueff)
     cmu = min(1.0 - c1, cfactor * 2.0 * (mueff - 2.0 + 1.0 / mueff) / ((n + 2.0) ** 2 + mueff))
     return mu, w, mueff, cc, c1, cmu
+
+
+RUNS_MIN_DIM = 6  # runs > 1: below, the reference's learning rates c1, cmu are zero or negative (cfactor = (n - 5) / 6)
+
+
+def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, seed, rng, constraints, workers,
+                   return_all, callback):
+    """``runs=R``: R independent runs, one workgroup each, one launch (csrc/sx_vd_runs.hip).  Everything that can be
+    refused is refused before the device is touched."""
+    n = len(lower)
+    if rng != "philox":
+        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
+    if not isinstance(fun_id, int):
+        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
+                         "(factory.batched and plain callables run between kernels)")
+    if workers not in (None, 1):
+        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
+    if callback is not None:
+        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
+    if return_all:
+        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
+    if constraints is not None:
+        raise ValueError(f"runs > 1 serves constraints=None (constraints={constraints!r}: the boundary-weight bookkeeping "
+                         "is not part of the run's kernel)")
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        seeds = [int(seed) + r for r in range(R)]
+    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
+        seeds = [int(s) for s in seed]
+    else:
+        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+    if maxiter < 1:
+        raise ValueError(f"runs > 1 needs maxiter >= 1 (maxiter={maxiter})")
+    if n < RUNS_MIN_DIM:
+        raise ValueError(f"runs > 1 with method='vdcma' needs ndim >= {RUNS_MIN_DIM} (ndim = {n}): below, the reference's "
+                         "learning rates c1 and cmu are zero or negative (cfactor = (ndim - 5) / 6) and the model never "
+                         "learns; method='cmaes' with runs serves ndim <= 32 properly")
+    lds = int(_lib.lib().sx_vd_runs_lds_bytes(P, n)) if P >= 1 else -1
+    mu = int(muperc * P)
+    if lds < 0 or mu < 1:
+        raise ValueError(f"runs > 1 keeps a run's model and staging rows in one workgroup's LDS: popsize {P} x {n} variables "
+                         f"(mu = {mu}) needs 2 <= popsize, mu >= 1, ndim <= {int(_lib.lib().sx_wide_from())} and at most "
+                         "160 KiB")
+    mu, w, mueff, cc, c1, cmu = _strategy_constants(n, P, muperc)
+    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
+    # what the single run of each seed draws on the host (_evolution._DeviceRun, _VdDeviceRun._model): its private legacy
+    # stream gives the initial mean -- unless the caller gave one -- and right after it the initial direction
+    xmean0, vvec0 = np.empty((R, n)), np.empty((R, n))
+    if x0 is not None:
+        xmean0[:] = (np.asarray(x0, dtype=np.float64) - xm) / xstd
+    for r, s in enumerate(seeds):
+        init = _rng.make_init_stream("philox", s)
+        if x0 is None:
+            xmean0[r] = init.uniform(-1.0, 1.0, n)
+        vvec0[r] = init.randn(n) / np.sqrt(n)
+
+    ctx = _device.Context()
+    t = _device.torch()
+    with t.cuda.stream(ctx.stream):
+        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
+        d_keys = ctx.upload_async(keys.view(np.int32))
+        d_xmean0, d_vvec0, d_w = ctx.upload(xmean0), ctx.upload(vvec0), ctx.upload(w)
+        d_std = ctx.upload_async(np.concatenate([xm, xstd]))
+        d_work = ctx.empty((int(ctx.L.sx_vd_runs_workspace_bytes(R, maxiter)) // 8,))
+        xs, funs, sigmas = ctx.empty((R, n)), ctx.empty((R,)), ctx.empty((R,))
+        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
+        a = _lib.SxVdRunsArgs()
+        a.keys, a.xmean0, a.vvec0, a.w = d_keys.data_ptr(), d_xmean0.data_ptr(), d_vvec0.data_ptr(), d_w.data_ptr()
+        a.xm, a.xstd = d_std[:n].data_ptr(), d_std[n:].data_ptr()
+        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
+                                                    statuses.data_ptr())
+        a.nfevs, a.sigmas, a.xmeans, a.dvecs, a.vvecs = None, sigmas.data_ptr(), None, None, None
+        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, fun_id, maxiter
+        a.ilim = int(10.0 + 30.0 * n / P)
+        a.mueff, a.cc, a.c1, a.cmu = mueff, cc, c1, cmu
+        a.cs, a.ds, a.wsum = 0.3, float(np.sqrt(n)), float(w.sum())
+        a.sigma = a.insigma = sigma
+        a.xtol, a.ftol = xtol, ftol
+        _lib.check(ctx.L.sx_vd_runs_launch(C.byref(a), ctx.stream_ptr), "sx_vd_runs_launch")
+        xs, funs, nits, statuses, sigmas = (xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy(),
+                                            sigmas.cpu().numpy())
+    best = int(np.argmin(funs))
+    status = int(statuses[best])
+    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
+                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
+                          xs=xs, funs=funs, nits=nits, statuses=statuses, sigmas=sigmas)
 
 
 class _VdDeviceRun(_evolution._DeviceRun):
