@@ -165,7 +165,11 @@ typedef struct sx_de_args {
     int32_t wide_from;      /* rows of more than this many elements take the one-workgroup-per-row kernels; 0 = sx_wide_from().
                                Clamped to [256, 4096], the rows the wavefront-per-row kernels can serve.  A run that needs the
                                chained kernel's peer exchange or global-donor gathers on rows of 2049 ... 4096 elements sets 4096 */
-    int32_t pad;
+    int32_t spec_store;     /* single-GPU chained kernel, rows of up to 128 elements: when a row is stored.  0 = the trial
+                               before the objective and the row that won again after it (what runs), 1 = once, after the
+                               objective; 2 / 3 (measurement aids) = the trial / the old row before the objective and
+                               afterwards only the rows for which that was the wrong one.  Same results whichever it is; the
+                               other kernels ignore it (this word was padding: size and layout of the struct are unchanged) */
     double F, CR, xtol, ftol;
     uint32_t key0, key1;    /* Philox key = seed                                      */
 } sx_de_args;

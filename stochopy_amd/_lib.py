@@ -52,7 +52,7 @@ class SxDeArgs(C.Structure):
         ("irand", vp), ("resample", vp),
         ("P", i64), ("ld", i64), ("row0", i64),
         ("n", i32), ("fun_id", i32), ("strategy", i32), ("constraints", i32), ("rng", i32), ("maxiter", i32),
-        ("wide_from", i32), ("pad", i32),
+        ("wide_from", i32), ("spec_store", i32),
         ("F", f64), ("CR", f64), ("xtol", f64), ("ftol", f64),
         ("key0", C.c_uint32), ("key1", C.c_uint32),
     ]

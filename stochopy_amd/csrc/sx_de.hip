@@ -38,6 +38,7 @@ int check_args(const sx_de_args *a) {
         SX_REQUIRE(a->constraints == 0 || a->resample, "sx_de: resample block missing");
     }
     SX_REQUIRE(a->constraints == 0 || (a->lower && a->upper), "sx_de: bounds missing");
+    SX_REQUIRE(a->spec_store >= 0 && a->spec_store <= 3, "sx_de: spec_store must be 0 ... 3");
     return 0;
 }
 

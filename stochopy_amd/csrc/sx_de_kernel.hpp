@@ -190,6 +190,19 @@ __device__ __forceinline__ void p2p_service(const sx_de_args &a, const sx_xchg_a
     }
 }
 
+// When the single-GPU chained kernel stores a one-batch row of up to 128 elements (sx_de_args.spec_store).  Same bits in
+// memory at the end of the launch, whichever it is.
+//   both (0, what runs): the trial BEFORE the objective, and the row that won -- trial or old row -- again after it
+//   late (1): once, after the objective, the row that won (the only form before; what every other kernel form does)
+//   trial-early (2) / old-early (3): the trial / the old row before the objective, afterwards only the rows for which that
+//     was the wrong one.  Measurement aids: they are what showed where the gain comes from.
+// Measured (profiles/de_spec_store.txt): a row stored ONCE costs the same wherever the store stands, early or late; a row
+// stored before AND after the objective takes 0.5-0.7 us of 7.2 out of the kernel boundary at the metric shape, whatever the
+// first store held (twice back to back does nothing).  Why is a GUESS -- a streaming store that hits a line this launch has
+// already written may leave the L2 at once instead of waiting for the end-of-kernel write-back -- and no counter pass has
+// confirmed it: the gain rests on cache behaviour nobody has explained and may go with a driver or firmware change.
+// If the headline moves back to the late figure, this is the first place to look (spec_store = 1 restores the old form).
+constexpr int SX_SPEC_BOTH = 0, SX_SPEC_LATE = 1, SX_SPEC_TRIAL_EARLY = 2, SX_SPEC_OLD_EARLY = 3;
 constexpr int kStep = 4;  // row steps per batch: one Philox call, and all its loads in flight together
 
 // FULL: n is a whole number of batches (n % (kStep*LPR) == 0) and P a whole number of workgroups, so
@@ -510,7 +523,21 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
     // gives rows of up to 64 / 128 elements 16 / 32 lanes: n <= kStep * LPR): trial and own row stay in registers for the
     // row store
     constexpr bool kRegRow = NFIX != 0 || LPR < kWave || ONEB;
+    // ... and, on one GPU, short rows may leave before the objective (SX_SPEC_*).  Whole-wave rows (129 ... 256 elements) store
+    // late as before: at n = 256 the old row early loses to the late store at every win fraction (profiles/de_spec_store.txt)
+    constexpr bool kSpec = kRegRow && XM == 1 && LPR < kWave;
+    const int smode = kSpec ? a.spec_store : SX_SPEC_LATE;  // (uniform: a kernel argument)
     double keep[kStep];
+    // a row's stores come from the same lane to the same address, so program order decides between them; nxt is read by
+    // nobody during this launch, and every exit of stage C lies before the first store
+    double *__restrict__ const xo = nxt + id.row * ld;
+    auto store_row = [&](const double(&v)[kStep]) {
+        if (FULL || id.active) {
+#pragma unroll
+            for (int t = 0; t < kStep; ++t)
+                if (NFIX != 0 || l + t * LPR < n) st_stream(xo + l + t * LPR, v[t]);
+        }
+    };
     auto trial_batch = [&](int q0, const Batch &bt) {
         const double(&bx)[kStep] = bt.x;
         const double(&bd)[kMaxDonors][kStep] = bt.d;
@@ -566,6 +593,9 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
                 g[t] = (use_best && (FULL || e < n)) ? gb[e] : 0.0;
             }
         }
+        if constexpr (kSpec) {  // old-early: the own row has arrived (it was asked for in stage B), the best row is on its way
+            if (smode == SX_SPEC_OLD_EARLY) store_row(bx);
+        }
 #pragma unroll
         for (int t = 0; t < kStep; ++t) {
             const int e = (q0 + t) * LPR + l;
@@ -593,16 +623,23 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
         }
     }
 
+    if constexpr (kSpec) {
+        if (smode == SX_SPEC_BOTH || smode == SX_SPEC_TRIAL_EARLY) store_row(keep);
+        __builtin_amdgcn_sched_barrier(0);  // the early stores stay in front of the objective
+    }
     SX_TP(2);
     const double fc = row_objective<FUN, LPR, NFIX, 1, ONEB>(U, n, plan, l);
     SX_TP(3);
     const bool better = fc < fold;  // _common.py:127 strict <
     if (FULL || id.active) {
-        double *__restrict__ xo = nxt + id.row * ld;
         if constexpr (kRegRow) {  // both rows are in registers already: no load behind the objective; streaming stores
+            // (trial-early / old-early: only the rows that stored the wrong one before the objective)
+            const bool again = smode == SX_SPEC_TRIAL_EARLY ? !better : smode == SX_SPEC_OLD_EARLY ? better : true;
+            if (again) {
 #pragma unroll
-            for (int t = 0; t < kStep; ++t)
-                if (NFIX != 0 || l + t * LPR < n) st_stream(xo + l + t * LPR, better ? keep[t] : B0.x[t]);
+                for (int t = 0; t < kStep; ++t)
+                    if (NFIX != 0 || l + t * LPR < n) st_stream(xo + l + t * LPR, better ? keep[t] : B0.x[t]);
+            }
         } else {
             const double *__restrict__ src = better ? U : xi;  // LDS or global: generic loads
             for (int e0 = l; e0 < n; e0 += kStep * LPR) {

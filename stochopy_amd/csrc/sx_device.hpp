@@ -934,6 +934,9 @@ __device__ __forceinline__ unsigned long long radius_decision(double r, double d
 // streaming (nt) stores they do not sit dirty in the XCDs' L2s until the end-of-kernel write-back: 7.45 -> 6.95 us per
 // generation (profiles/r4_de_m_store_flavours.txt: sc1 / sc0 sc1 write-through -1 %, uncached buffers +2.6 %, nt LOADS
 // of the own / donor rows +1 % / +8 %).  NOT for long rows or PSO: n=1024 P=16384 90 -> 96 us, C3a / C3b unchanged.
+// A row stored this way twice in one launch -- before and after the objective -- costs the kernel boundary less than one
+// stored once: profiles/de_spec_store.txt (sx_de_kernel.hpp SX_SPEC_*).  Measured, not explained: no counter pass has shown
+// what the L2 does with the second store, so the gain may not survive a driver or firmware change.
 template <class T>
 __device__ __forceinline__ void st_stream(T *p, T v) {
     __builtin_nontemporal_store(v, p);

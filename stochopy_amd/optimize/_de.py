@@ -193,11 +193,17 @@ class _DeRun(_PopulationRun):
     _warned_island = False
 
     def __init__(self, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol, return_all,
-                 verbosity, callback, rng, seed, workers, autorun=True, exchange=None, donors=None, immediate=False):
+                 verbosity, callback, rng, seed, workers, autorun=True, exchange=None, donors=None, immediate=False,
+                 spec_store=0):
         super().__init__("de", fun_id, lower, upper, x0, maxiter, P, xtol, ftol, return_all, verbosity, callback, rng, seed,
                          workers, immediate)
         self.F, self.CR, self.strategy, self.constraints = F, CR, strategy, constraints
         self.k = _lib.DE_DONORS[strategy]
+        # when the chained kernel stores a short row (include/stochopy_hip.h sx_de_args.spec_store): 0 = before and after the
+        # objective (what runs), 1 = once, after it, 2 / 3 = measurement aids; tests and tools only, not an option of minimize()
+        if spec_store not in (0, 1, 2, 3):
+            raise ValueError("spec_store must be 0, 1, 2 or 3")
+        self.spec_store = spec_store
         # the reference works in place on x0 (de/_de.py:208 + _common.py:128-129): mirrored on one GPU
         self.x0_in_place = self.world is None
         if donors not in (None, "shard", "global"):
@@ -496,6 +502,7 @@ class _DeRun(_PopulationRun):
         a.gbest = None if self.chain else self.gbest.data_ptr()
         a.P, a.ld, a.row0, a.n = P, n, self.row0, n
         a.wide_from = self.wide_from
+        a.spec_store = self.spec_store
         a.fun_id, a.strategy = (self.fun_id if self.external is None else 0), _lib.DE_STRATEGIES[self.strategy]
         if self.external is not None:
             self.cand = ctx.empty((P, n))
