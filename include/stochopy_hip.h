@@ -701,6 +701,36 @@ int sx_sample_chains_per_workgroup(int method, int jac, int n);
 int sx_sample_gradient(int fun_id, const double *X, int64_t P, int n, double *G, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Samplers around a CALLER-SUPPLIED objective (csrc/sx_sample_unfused.hip): the objective (and, for hmc, the gradient)
+ * is evaluated between the launches below, on (C, n) device arrays.  Same draws, arithmetic and per-chain state as
+ * sx_sample_run: with bit-identical objective / gradient values the run is sx_sample_run's, bit for bit.  rng must be
+ * SX_RNG_PHILOX; fun_id, normals and logu are not read.  Every function is one launch; prop / pmom / q / G are (C, n)
+ * DEVICE, fprop / k0 (C) DEVICE.
+ *   sample `it` of mcmc:  propose -> fprop = fun(prop) -> decide
+ *   sample `it` of hmc:   propose -> (nleap + 2) x (G = gradient(prop) -> leap) -> fprop = fun(prop) -> decide
+ *   sample 0:             propose -> fprop = fun(prop) -> decide
+ * ------------------------------------------------------------------------- */
+/* replaces mcmc/_mcmc.py:93 and hmc/_hmc.py:124 (it = 0: prop = the initial point), mcmc/_mcmc.py:106-118 (prop = cur with
+ * block (it-1) mod ceil(n/k) perturbed) and hmc/_hmc.py:137-141 (prop = cur, pmom = randn(n), k0 = 0.5 sum pmom^2).
+ * pmom / k0 may be NULL for mcmc */
+int sx_sample_propose(const sx_sample_args *a, int64_t it, double *prop, double *pmom, double *k0, void *stream);
+/* replaces hmc/_hmc.py:143-155, one step: pmom -= (coef * step) * G; then, if move, q += step * pmom
+ * (coef = 0.5 for the first and the last of the nleap + 2 momentum steps, move = 0 for the last) */
+int sx_sample_leap(const sx_sample_args *a, double coef, int move, double *q, double *pmom, const double *G, void *stream);
+/* replaces the rows numerical_gradient evaluates (hmc/_hmc.py:217-233), axes [axis0, axis0 + naxes) of every chain:
+ * W (naxes, 2, C, n) DEVICE, W[i,0,c,:] = q[c,:] with component axis0+i moved by +fd_step, W[i,1,c,:] by -fd_step, the
+ * components before it carrying the reference's in-place round trip ((q + h) - h, (q - h) + h) */
+int sx_sample_fd_rows(const sx_sample_args *a, const double *q, int axis0, int naxes, double *W, void *stream);
+/* replaces hmc/_hmc.py:227-233: fW (naxes, 2, C) DEVICE the objective's values of those rows ->
+ * G[c, axis0+i] = (0.5 * (fW[i,0,c] - fW[i,1,c])) / fd_step */
+int sx_sample_fd_gradient(const sx_sample_args *a, const double *fW, int axis0, int naxes, double *G, void *stream);
+/* replaces mcmc/_mcmc.py:120-140 and hmc/_hmc.py:157-172: feasibility (reject), the acceptance draw and decision with
+ * fprop = fun(prop), the chain's counts and best samples, row `it` of xall / funall (it = 0 starts the chains: cur = prop).
+ * pmom / k0 (hmc: what propose and the leaps left) may be NULL for mcmc */
+int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop, const double *pmom,
+                     const double *k0, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).
  * replaces: R calls of de/_de.py:176-301 (`de`: initial population :208-218, the generation loop :236-283) with
  *           de_sync (:314-351), the strategies (de/_strategy.py:1-46), Random (de/_constraints.py:13-28),

@@ -248,6 +248,11 @@ PROTOTYPES = {
     "sx_sample_run": (C.c_int, [C.POINTER(SxSampleArgs), i64, i64, vp]),
     "sx_sample_chains_per_workgroup": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sx_sample_gradient": (C.c_int, [C.c_int, vp, i64, C.c_int, vp, vp]),
+    "sx_sample_propose": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, vp]),
+    "sx_sample_leap": (C.c_int, [C.POINTER(SxSampleArgs), f64, C.c_int, vp, vp, vp, vp]),
+    "sx_sample_fd_rows": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
+    "sx_sample_fd_gradient": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
+    "sx_sample_decide": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_pso_runs_launch": (C.c_int, [C.POINTER(SxPsoRunsArgs), vp]),

@@ -1,12 +1,58 @@
 """What both samplers share: argument checks (no device needed), the draws of the numpy-legacy mode, the launches of the
-chain kernels (csrc/sx_sample.hip) and the assembly of the result."""
+chain kernels (csrc/sx_sample.hip; around a caller's own objective: csrc/sx_sample_unfused.hip) and the assembly of the
+result."""
 import ctypes as C
 
 import numpy as np
 
 from .. import _device, _lib, _rng
-from ..factory.benchmark import Objective
+from ..factory.benchmark import Objective, batched
+from ..optimize._common import External
 from ._helpers import SampleResult
+
+# hmc with a factory.batched objective and jac=None: the finite differences' rows of one chunk of axes are stacked into one
+# (axes, 2, chains, ndim) array so that ONE call of the caller's objective evaluates them; the chunk is as many axes as keep
+# that array under this many bytes (at least one)
+FD_STACK_BYTES = 256 << 20
+
+
+def fd_axes_per_chunk(chains, ndim):
+    """Axes whose 2 * chains finite-difference rows of ndim doubles fit FD_STACK_BYTES: 1 ... ndim."""
+    return max(1, min(ndim, FD_STACK_BYTES // (2 * chains * ndim * 8)))
+
+
+class Gradient:
+    """A caller-supplied gradient (``jac=factory.batched(g)``) as the hmc loop uses it: ``grad(ctx, X)`` -> (C, n) device
+    tensor.  Checked as ``optimize._common.External`` checks an objective."""
+
+    def __init__(self, tagged, args):
+        self.fun = tagged.fun
+        self.args = tuple(args) if args not in ((), None) else ()
+        self.name = tagged.__name__
+
+    def __call__(self, ctx, X):
+        t = _device.torch()
+        g = self.fun(X, *self.args)
+        if not isinstance(g, t.Tensor) or g.device != X.device:
+            raise TypeError(f"batched gradient {self.name}: expected a tensor on {X.device}, got {type(g).__name__}")
+        if g.shape != X.shape:
+            raise ValueError(f"batched gradient {self.name}: expected shape {tuple(X.shape)}, got {tuple(g.shape)}")
+        return g.to(t.float64).contiguous()
+
+
+class AutogradGradient:
+    """``jac="autograd"``: the chains' rows are independent, so the gradient of ``fun(X).sum()`` with respect to X holds
+    every chain's own gradient in its row."""
+
+    def __init__(self, external):
+        self.external = external
+
+    def __call__(self, ctx, X):
+        t = _device.torch()
+        with t.enable_grad():
+            Xg = X.detach().requires_grad_(True)
+            (g,) = t.autograd.grad(self.external(ctx, Xg).sum(), Xg)
+        return g.to(t.float64).contiguous()
 
 
 class Setup:
@@ -17,6 +63,8 @@ class Setup:
     nleap = 1
     jac = _lib.SX_JAC_FINITE_DIFF
     fd_step = 1.0e-4
+    external = None  # a factory.batched objective: optimize._common.External (the chain kernels then run unfused)
+    gradient = None  # hmc with such an objective: Gradient / AutogradGradient, or None for finite differences
 
     def __init__(self, fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                  backend, nleap=None):
@@ -50,12 +98,20 @@ class Setup:
         # -- this backend's own conditions
         if backend != "hip":
             raise ValueError(f'unknown backend {backend!r}: "hip" is the only one')
-        if not isinstance(fun, Objective):
-            raise TypeError("stochopy_amd.sample fuses the objective into the chain kernels: fun must be one of the "
-                            "stochopy_amd.factory objectives (factory.batched and Python callables are not supported)")
-        if args not in ((), None):
-            raise TypeError("factory objectives take no extra args")
-        self.fun_id = fun.sx_id
+        if isinstance(fun, batched):
+            if rng == "numpy-legacy":
+                raise TypeError('a factory.batched objective needs rng="philox": rng="numpy-legacy" replays the one stream '
+                                "of the reference inside the fused chain kernels")
+            self.external = External(fun, args)
+            self.fun_id = 0  # (not read by the unfused kernels)
+        elif not isinstance(fun, Objective):
+            raise TypeError("stochopy_amd.sample runs the chains on the device: fun must be one of the stochopy_amd.factory "
+                            "objectives or a device objective tagged with factory.batched (plain Python callables are not "
+                            "supported)")
+        else:
+            if args not in ((), None):
+                raise TypeError("factory objectives take no extra args")
+            self.fun_id = fun.sx_id
         # (csrc/sx_device.hpp kWideFrom: the longest row the kernels with one row per wavefront take)
         if ndim < 1 or ndim > _lib.wide_from():
             raise ValueError(f"stochopy_amd.sample serves rows of 1 to {_lib.wide_from()} elements, not {ndim}")
@@ -105,6 +161,51 @@ def _legacy_draws(s):
     return stream, np.ascontiguousarray(x0, dtype=np.float64), normals, logu
 
 
+class _Unfused:
+    """One sample around a caller-supplied objective (csrc/sx_sample_unfused.hip), launched eagerly on the engine's stream:
+    propose -> fun -> decide; hmc puts nleap + 2 rounds of (gradient, leap) in front of fun.  The chains' state stays in the
+    arrays of ``a``, as between the launches of a fused run with a callback."""
+
+    def __init__(self, s, ctx, a):
+        self.s, self.ctx, self.a, self.L = s, ctx, a, ctx.L
+        Cn, n = s.chains, s.ndim
+        self.hmc = s.method == _lib.SX_SAMPLE_HMC
+        self.prop = ctx.empty((Cn, n))
+        self.pmom = self.k0 = None
+        if self.hmc:
+            self.pmom = ctx.empty((Cn, n))
+            self.k0 = ctx.empty((Cn,))
+            if s.gradient is None:
+                self.chunk = fd_axes_per_chunk(Cn, n)
+                self.W = ctx.empty((self.chunk, 2, Cn, n))
+                self.G = ctx.empty((Cn, n))
+
+    def call(self, name, *args):
+        _lib.check(getattr(self.L, name)(C.byref(self.a), *args, self.ctx.stream_ptr), name)
+
+    def gradient(self):
+        s, ptr = self.s, _device.ptr
+        if s.gradient is not None:
+            return s.gradient(self.ctx, self.prop)
+        for axis0 in range(0, s.ndim, self.chunk):
+            naxes = min(self.chunk, s.ndim - axis0)
+            self.call("sx_sample_fd_rows", ptr(self.prop), axis0, naxes, ptr(self.W))
+            fW = s.external(self.ctx, self.W[:naxes].reshape(-1, s.ndim))  # one call for the chunk's 2 * naxes * C rows
+            self.call("sx_sample_fd_gradient", ptr(fW), axis0, naxes, ptr(self.G))
+        return self.G
+
+    def sample(self, i):
+        s, ptr = self.s, _device.ptr
+        self.call("sx_sample_propose", i, ptr(self.prop), ptr(self.pmom), ptr(self.k0))
+        if self.hmc and i > 0:
+            for g in range(s.nleap + 2):
+                G = self.gradient()
+                self.call("sx_sample_leap", 0.5 if g in (0, s.nleap + 1) else 1.0, int(g <= s.nleap), ptr(self.prop),
+                          ptr(self.pmom), ptr(G))
+        f = s.external(self.ctx, self.prop)
+        self.call("sx_sample_decide", i, ptr(self.prop), ptr(f), ptr(self.pmom), ptr(self.k0))
+
+
 def run(s):
     L = _lib.lib()
     legacy = s.rng == "numpy-legacy"
@@ -144,9 +245,18 @@ def run(s):
         def host(name):
             return dev[name].cpu().numpy()
 
+        if s.external is not None:
+            advance = _Unfused(s, ctx, a).sample
+        else:
+            def advance(i):
+                _lib.check(L.sx_sample_run(C.byref(a), i, 1, ctx.stream_ptr), "sx_sample_run")
+
         if s.callback is None:
-            # the whole run is one launch
-            _lib.check(L.sx_sample_run(C.byref(a), 0, m, ctx.stream_ptr), "sx_sample_run")
+            if s.external is not None:
+                for i in range(m):
+                    advance(i)
+            else:  # the whole run is one launch
+                _lib.check(L.sx_sample_run(C.byref(a), 0, m, ctx.stream_ptr), "sx_sample_run")
             xall = host("xall") if on_device_all else None
             funall = host("funall") if on_device_all else None
         else:
@@ -156,7 +266,7 @@ def run(s):
             xall = np.empty((Cn, m, n))
             funall = np.empty((Cn, m))
             for i in range(m):
-                _lib.check(L.sx_sample_run(C.byref(a), i, 1, ctx.stream_ptr), "sx_sample_run")
+                advance(i)
                 xall[:, i] = host("cur")
                 funall[:, i] = host("fcur")
                 iacc = host("iacc")

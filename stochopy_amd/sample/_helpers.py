@@ -25,7 +25,11 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
 
     Same signature and dispatch as the reference (``_helpers.py:41-88``): ``options`` is splatted into the
     per-method function, ``method`` is ``"mcmc"`` or ``"hmc"``.  ``fun`` is one of the ``stochopy_amd.factory``
-    handles (fused into the chain kernels); anything else raises ``TypeError``.  Options added by this backend:
+    handles (fused into the chain kernels), or the caller's own device objective tagged with ``factory.batched``:
+    ``fun(X, *args)`` maps the ``(chains, ndim)`` float64 ROCm tensor of proposals to the ``(chains,)`` tensor of
+    values on the same device (``args`` is passed through; needs ``rng="philox"``).  A sample then is propose kernel ->
+    ``fun`` -> decide kernel, launched one by one: same draws, same arithmetic, same results for the same values, a
+    few launches per sample slower.  A plain Python callable raises ``TypeError``.  Options added by this backend:
 
     - ``chains`` (int >= 1, default 1): independent chains, each resident in one kernel for the whole run.  With
       ``chains = C > 1`` the result's ``xall`` is ``(C, maxiter, ndim)``, ``funall`` ``(C, maxiter)``, ``x`` / ``fun``

@@ -1,5 +1,6 @@
 """Hamiltonian (hybrid) Monte-Carlo (reference: stochopy/sample/hmc/_hmc.py)."""
 from .. import _lib
+from ..factory.benchmark import batched
 from . import _chains
 from ._helpers import register
 
@@ -38,19 +39,36 @@ def sample(
     - ``jac``: the reference recurses without end for a callable.  Here ``jac`` is ``None`` (2-point finite
       differences with ``finite_diff_abs_step``, as the reference, perturbing and restoring the components in place)
       or the string ``"analytic"`` (the closed-form gradient of the factory objective, computed in the kernel; ackley's
-      gradient at the origin is taken as 0, and griewank's needs every cosine factor to be non-zero).  Anything else
-      raises ``TypeError``.
+      gradient at the origin is taken as 0, and griewank's needs every cosine factor to be non-zero).  With a
+      ``factory.batched`` objective (see ``stochopy_amd.sample.sample``) ``jac`` is ``None`` (the same finite
+      differences, the perturbed rows of several axes stacked into one call of ``fun``; ``nfev`` counts them),
+      ``factory.batched(g)`` (``g(X, *args)`` returns the ``(chains, ndim)`` gradient tensor on the same device) or
+      ``"autograd"`` (``torch.autograd.grad(fun(X).sum(), X)``: rows are independent, so that is each chain's own
+      gradient); ``"analytic"`` is for factory objectives only.  Anything else raises ``TypeError``.
     - ``constraints="Reject"``: the reference's feasibility helper returns ``None`` for it, so every proposal is
       rejected.  Here a trajectory that ends outside ``[lower, upper]`` is rejected, without an acceptance draw.  The
       draw sequence then depends on the data, so it needs ``rng="philox"``.
     """
     run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                         backend, nleap=nleap)
-    if not (jac is None or jac == "analytic"):
-        raise TypeError('jac is None (finite differences) or "analytic" (the factory objective\'s closed-form gradient)')
+    external = run.external is not None
+    own_gradient = isinstance(jac, batched) or (isinstance(jac, str) and jac == "autograd")
+    if own_gradient and not external:
+        raise TypeError('jac=factory.batched(g) and jac="autograd" go with a factory.batched objective; a factory objective '
+                        'takes jac=None or "analytic"')
+    if isinstance(jac, str) and jac == "analytic" and external:
+        raise TypeError('jac="analytic" is the closed form of a factory objective; with a factory.batched objective give '
+                        'jac=factory.batched(g) (your own gradient) or jac="autograd", or None for finite differences')
+    if not (jac is None or own_gradient or (isinstance(jac, str) and jac == "analytic")):
+        raise TypeError('jac is None (finite differences), "analytic" (a factory objective\'s closed-form gradient), or, with '
+                        'a factory.batched objective, factory.batched(g) or "autograd"')
     run.method = _lib.SX_SAMPLE_HMC
     run.nleap = int(nleap)
     run.jac = _lib.SX_JAC_FINITE_DIFF if jac is None else _lib.SX_JAC_ANALYTIC
+    if isinstance(jac, batched):
+        run.gradient = _chains.Gradient(jac, args)
+    elif own_gradient:
+        run.gradient = _chains.AutogradGradient(run.external)
     run.fd_step = float(finite_diff_abs_step)
     return _chains.run(run)
 

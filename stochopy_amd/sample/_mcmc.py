@@ -28,7 +28,8 @@ def sample(
     Arguments, defaults and results are the reference's.  Sample ``i`` perturbs one block of
     ``k = max(1, int(perc * ndim))`` consecutive variables with ``randn(k) * stepsize * 0.5 * (upper - lower)``,
     the blocks taking turns from variable 0; ``x`` / ``fun`` are the best among the ACCEPTED samples (``fun`` is
-    ``inf`` and ``x`` the first sample when nothing was accepted).  ``chains``, ``rng``, ``backend``:
+    ``inf`` and ``x`` the first sample when nothing was accepted).  ``chains``, ``rng``, ``backend`` and a
+    ``factory.batched`` objective (``fun(X, *args)`` on the ``(chains, ndim)`` device tensor, ``rng="philox"``):
     see ``stochopy_amd.sample.sample``.
 
     Where the reference is not well defined:
