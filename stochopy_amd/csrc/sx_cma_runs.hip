@@ -40,9 +40,9 @@
 // kRunsSweeps, P, mu or n.
 #include "sx_device.hpp"
 #include "sx_eigh_small.hpp"
-#include "sx_enqueue.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
+#include "sx_runs.hpp"
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out);
@@ -51,7 +51,6 @@ using namespace sx;
 
 namespace {
 
-constexpr int64_t kLdsLimit = 160 * 1024;  // what one workgroup may declare on gfx950
 constexpr int kRunsMaxDim = 32;            // the one-workgroup solver's range (sx_eigh.hip kSmallPathMax)
 constexpr int kRunsSweeps = 40;            // what the single run allows a decomposition started from the identity (COLD_SWEEPS)
 constexpr int kRunsLpr = 16;               // lanes per candidate row (lanes_per_row(n) for n <= 64)
@@ -417,21 +416,6 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
     }
 }
 
-typedef void (*cma_runs_kernel_t)(const sx_cma_runs_args, const PlanArg);
-
-template <int M2>
-cma_runs_kernel_t pick_runs(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return cma_runs_kernel<SX_FUN_ACKLEY, M2>;
-        case SX_FUN_GRIEWANK: return cma_runs_kernel<SX_FUN_GRIEWANK, M2>;
-        case SX_FUN_QUARTIC: return cma_runs_kernel<SX_FUN_QUARTIC, M2>;
-        case SX_FUN_RASTRIGIN: return cma_runs_kernel<SX_FUN_RASTRIGIN, M2>;
-        case SX_FUN_ROSENBROCK: return cma_runs_kernel<SX_FUN_ROSENBROCK, M2>;
-        case SX_FUN_SPHERE: return cma_runs_kernel<SX_FUN_SPHERE, M2>;
-        default: return cma_runs_kernel<SX_FUN_STYBLINSKI_TANG, M2>;
-    }
-}
-
 }  // namespace
 
 extern "C" int64_t sx_cma_runs_lds_bytes(int64_t P, int n) {
@@ -458,15 +442,11 @@ extern "C" int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream) {
     SX_REQUIRE(lds > 0, "sx_cma_runs_launch: the run's model and candidates do not fit one workgroup's LDS");
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const int m2 = runs_m2(a->n);
-    cma_runs_kernel_t kern = m2 == 16 ? pick_runs<16>(a->fun_id) : pick_runs<32>(a->fun_id);
-    const int threads = m2 == 16 ? runs_threads<16>() : runs_threads<32>();
-    if (lds > 64 * 1024)  // more than the default limit of dynamic LDS
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
     SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_cma_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
-    Enqueue q((hipStream_t)stream);
-    if (int rc = q.kernel(kern, dim3((unsigned)a->R), dim3((unsigned)threads), (size_t)lds, *a, plan)) return rc;
-    SX_LAUNCH_CHECK();
-    return 0;
+    if (runs_m2(a->n) == 16) {
+        SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(cma_runs_kernel<FUN, 16>, *a, plan, runs_threads<16>(), lds, stream))
+    }
+    SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(cma_runs_kernel<FUN, 32>, *a, plan, runs_threads<32>(), lds, stream))
+    return -1;
 }

@@ -22,6 +22,7 @@
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
+#include "sx_runs.hpp"
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out);
@@ -31,7 +32,6 @@ using namespace sx;
 namespace {
 
 constexpr int kStep = 4;                    // row steps per batch: one pair of Philox calls (de_propose_kernel's layout)
-constexpr int64_t kLdsLimit = 160 * 1024;   // what one workgroup may declare on gfx950
 constexpr int kBroadcastWords = 4;          // best value, best row, status, (spare)
 constexpr int kFinalThreads = 256;          // threads of select_finalize_kernel (sx_core.hip): its dx sums in their order
 
@@ -202,21 +202,6 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de
     }
 }
 
-typedef void (*de_runs_kernel_t)(const sx_de_runs_args, const PlanArg);
-
-template <int LPR>
-de_runs_kernel_t pick_runs(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return de_runs_kernel<SX_FUN_ACKLEY, LPR>;
-        case SX_FUN_GRIEWANK: return de_runs_kernel<SX_FUN_GRIEWANK, LPR>;
-        case SX_FUN_QUARTIC: return de_runs_kernel<SX_FUN_QUARTIC, LPR>;
-        case SX_FUN_RASTRIGIN: return de_runs_kernel<SX_FUN_RASTRIGIN, LPR>;
-        case SX_FUN_ROSENBROCK: return de_runs_kernel<SX_FUN_ROSENBROCK, LPR>;
-        case SX_FUN_SPHERE: return de_runs_kernel<SX_FUN_SPHERE, LPR>;
-        default: return de_runs_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
-    }
-}
-
 }  // namespace
 
 extern "C" int64_t sx_de_runs_lds_bytes(int64_t P, int n) {
@@ -239,12 +224,7 @@ extern "C" int sx_de_runs_launch(const sx_de_runs_args *a, void *stream) {
     SX_REQUIRE(lds > 0, "sx_de_runs_launch: the run's two populations do not fit one workgroup's LDS");
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    de_runs_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = pick_runs<LPR>(a->fun_id))
-    if (lds > 64 * 1024)  // more than the default limit of dynamic LDS
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)a->R), dim3((unsigned)(runs_waves(a->P, a->n) * kWave)), (size_t)lds,
-                       (hipStream_t)stream, *a, plan);
-    SX_LAUNCH_CHECK();
-    return 0;
+    const int threads = runs_waves(a->P, a->n) * kWave;
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(de_runs_kernel<FUN, LPR>, *a, plan, threads, lds, stream)))
+    return -1;
 }

@@ -42,6 +42,7 @@
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
+#include "sx_runs.hpp"
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out);
@@ -51,7 +52,6 @@ using namespace sx;
 namespace {
 
 constexpr int kStep = 2;                   // row steps per Philox call: two 53-bit uniforms
-constexpr int64_t kLdsLimit = 160 * 1024;  // what one workgroup may declare on gfx950
 constexpr int kBroadcastWords = 4;         // best value, status, (two spare: gbest is a copy, nobody needs the best row)
 constexpr int kMaxPasses = 64;             // passes over the rows: the restart flags of a row group are one 64-bit word
 
@@ -323,21 +323,6 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void p
     }
 }
 
-typedef void (*pso_runs_kernel_t)(const sx_pso_runs_args, const PlanArg);
-
-template <int LPR>
-pso_runs_kernel_t pick_runs(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return pso_runs_kernel<SX_FUN_ACKLEY, LPR>;
-        case SX_FUN_GRIEWANK: return pso_runs_kernel<SX_FUN_GRIEWANK, LPR>;
-        case SX_FUN_QUARTIC: return pso_runs_kernel<SX_FUN_QUARTIC, LPR>;
-        case SX_FUN_RASTRIGIN: return pso_runs_kernel<SX_FUN_RASTRIGIN, LPR>;
-        case SX_FUN_ROSENBROCK: return pso_runs_kernel<SX_FUN_ROSENBROCK, LPR>;
-        case SX_FUN_SPHERE: return pso_runs_kernel<SX_FUN_SPHERE, LPR>;
-        default: return pso_runs_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
-    }
-}
-
 }  // namespace
 
 extern "C" int64_t sx_pso_runs_lds_bytes(int64_t P, int n) {
@@ -371,12 +356,7 @@ extern "C" int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream) {
     SX_REQUIRE((a->P + rpp - 1) / rpp <= kMaxPasses, "sx_pso_runs_launch: more passes over the rows than restart flags");
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    pso_runs_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = pick_runs<LPR>(a->fun_id))
-    if (lds > 64 * 1024)  // more than the default limit of dynamic LDS
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)a->R), dim3((unsigned)(waves * kWave)), (size_t)lds, (hipStream_t)stream, args,
-                       plan);
-    SX_LAUNCH_CHECK();
-    return 0;
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(pso_runs_kernel<FUN, LPR>, args, plan,
+                                                                         waves * kWave, lds, stream)))
+    return -1;
 }

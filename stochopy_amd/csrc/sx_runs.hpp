@@ -1,0 +1,37 @@
+// The host tail the batched-runs kernels share (sx_de_runs.hip, sx_pso_runs.hip, sx_cma_runs.hip, sx_vd_runs.hip): one
+// workgroup per run, its whole state in dynamic LDS.
+#pragma once
+#include <cstdint>
+
+#include "sx_device.hpp"
+#include "sx_enqueue.hpp"
+
+namespace sx {
+
+constexpr int64_t kLdsLimit = 160 * 1024;  // what one workgroup may declare on gfx950
+
+// run CALL with `constexpr int FUN` bound to the objective `fun_id` names (checked by the caller: 0 <= fun_id < SX_FUN_COUNT)
+#define SX_DISPATCH_FUN(fun_id, CALL)                                                           \
+    switch (fun_id) {                                                                           \
+        case SX_FUN_ACKLEY: { constexpr int FUN = SX_FUN_ACKLEY; CALL; } break;                 \
+        case SX_FUN_GRIEWANK: { constexpr int FUN = SX_FUN_GRIEWANK; CALL; } break;             \
+        case SX_FUN_QUARTIC: { constexpr int FUN = SX_FUN_QUARTIC; CALL; } break;               \
+        case SX_FUN_RASTRIGIN: { constexpr int FUN = SX_FUN_RASTRIGIN; CALL; } break;           \
+        case SX_FUN_ROSENBROCK: { constexpr int FUN = SX_FUN_ROSENBROCK; CALL; } break;         \
+        case SX_FUN_SPHERE: { constexpr int FUN = SX_FUN_SPHERE; CALL; } break;                 \
+        default: { constexpr int FUN = SX_FUN_STYBLINSKI_TANG; CALL; } break;                   \
+    }
+
+// R workgroups of `threads` threads with `lds` bytes of dynamic LDS each, onto `stream`
+template <class Args>
+__attribute__((visibility("hidden"))) int enqueue_runs(void (*kern)(const Args, const PlanArg), const Args &a,
+                                                       const PlanArg &plan, int threads, int64_t lds, void *stream) {
+    if (lds > 64 * 1024)  // more than the default limit of dynamic LDS
+        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    Enqueue q((hipStream_t)stream);
+    if (int rc = q.kernel(kern, dim3((unsigned)a.R), dim3((unsigned)threads), (size_t)lds, a, plan)) return rc;
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace sx

@@ -55,9 +55,9 @@
 // Nothing passes between workgroups: no grid barrier, no spin-wait, no atomics.  Every loop is bounded by maxiter, P, mu
 // or n.
 #include "sx_device.hpp"
-#include "sx_enqueue.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
+#include "sx_runs.hpp"
 
 namespace sx {
 int make_plan_arg(int fun_id, int n, PlanArg *out);
@@ -66,7 +66,6 @@ using namespace sx;
 
 namespace {
 
-constexpr int64_t kLdsLimit = 160 * 1024;  // what one workgroup may declare on gfx950
 constexpr int kVrMinDim = 6;               // below, the reference's learning rates are <= 0 (cfactor = (n - 5) / 6)
 constexpr int kVrVecs = 11, kVrRed = 80, kVrPos = 8, kVrMaxSlices = 8;
 
@@ -533,21 +532,6 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
     }
 }
 
-typedef void (*vd_runs_kernel_t)(const sx_vd_runs_args, const PlanArg);
-
-template <int LPR>
-vd_runs_kernel_t pick_runs(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return vd_runs_kernel<SX_FUN_ACKLEY, LPR>;
-        case SX_FUN_GRIEWANK: return vd_runs_kernel<SX_FUN_GRIEWANK, LPR>;
-        case SX_FUN_QUARTIC: return vd_runs_kernel<SX_FUN_QUARTIC, LPR>;
-        case SX_FUN_RASTRIGIN: return vd_runs_kernel<SX_FUN_RASTRIGIN, LPR>;
-        case SX_FUN_ROSENBROCK: return vd_runs_kernel<SX_FUN_ROSENBROCK, LPR>;
-        case SX_FUN_SPHERE: return vd_runs_kernel<SX_FUN_SPHERE, LPR>;
-        default: return vd_runs_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
-    }
-}
-
 }  // namespace
 
 extern "C" int sx_vd_runs_args_bytes(void) { return (int)sizeof(sx_vd_runs_args); }
@@ -577,14 +561,9 @@ extern "C" int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream) {
     SX_REQUIRE(lds > 0, "sx_vd_runs_launch: the run's model and staging rows do not fit one workgroup's LDS");
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    vd_runs_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = pick_runs<LPR>(a->fun_id))
-    if (lds > 64 * 1024)  // more than the default limit of dynamic LDS
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
     SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_vd_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
-    Enqueue q((hipStream_t)stream);
-    if (int rc = q.kernel(kern, dim3((unsigned)a->R), dim3((unsigned)vr_threads(a->n)), (size_t)lds, *a, plan)) return rc;
-    SX_LAUNCH_CHECK();
-    return 0;
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(vd_runs_kernel<FUN, LPR>, *a, plan,
+                                                                         vr_threads(a->n), lds, stream)))
+    return -1;
 }

@@ -13,16 +13,15 @@ candidates, the objective and the weighted squared excess run in one device kern
 (``sx_cmaes_eval_penalized``); the scalar bookkeeping of the boundary weights stays on the host.
 """
 
-import ctypes as C
 import os
 import warnings
 
 import numpy as np
 
-from .. import _device, _lib, _rng
+from .. import _device, _lib
 from ..linalg import Eigh
-from . import _common, _evolution
-from ._helpers import OptimizeResult, register
+from . import _common, _evolution, _runs
+from ._helpers import register
 
 __all__ = ["minimize"]
 
@@ -85,9 +84,7 @@ def minimize(
     ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, ``constraints=None``, the device
     eigensolver, ``ndim <= 32`` and a population that fits one workgroup's LDS (``sx_cma_runs_lds_bytes``).
     """
-    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
-        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
-    batched_runs = runs is not None and runs > 1
+    batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     if batched_runs and x0 is not None and np.ndim(x0) == 2:  # a point per run
@@ -144,31 +141,13 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
     """``runs=R``: R independent runs, one workgroup each, one launch (csrc/sx_cma_runs.hip).  Everything that can be
     refused is refused before the device is touched."""
     n = len(lower)
-    if rng != "philox":
-        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
-    if not isinstance(fun_id, int):
-        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
-                         "(factory.batched and plain callables run between kernels)")
-    if workers not in (None, 1):
-        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
-    if callback is not None:
-        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
-    if return_all:
-        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
-    if constraints is not None:
-        raise ValueError(f"runs > 1 serves constraints=None (constraints={constraints!r}: the boundary-weight bookkeeping "
-                         "is not part of the run's kernel)")
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_constraints(constraints)
     if eigh is not None and (callable(eigh) or eigh != "device"):
         raise ValueError('runs > 1 decomposes C inside the run\'s kernel: eigh=None or "device" '
                          f"(eigh={'a callable' if callable(eigh) else repr(eigh)})")
-    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
-        seeds = [int(seed) + r for r in range(R)]
-    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
-        seeds = [int(s) for s in seed]
-    else:
-        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
-    if maxiter < 1:
-        raise ValueError(f"runs > 1 needs maxiter >= 1 (maxiter={maxiter})")
+    seeds = _runs.seeds_of(R, seed)
+    _runs.refuse_maxiter(maxiter)
     if n > RUNS_MAX_DIM:
         raise ValueError(f"runs > 1 keeps a run's covariance and its eigendecomposition in one workgroup: ndim <= "
                          f"{RUNS_MAX_DIM} (ndim = {n}, popsize = {P})")
@@ -177,42 +156,31 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
     if lds < 0 or mu < 1:
         raise ValueError(f"runs > 1 keeps a run's model and candidates in one workgroup's LDS: popsize {P} x {n} variables "
                          f"(mu = {mu}) needs 2 <= popsize, mu >= 1 and at most 160 KiB")
+    batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol)
+    batch.launch()
+    return _runs.result(batch.fetch(), P)
+
+
+def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, outputs=()):
+    """The batch of one sx_cma_runs_launch; ``outputs``: of the optional ones, ``"nfevs"`` and ``"xmeans"`` (every run's
+    final mean, standardised)."""
+    n, R = len(lower), len(seeds)
     mu, w, *constants = _strategy_constants(n, P, muperc)
-    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
-    if x0 is None:
+    xm, xstd, xmean0 = _runs.standardised(lower, upper, x0, R)
+    if xmean0 is None:
         # the initial mean of the single run of each seed: its private legacy stream (_rng.make_init_stream), n uniforms
         xmean0 = np.array([np.random.RandomState(s & 0xFFFFFFFF).uniform(-1.0, 1.0, n) for s in seeds])
-    else:
-        xmean0 = np.ascontiguousarray(np.broadcast_to((np.asarray(x0, dtype=np.float64) - xm) / xstd, (R, n)))
-
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
+    batch = _runs.Batch("sx_cma_runs_launch", _lib.SxCmaRunsArgs(), seeds, P)
+    a, ctx = batch.a, batch.ctx
+    with batch.stream():
+        batch.upload_keys()
         d_xmean0, d_std, d_w = ctx.upload(xmean0), ctx.upload_async(np.concatenate([xm, xstd])), ctx.upload(w)
-        d_work = ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,))
-        xs, funs, sigmas = ctx.empty((R, n)), ctx.empty((R,)), ctx.empty((R,))
-        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
-        a = _lib.SxCmaRunsArgs()
-        a.keys, a.xmean0, a.xm, a.xstd, a.w = (d_keys.data_ptr(), d_xmean0.data_ptr(), d_std[:n].data_ptr(),
-                                               d_std[n:].data_ptr(), d_w.data_ptr())
-        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
-                                                    statuses.data_ptr())
-        a.nfevs, a.sigmas, a.xmeans = None, sigmas.data_ptr(), None
-        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, fun_id, maxiter
-        a.ilim = int(10.0 + 30.0 * n / P)
-        a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
-        a.sigma = a.insigma = sigma
-        a.xtol, a.ftol = xtol, ftol
-        _lib.check(ctx.L.sx_cma_runs_launch(C.byref(a), ctx.stream_ptr), "sx_cma_runs_launch")
-        xs, funs, nits, statuses, sigmas = (xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy(),
-                                            sigmas.cpu().numpy())
-    best = int(np.argmin(funs))
-    status = int(statuses[best])
-    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
-                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
-                          xs=xs, funs=funs, nits=nits, statuses=statuses, sigmas=sigmas)
+        batch.bind(xmean0=d_xmean0, xm=d_std[:n], xstd=d_std[n:], w=d_w,
+                   work=ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,)))
+        batch.outputs(n, {"nfevs": ((R,), _device.torch().int64), "xmeans": ((R, n), None)}, outputs, extra=("sigmas",))
+    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, sigma, xtol, ftol)
+    a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
+    return batch
 
 
 COLD_SWEEPS = 40   # launched for a decomposition started from the identity (n=512: 11-13 are carried out)

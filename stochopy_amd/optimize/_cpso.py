@@ -11,13 +11,12 @@ best/termination kernel; the competitive restart (:405-426) is three small kerne
 """
 import ctypes as C
 import os
-import warnings
 
 import numpy as np
 
 from .. import _device, _lib, _rng
-from . import _common
-from ._helpers import OptimizeResult, register
+from . import _common, _runs
+from ._helpers import register
 from ._population import _PopulationRun
 
 __all__ = ["minimize"]
@@ -67,9 +66,7 @@ def minimize(
     per run.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a swarm that fits one workgroup's LDS (``sx_pso_runs_lds_bytes``).
     """
-    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
-        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
-    batched_runs = runs is not None and runs > 1
+    batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     if batched_runs and x0 is not None and np.ndim(x0) == 3:  # a swarm per run
@@ -116,69 +113,45 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competiti
     """``runs=R``: R independent deferred-updating runs, one workgroup each, one launch (csrc/sx_pso_runs.hip).  Everything
     that can be refused is refused before the device is touched."""
     n = len(lower)
-    if rng != "philox":
-        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
-    if not isinstance(fun_id, int):
-        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
-                         "(factory.batched and plain callables run between kernels)")
-    if workers not in (None, 1):
-        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
-    if callback is not None:
-        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
-    if return_all:
-        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
-    if updating == "immediate":
-        if strict_updating:
-            raise ValueError('strict_updating=True: updating="immediate" is an ordered sweep; runs > 1 are whole generations in '
-                             'parallel (updating="deferred")')
-        if strict_updating is None:
-            warnings.warn('stochopy_amd: updating="immediate" is an ordered sweep of ONE run; runs > 1 use "deferred" updating, '
-                          "as a parallel backend of the reference does (cpso/_cpso.py:147-150).", RuntimeWarning, stacklevel=3)
-    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
-        seeds = [int(seed) + r for r in range(R)]
-    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
-        seeds = [int(s) for s in seed]
-    else:
-        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_immediate(updating, strict_updating, "cpso/_cpso.py:147-150")
+    seeds = _runs.seeds_of(R, seed)
     if n > _lib.wide_from():
         raise ValueError(f"runs > 1 serves rows of up to {_lib.wide_from()} elements (n = {n})")
-    lds = int(_lib.lib().sx_pso_runs_lds_bytes(P, n))
-    if lds < 0:
+    if int(_lib.lib().sx_pso_runs_lds_bytes(P, n)) < 0:
         raise ValueError(f"runs > 1 keeps a run's swarm (X and pbest at the least) in one workgroup's LDS: popsize {P} x {n} "
                          "variables is more than its 160 KiB hold")
+    batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competitivity, constraints, xtol, ftol)
+    batch.launch()
+    return _runs.result(batch.fetch(), P)
+
+
+def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competitivity, constraints, xtol, ftol, outputs=()):
+    """The batch of one sx_pso_runs_launch; ``outputs``: of the optional ones, every run's last swarm -- ``"xfinal"``,
+    ``"pbest_final"``, ``"pbestfit_final"``."""
+    n = len(lower)
     gamma = float(competitivity) if competitivity else 0.0
     # cpso/_cpso.py:215-216 (depends on maxiter and the swarm's size)
     delta = float(np.log(1.0 + 0.003 * P) / np.max((0.2, np.log(0.01 * maxiter)))) if gamma else 0.0
-
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
+    batch = _runs.Batch("sx_pso_runs_launch", _lib.SxPsoRunsArgs(), seeds, P)
+    a, ctx, R = batch.a, batch.ctx, batch.R
+    with batch.stream():
+        batch.upload_keys()
         d_bounds = ctx.upload_async(np.concatenate([lower, upper]))
-        d_x0 = None if x0 is None else ctx.upload(np.array(x0, dtype=np.float64))
-        xs, funs = ctx.empty((R, n)), ctx.empty((R,))
-        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
-        a = _lib.SxPsoRunsArgs()
-        a.keys, a.lower, a.upper = d_keys.data_ptr(), d_bounds[:n].data_ptr(), d_bounds[n:].data_ptr()
-        a.x0 = None if d_x0 is None else d_x0.data_ptr()
-        a.xs, a.funs, a.nits, a.statuses = xs.data_ptr(), funs.data_ptr(), nits.data_ptr(), statuses.data_ptr()
-        a.xfinal = a.pbest_final = a.pbestfit_final = None
+        batch.bind(lower=d_bounds[:n], upper=d_bounds[n:])
+        if x0 is not None:
+            batch.bind(x0=ctx.upload(np.array(x0, dtype=np.float64)))
+            a.x0_stride = P * n if batch.dev["x0"].dim() == 3 else 0
+        batch.outputs(n, {"xfinal": ((R, P, n), None), "pbest_final": ((R, P, n), None), "pbestfit_final": ((R, P), None)},
+                      outputs)
         # (a swarm whose X, V and pbest do not fit the LDS together keeps its velocities here)
         vwork = int(ctx.L.sx_pso_runs_workspace_bytes(R, P, n))
-        d_vwork = ctx.empty((vwork // 8,)) if vwork else None
-        a.vwork = None if d_vwork is None else d_vwork.data_ptr()
-        a.R, a.P, a.x0_stride = R, P, (P * n if d_x0 is not None and d_x0.dim() == 3 else 0)
-        a.n, a.fun_id = n, fun_id
-        a.constraints, a.maxiter = (1 if constraints == "Shrink" else 0), maxiter
-        a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = w, c1, c2, gamma, delta, xtol, ftol
-        _lib.check(ctx.L.sx_pso_runs_launch(C.byref(a), ctx.stream_ptr), "sx_pso_runs_launch")
-        xs, funs, nits, statuses = xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy()
-    best = int(np.argmin(funs))
-    status = int(statuses[best])
-    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
-                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
-                          xs=xs, funs=funs, nits=nits, statuses=statuses)
+        if vwork:
+            batch.bind(vwork=ctx.empty((vwork // 8,)))
+    a.n, a.fun_id = n, fun_id
+    a.constraints, a.maxiter = (1 if constraints == "Shrink" else 0), maxiter
+    a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = w, c1, c2, gamma, delta, xtol, ftol
+    return batch
 
 
 class _PsoRun(_PopulationRun):

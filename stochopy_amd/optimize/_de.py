@@ -15,8 +15,8 @@ import warnings
 import numpy as np
 
 from .. import _device, _lib, _rng
-from . import _common
-from ._helpers import OptimizeResult, register
+from . import _common, _runs
+from ._helpers import register
 from ._population import _PopulationRun
 
 __all__ = ["minimize"]
@@ -78,9 +78,7 @@ def minimize(
     per run.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a population whose two generations fit one workgroup's LDS (``sx_de_runs_lds_bytes``).
     """
-    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
-        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
-    batched_runs = runs is not None and runs > 1
+    batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     if batched_runs and x0 is not None and np.ndim(x0) == 3:  # a population per run
@@ -130,61 +128,36 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, con
     """``runs=R``: R independent deferred-updating runs, one workgroup each, one launch (csrc/sx_de_runs.hip).  Everything
     that can be refused is refused before the device is touched."""
     n = len(lower)
-    if rng != "philox":
-        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
-    if not isinstance(fun_id, int):
-        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
-                         "(factory.batched and plain callables run between kernels)")
-    if workers not in (None, 1):
-        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
-    if callback is not None:
-        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
-    if return_all:
-        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
-    if updating == "immediate":
-        if strict_updating:
-            raise ValueError('strict_updating=True: updating="immediate" is an ordered sweep; runs > 1 are whole generations in '
-                             'parallel (updating="deferred")')
-        if strict_updating is None:
-            warnings.warn('stochopy_amd: updating="immediate" is an ordered sweep of ONE run; runs > 1 use "deferred" updating, '
-                          "as a parallel backend of the reference does (de/_de.py:142-145).", RuntimeWarning, stacklevel=3)
-    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
-        seeds = [int(seed) + r for r in range(R)]
-    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
-        seeds = [int(s) for s in seed]
-    else:
-        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_immediate(updating, strict_updating, "de/_de.py:142-145")
+    seeds = _runs.seeds_of(R, seed)
     if n > _lib.wide_from():
         raise ValueError(f"runs > 1 serves rows of up to {_lib.wide_from()} elements (n = {n})")
-    lds = int(_lib.lib().sx_de_runs_lds_bytes(P, n))
-    if lds < 0:
+    if int(_lib.lib().sx_de_runs_lds_bytes(P, n)) < 0:
         raise ValueError(f"runs > 1 keeps a run's two generations in one workgroup's LDS: popsize {P} x {n} variables "
                          "is more than its 160 KiB hold")
+    batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol)
+    batch.launch()
+    return _runs.result(batch.fetch(), P)
 
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
+
+def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol, outputs=()):
+    """The batch of one sx_de_runs_launch; ``outputs``: of the optional ones, ``"xfinal"`` (every run's last population)."""
+    n = len(lower)
+    batch = _runs.Batch("sx_de_runs_launch", _lib.SxDeRunsArgs(), seeds, P)
+    a, ctx, R = batch.a, batch.ctx, batch.R
+    with batch.stream():
+        batch.upload_keys()
         d_bounds = ctx.upload_async(np.concatenate([lower, upper]))
-        d_x0 = None if x0 is None else ctx.upload(np.array(x0, dtype=np.float64))
-        xs, funs = ctx.empty((R, n)), ctx.empty((R,))
-        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
-        a = _lib.SxDeRunsArgs()
-        a.keys, a.lower, a.upper = d_keys.data_ptr(), d_bounds[:n].data_ptr(), d_bounds[n:].data_ptr()
-        a.x0 = None if d_x0 is None else d_x0.data_ptr()
-        a.xs, a.funs, a.nits, a.statuses, a.xfinal = xs.data_ptr(), funs.data_ptr(), nits.data_ptr(), statuses.data_ptr(), None
-        a.R, a.P, a.x0_stride = R, P, (P * n if d_x0 is not None and d_x0.dim() == 3 else 0)
-        a.n, a.fun_id, a.strategy = n, fun_id, _lib.DE_STRATEGIES[strategy]
-        a.constraints, a.maxiter = (1 if constraints == "Random" else 0), maxiter
-        a.F, a.CR, a.xtol, a.ftol = F, CR, xtol, ftol
-        _lib.check(ctx.L.sx_de_runs_launch(C.byref(a), ctx.stream_ptr), "sx_de_runs_launch")
-        xs, funs, nits, statuses = xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy()
-    best = int(np.argmin(funs))
-    status = int(statuses[best])
-    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
-                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
-                          xs=xs, funs=funs, nits=nits, statuses=statuses)
+        batch.bind(lower=d_bounds[:n], upper=d_bounds[n:])
+        if x0 is not None:
+            batch.bind(x0=ctx.upload(np.array(x0, dtype=np.float64)))
+            a.x0_stride = P * n if batch.dev["x0"].dim() == 3 else 0
+        batch.outputs(n, {"xfinal": ((R, P, n), None)}, outputs)
+    a.n, a.fun_id, a.strategy = n, fun_id, _lib.DE_STRATEGIES[strategy]
+    a.constraints, a.maxiter = (1 if constraints == "Random" else 0), maxiter
+    a.F, a.CR, a.xtol, a.ftol = F, CR, xtol, ftol
+    return batch
 
 
 class _DeRun(_PopulationRun):

@@ -1,0 +1,137 @@
+"""``options["runs"] = R``: the host path the batched methods share (de, pso / cpso, cmaes, vdcma) -- the option's
+validation, the refusals, the seed rule, the batch that one ``sx_*_runs_launch`` takes, and the result.  A method module
+keeps the one function that builds its batch (its constants, its inputs, its struct fields) and its own refusals.
+"""
+import ctypes as C
+import warnings
+
+import numpy as np
+
+from .. import _device, _lib, _rng
+from . import _common
+from ._helpers import OptimizeResult
+
+
+def batched(runs):
+    """Validate ``runs``; is this call a batch (R >= 2)?"""
+    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
+        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
+    return runs is not None and runs > 1
+
+
+def refuse_common(rng, fun_id, workers, callback, return_all):
+    """What no batched method serves: a run lives in one kernel on one GPU."""
+    if rng != "philox":
+        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
+    if not isinstance(fun_id, int):
+        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
+                         "(factory.batched and plain callables run between kernels)")
+    if workers not in (None, 1):
+        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
+    if callback is not None:
+        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
+    if return_all:
+        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
+
+
+def refuse_immediate(updating, strict_updating, citation):
+    """DE, PSO: ``updating="immediate"`` is refused (strict) or deferred with a warning that points at the line that called
+    the method's ``minimize`` (this function <- ``_minimize_runs`` <- ``minimize`` <- that line)."""
+    if updating == "immediate":
+        if strict_updating:
+            raise ValueError('strict_updating=True: updating="immediate" is an ordered sweep; runs > 1 are whole generations in '
+                             'parallel (updating="deferred")')
+        if strict_updating is None:
+            warnings.warn('stochopy_amd: updating="immediate" is an ordered sweep of ONE run; runs > 1 use "deferred" updating, '
+                          f"as a parallel backend of the reference does ({citation}).", RuntimeWarning, stacklevel=4)
+
+
+def refuse_constraints(constraints):
+    """CMA-ES, VD-CMA."""
+    if constraints is not None:
+        raise ValueError(f"runs > 1 serves constraints=None (constraints={constraints!r}: the boundary-weight bookkeeping "
+                         "is not part of the run's kernel)")
+
+
+def refuse_maxiter(maxiter):
+    """CMA-ES, VD-CMA: generation 1 is inside the loop."""
+    if maxiter < 1:
+        raise ValueError(f"runs > 1 needs maxiter >= 1 (maxiter={maxiter})")
+
+
+def seeds_of(R, seed):
+    """An integer s gives s + r to run r; a sequence of R integers is taken as given."""
+    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
+        return [int(seed) + r for r in range(R)]
+    if seed is not None and np.ndim(seed) == 1 and len(seed) == R:
+        return [int(s) for s in seed]
+    raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
+
+
+def standardised(lower, upper, x0, R):
+    """CMA-ES, VD-CMA: xm, xstd of the box and the caller's ``x0`` -- (n,) for all runs or (R, n) -- in the model's
+    coordinates, (R, n); None without an ``x0``."""
+    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
+    if x0 is None:
+        return xm, xstd, None
+    return xm, xstd, np.ascontiguousarray(np.broadcast_to((np.asarray(x0, dtype=np.float64) - xm) / xstd, (R, len(lower))))
+
+
+def set_model_scalars(a, n, mu, fun_id, maxiter, sigma, xtol, ftol):
+    """CMA-ES, VD-CMA: the struct fields the two share (``ilim``: cmaes/_cmaes.py:221)."""
+    a.n, a.mu, a.fun_id, a.maxiter = n, mu, fun_id, maxiter
+    a.ilim = int(10.0 + 30.0 * n / a.P)
+    a.sigma = a.insigma = sigma
+    a.xtol, a.ftol = xtol, ftol
+
+
+class Batch:
+    """R runs for one ``sx_*_runs_launch``: the device context, the argument struct ``a`` and ``dev``, the device tensors its
+    pointers name (inputs, outputs, workspace).  Pointers that are never bound stay NULL."""
+
+    def __init__(self, entry, args, seeds, P):
+        self.entry, self.a, self.seeds, self.R, self.P = entry, args, seeds, len(seeds), P
+        self.ctx = _device.Context()
+        self.dev, self.out = {}, ()
+        args.R, args.P = self.R, P
+
+    def stream(self):
+        """Uploads, fills and read-backs go inside ``with batch.stream():``."""
+        return _device.torch().cuda.stream(self.ctx.stream)
+
+    def bind(self, **tensors):
+        for name, tensor in tensors.items():
+            self.dev[name] = tensor
+            setattr(self.a, name, tensor.data_ptr())
+
+    def upload_keys(self):
+        keys = np.array([_rng.philox_key(s) for s in self.seeds], dtype=np.uint32)
+        self.bind(keys=self.ctx.upload_async(keys.view(np.int32)))
+
+    def outputs(self, n, optional, wanted, extra=()):
+        """xs, funs, nits, statuses, the method's ``extra`` per-run doubles, and those of ``optional`` (name -> (shape,
+        dtype); None: double) that ``wanted`` names."""
+        t, R = _device.torch(), self.R
+        spec = {"xs": ((R, n), None), "funs": ((R,), None), "nits": ((R,), t.int64), "statuses": ((R,), t.int32)}
+        spec.update({name: ((R,), None) for name in extra})
+        spec.update({name: optional[name] for name in wanted})
+        for name in ("xs", "funs", *extra, "nits", "statuses", *wanted):
+            self.bind(**{name: self.ctx.empty(*spec[name])})
+        self.out = ("xs", "funs", "nits", "statuses", *extra, *wanted)
+
+    def launch(self):
+        _lib.check(getattr(self.ctx.L, self.entry)(C.byref(self.a), self.ctx.stream_ptr), self.entry)
+
+    def fetch(self):
+        """The outputs as numpy arrays, by name."""
+        with self.stream():
+            return {name: self.dev[name].cpu().numpy() for name in self.out}
+
+
+def result(out, P):
+    """The best run (``np.argmin``) as the result, with every run's outputs beside it."""
+    xs, funs, nits, statuses = out["xs"], out["funs"], out["nits"], out["statuses"]
+    best = int(np.argmin(funs))
+    status = int(statuses[best])
+    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
+                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best, **out)

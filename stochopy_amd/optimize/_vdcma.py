@@ -18,14 +18,13 @@ sharded run forms t_k from the gathered y as (y / d) . vn (csrc/sx_vd_loop.hip v
 differ in the last bits of every t_k, so there the sharded run follows the one-GPU run to rounding, not bit for bit.
 """
 
-import ctypes as C
 import os
 
 import numpy as np
 
 from .. import _device, _lib, _rng
-from . import _common, _evolution
-from ._helpers import OptimizeResult, register
+from . import _common, _evolution, _runs
+from ._helpers import register
 
 __all__ = ["minimize"]
 
@@ -64,9 +63,7 @@ def minimize(
     ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  Needs ``rng="philox"``, a factory objective, one
     GPU, no callback, no ``return_all``, ``constraints=None``, ``ndim >= 6`` and a shape that fits one workgroup's LDS
     (``sx_vd_runs_lds_bytes``: popsize 10 up to ndim 512 and beyond)."""
-    if runs is not None and (not isinstance(runs, (int, np.integer)) or isinstance(runs, bool) or runs < 1):
-        raise ValueError(f"runs={runs!r}: expected the number of independent runs, an integer >= 1")
-    batched_runs = runs is not None and runs > 1
+    batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     if batched_runs and x0 is not None and np.ndim(x0) == 2:  # a point per run
@@ -117,28 +114,10 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
     """``runs=R``: R independent runs, one workgroup each, one launch (csrc/sx_vd_runs.hip).  Everything that can be
     refused is refused before the device is touched."""
     n = len(lower)
-    if rng != "philox":
-        raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
-    if not isinstance(fun_id, int):
-        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
-                         "(factory.batched and plain callables run between kernels)")
-    if workers not in (None, 1):
-        raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
-    if callback is not None:
-        raise ValueError("runs > 1 takes no callback: a run never leaves its kernel")
-    if return_all:
-        raise ValueError("runs > 1 keeps no history (return_all=True): a run never leaves its kernel")
-    if constraints is not None:
-        raise ValueError(f"runs > 1 serves constraints=None (constraints={constraints!r}: the boundary-weight bookkeeping "
-                         "is not part of the run's kernel)")
-    if isinstance(seed, (int, np.integer)) and not isinstance(seed, bool):
-        seeds = [int(seed) + r for r in range(R)]
-    elif seed is not None and np.ndim(seed) == 1 and len(seed) == R:
-        seeds = [int(s) for s in seed]
-    else:
-        raise ValueError(f"runs={R} needs seed = an integer s (run r uses s + r) or a sequence of {R} integers")
-    if maxiter < 1:
-        raise ValueError(f"runs > 1 needs maxiter >= 1 (maxiter={maxiter})")
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_constraints(constraints)
+    seeds = _runs.seeds_of(R, seed)
+    _runs.refuse_maxiter(maxiter)
     if n < RUNS_MIN_DIM:
         raise ValueError(f"runs > 1 with method='vdcma' needs ndim >= {RUNS_MIN_DIM} (ndim = {n}): below, the reference's "
                          "learning rates c1 and cmu are zero or negative (cfactor = (ndim - 5) / 6) and the model never "
@@ -149,49 +128,40 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
         raise ValueError(f"runs > 1 keeps a run's model and staging rows in one workgroup's LDS: popsize {P} x {n} variables "
                          f"(mu = {mu}) needs 2 <= popsize, mu >= 1, ndim <= {int(_lib.lib().sx_wide_from())} and at most "
                          "160 KiB")
+    batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol)
+    batch.launch()
+    return _runs.result(batch.fetch(), P)
+
+
+def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, outputs=()):
+    """The batch of one sx_vd_runs_launch; ``outputs``: of the optional ones, ``"nfevs"`` and every run's final model --
+    ``"xmeans"`` (standardised), ``"dvecs"``, ``"vvecs"``."""
+    n, R = len(lower), len(seeds)
     mu, w, mueff, cc, c1, cmu = _strategy_constants(n, P, muperc)
-    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
+    xm, xstd, given = _runs.standardised(lower, upper, x0, R)
     # what the single run of each seed draws on the host (_evolution._DeviceRun, _VdDeviceRun._model): its private legacy
     # stream gives the initial mean -- unless the caller gave one -- and right after it the initial direction
-    xmean0, vvec0 = np.empty((R, n)), np.empty((R, n))
-    if x0 is not None:
-        xmean0[:] = (np.asarray(x0, dtype=np.float64) - xm) / xstd
+    xmean0, vvec0 = np.empty((R, n)) if given is None else given, np.empty((R, n))
     for r, s in enumerate(seeds):
         init = _rng.make_init_stream("philox", s)
-        if x0 is None:
+        if given is None:
             xmean0[r] = init.uniform(-1.0, 1.0, n)
         vvec0[r] = init.randn(n) / np.sqrt(n)
-
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
+    batch = _runs.Batch("sx_vd_runs_launch", _lib.SxVdRunsArgs(), seeds, P)
+    a, ctx = batch.a, batch.ctx
+    with batch.stream():
+        batch.upload_keys()
         d_xmean0, d_vvec0, d_w = ctx.upload(xmean0), ctx.upload(vvec0), ctx.upload(w)
         d_std = ctx.upload_async(np.concatenate([xm, xstd]))
-        d_work = ctx.empty((int(ctx.L.sx_vd_runs_workspace_bytes(R, maxiter)) // 8,))
-        xs, funs, sigmas = ctx.empty((R, n)), ctx.empty((R,)), ctx.empty((R,))
-        nits, statuses = ctx.empty((R,), dtype=t.int64), ctx.empty((R,), dtype=t.int32)
-        a = _lib.SxVdRunsArgs()
-        a.keys, a.xmean0, a.vvec0, a.w = d_keys.data_ptr(), d_xmean0.data_ptr(), d_vvec0.data_ptr(), d_w.data_ptr()
-        a.xm, a.xstd = d_std[:n].data_ptr(), d_std[n:].data_ptr()
-        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
-                                                    statuses.data_ptr())
-        a.nfevs, a.sigmas, a.xmeans, a.dvecs, a.vvecs = None, sigmas.data_ptr(), None, None, None
-        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, fun_id, maxiter
-        a.ilim = int(10.0 + 30.0 * n / P)
-        a.mueff, a.cc, a.c1, a.cmu = mueff, cc, c1, cmu
-        a.cs, a.ds, a.wsum = 0.3, float(np.sqrt(n)), float(w.sum())
-        a.sigma = a.insigma = sigma
-        a.xtol, a.ftol = xtol, ftol
-        _lib.check(ctx.L.sx_vd_runs_launch(C.byref(a), ctx.stream_ptr), "sx_vd_runs_launch")
-        xs, funs, nits, statuses, sigmas = (xs.cpu().numpy(), funs.cpu().numpy(), nits.cpu().numpy(), statuses.cpu().numpy(),
-                                            sigmas.cpu().numpy())
-    best = int(np.argmin(funs))
-    status = int(statuses[best])
-    return OptimizeResult(x=xs[best].copy(), success=status >= 0, status=status, message=_common.messages[status],
-                          fun=float(funs[best]), nfev=int(nits.sum()) * P, nit=int(nits[best]), run=best,
-                          xs=xs, funs=funs, nits=nits, statuses=statuses, sigmas=sigmas)
+        batch.bind(xmean0=d_xmean0, vvec0=d_vvec0, w=d_w, xm=d_std[:n], xstd=d_std[n:],
+                   work=ctx.empty((int(ctx.L.sx_vd_runs_workspace_bytes(R, maxiter)) // 8,)))
+        vec = ((R, n), None)
+        batch.outputs(n, {"nfevs": ((R,), _device.torch().int64), "xmeans": vec, "dvecs": vec, "vvecs": vec}, outputs,
+                      extra=("sigmas",))
+    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, sigma, xtol, ftol)
+    a.mueff, a.cc, a.c1, a.cmu = mueff, cc, c1, cmu
+    a.cs, a.ds, a.wsum = 0.3, float(np.sqrt(n)), float(w.sum())
+    return batch
 
 
 class _VdDeviceRun(_evolution._DeviceRun):

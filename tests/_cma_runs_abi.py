@@ -1,10 +1,11 @@
-"""The batched-runs CMA-ES kernel (csrc/sx_cma_runs.hip) through its C ABI, restated for the tests: the LDS layout the kernel's
-header comment documents, in bytes; launch_runs, one sx_cma_runs_launch filled as optimize/_cmaes.py _minimize_runs fills it
-but with real nfevs / sigmas / xmeans buffers (optimize.minimize(runs=R) passes nfevs = xmeans = NULL); generation_one, a plain
-numpy reference of a run's first generation; and the shapes the generation-1 tests share.  A plain helper module (imported,
-not collected)."""
+"""The batched-runs CMA-ES kernel (csrc/sx_cma_runs.hip) for the tests: the LDS layout the kernel's header comment documents,
+restated in bytes; launch_runs, the batch optimize.minimize(runs=R) launches (optimize/_cmaes.py _runs_batch) but with real
+nfevs / xmeans buffers (minimize() passes nfevs = xmeans = NULL); generation_one, a plain numpy reference of a run's first
+generation; and the shapes the generation-1 tests share.  A plain helper module (imported, not collected)."""
 
 import numpy as np
+
+from _runs_abi import FILL, largest, launch_filled
 
 LDS_LIMIT = 160 * 1024
 MAX_DIM = 32
@@ -29,16 +30,8 @@ def workspace_bytes(R, maxiter):
 
 
 def largest_popsize(lib, n):
-    """The largest P with sx_cma_runs_lds_bytes(P, n) > 0, by bisection (the function refuses everything above it)."""
-    lo, hi = 2, 1 << 20
-    assert lib.sx_cma_runs_lds_bytes(lo, n) > 0 and lib.sx_cma_runs_lds_bytes(hi, n) < 0
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if lib.sx_cma_runs_lds_bytes(mid, n) > 0:
-            lo = mid
-        else:
-            hi = mid
-    return lo
+    """The largest P with sx_cma_runs_lds_bytes(P, n) > 0 (the function refuses everything above it)."""
+    return largest(lambda p: lib.sx_cma_runs_lds_bytes(p, n) > 0, 2, 1 << 20)
 
 
 def jacobi_doubles(n):
@@ -67,52 +60,21 @@ def standardise(lower, upper):
 
 
 def launch_runs(objective, lower, upper, P, seeds, x0=None, maxiter=100, sigma=0.1, muperc=0.5, xtol=1e-8, ftol=1e-8):
-    """One sx_cma_runs_launch of len(seeds) runs of `objective` (a factory name), its arguments filled exactly as
-    optimize/_cmaes.py _minimize_runs fills them, but with real nfevs / sigmas / xmeans buffers.  lower / upper: one value per
-    dimension.  x0: None (every run draws its initial mean as the single run of its seed does), (n,) or (R, n), in the caller's
-    coordinates.  Returns xs (R, n), funs (R,), nits (R,), statuses (R,), nfevs (R,), sigmas (R,), xmeans (R, n; standardised)."""
-    import ctypes as C
+    """One sx_cma_runs_launch of len(seeds) runs of `objective` (a factory name): the batch minimize() launches
+    (optimize/_cmaes.py _runs_batch), with real nfevs / xmeans buffers.  lower / upper: one value per dimension.  x0: None
+    (every run draws its initial mean as the single run of its seed does), (n,) or (R, n), in the caller's coordinates.
+    Returns xs (R, n), funs (R,), nits (R,), statuses (R,), nfevs (R,), sigmas (R,), xmeans (R, n; standardised)."""
+    from stochopy_amd import _lib
+    from stochopy_amd.optimize._cmaes import _runs_batch
 
-    from stochopy_amd import _device, _lib, _rng
-    from stochopy_amd.optimize._cmaes import _strategy_constants
-
-    seeds = [int(s) for s in seeds]
-    R = len(seeds)
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
-    n = len(lower)
-    mu, w, *constants = _strategy_constants(n, P, muperc)
-    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
-    if x0 is None:
-        xmean0 = np.array([np.random.RandomState(s & 0xFFFFFFFF).uniform(-1.0, 1.0, n) for s in seeds])
-    else:
-        xmean0 = np.ascontiguousarray(np.broadcast_to((np.asarray(x0, dtype=np.float64) - xm) / xstd, (R, n)))
-
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
-        d_xmean0, d_std, d_w = ctx.upload(xmean0), ctx.upload_async(np.concatenate([xm, xstd])), ctx.upload(w)
-        d_work = ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,))
-        # filled with values no run produces: an element the kernel does not write cannot pass for a result
-        fill = -12345.678
-        xs, funs, sigmas, xmeans = [t.full(shape, fill, dtype=t.float64, device=ctx.device) for shape in ((R, n), (R,), (R,), (R, n))]
-        nits, nfevs = [t.full((R,), -7, dtype=t.int64, device=ctx.device) for _ in range(2)]
-        statuses = t.full((R,), 77, dtype=t.int32, device=ctx.device)
-        a = _lib.SxCmaRunsArgs()
-        a.keys, a.xmean0, a.xm, a.xstd, a.w = (d_keys.data_ptr(), d_xmean0.data_ptr(), d_std[:n].data_ptr(),
-                                               d_std[n:].data_ptr(), d_w.data_ptr())
-        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
-                                                    statuses.data_ptr())
-        a.nfevs, a.sigmas, a.xmeans = nfevs.data_ptr(), sigmas.data_ptr(), xmeans.data_ptr()
-        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, _lib.FUN_IDS[objective], maxiter
-        a.ilim = int(10.0 + 30.0 * n / P)
-        a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
-        a.sigma = a.insigma = sigma
-        a.xtol, a.ftol = xtol, ftol
-        _lib.check(ctx.L.sx_cma_runs_launch(C.byref(a), ctx.stream_ptr), "sx_cma_runs_launch")
-        out = tuple(v.cpu().numpy() for v in (xs, funs, nits, statuses, nfevs, sigmas, xmeans))
-    assert not (out[0] == fill).any() and not (out[6] == fill).any() and not (out[5] == fill).any()
+    batch = _runs_batch([int(s) for s in seeds], _lib.FUN_IDS[objective], lower, upper, x0, maxiter, P, sigma, muperc, xtol,
+                        ftol, outputs=("nfevs", "xmeans"))
+    # filled with values no run produces: an element the kernel does not write cannot pass for a result
+    fills = dict(dict.fromkeys(("xs", "funs", "sigmas", "xmeans"), FILL), nits=-7, nfevs=-7, statuses=77)
+    out = launch_filled(batch, fills)
+    out = tuple(out[k] for k in ("xs", "funs", "nits", "statuses", "nfevs", "sigmas", "xmeans"))
+    assert not (out[0] == FILL).any() and not (out[6] == FILL).any() and not (out[5] == FILL).any()
     assert (out[2] > 0).all() and (out[4] > 0).all() and (out[3] != 77).all()
     return out
 

@@ -1,11 +1,12 @@
-"""The batched-runs VD-CMA kernel (csrc/sx_vd_runs.hip) through its C ABI, restated for the tests: the LDS layout the kernel's
-header comment documents, in bytes; launch_runs, one sx_vd_runs_launch filled as optimize/_vdcma.py _minimize_runs fills it
-but with real nfevs / sigmas / xmeans / dvecs / vvecs buffers; and a plain numpy generation 1.  A plain helper module
-(imported, not collected)."""
+"""The batched-runs VD-CMA kernel (csrc/sx_vd_runs.hip) for the tests: the LDS layout the kernel's header comment documents,
+restated in bytes; launch_runs, the batch optimize.minimize(runs=R) launches (optimize/_vdcma.py _runs_batch) but with real
+nfevs / xmeans / dvecs / vvecs buffers; and a plain numpy generation 1.  A plain helper module (imported, not collected)."""
 
 import math
 
 import numpy as np
+
+from _runs_abi import FILL, largest, launch_filled
 
 LDS_LIMIT = 160 * 1024
 MIN_DIM = 6
@@ -44,18 +45,6 @@ def workspace_bytes(R, maxiter):
     return 8 * R * maxiter
 
 
-def largest(fits, lo, hi):
-    """The largest k in [lo, hi) with fits(k), fits being true up to some point and false beyond."""
-    assert fits(lo) and not fits(hi)
-    while hi - lo > 1:
-        mid = (lo + hi) // 2
-        if fits(mid):
-            lo = mid
-        else:
-            hi = mid
-    return lo
-
-
 def largest_popsize(lib, n):
     return largest(lambda p: lib.sx_vd_runs_lds_bytes(p, n) > 0, 2, 1 << 20)
 
@@ -72,58 +61,16 @@ def launch_runs(objective, lower, upper, P, seeds, x0=None, maxiter=100, sigma=0
     """One sx_vd_runs_launch of len(seeds) runs of `objective` (a factory name) with every optional output.  lower / upper:
     one value per dimension.  x0: None, (n,) or (R, n), in the caller's coordinates.  Returns a dict of numpy arrays: xs, funs,
     nits, statuses, nfevs, sigmas, xmeans (standardised), dvecs, vvecs."""
-    import ctypes as C
+    from stochopy_amd import _lib
+    from stochopy_amd.optimize._vdcma import _runs_batch
 
-    from stochopy_amd import _device, _lib, _rng
-    from stochopy_amd.optimize._vdcma import _strategy_constants
-
-    seeds = [int(s) for s in seeds]
-    R = len(seeds)
     lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
-    n = len(lower)
-    mu, w, mueff, cc, c1, cmu = _strategy_constants(n, P, muperc)
-    xm, xstd = 0.5 * (upper + lower), 0.5 * (upper - lower)
-    xmean0, vvec0 = np.empty((R, n)), np.empty((R, n))
-    if x0 is not None:
-        xmean0[:] = (np.asarray(x0, dtype=np.float64) - xm) / xstd
-    for r, s in enumerate(seeds):
-        init = np.random.RandomState(s & 0xFFFFFFFF)
-        if x0 is None:
-            xmean0[r] = init.uniform(-1.0, 1.0, n)
-        vvec0[r] = init.randn(n) / np.sqrt(n)
-
-    ctx = _device.Context()
-    t = _device.torch()
-    with t.cuda.stream(ctx.stream):
-        keys = np.array([_rng.philox_key(s) for s in seeds], dtype=np.uint32)
-        d_keys = ctx.upload_async(keys.view(np.int32))
-        d_xmean0, d_vvec0, d_w = ctx.upload(xmean0), ctx.upload(vvec0), ctx.upload(w)
-        d_std = ctx.upload_async(np.concatenate([xm, xstd]))
-        d_work = ctx.empty((int(ctx.L.sx_vd_runs_workspace_bytes(R, maxiter)) // 8,))
-        fill = -12345.678  # no run produces it: an element the kernel does not write cannot pass for a result
-        xs, xmeans, dvecs, vvecs = [t.full((R, n), fill, dtype=t.float64, device=ctx.device) for _ in range(4)]
-        funs, sigmas = [t.full((R,), fill, dtype=t.float64, device=ctx.device) for _ in range(2)]
-        nits, nfevs = [t.full((R,), -7, dtype=t.int64, device=ctx.device) for _ in range(2)]
-        statuses = t.full((R,), 77, dtype=t.int32, device=ctx.device)
-        a = _lib.SxVdRunsArgs()
-        a.keys, a.xmean0, a.vvec0, a.w = d_keys.data_ptr(), d_xmean0.data_ptr(), d_vvec0.data_ptr(), d_w.data_ptr()
-        a.xm, a.xstd = d_std[:n].data_ptr(), d_std[n:].data_ptr()
-        a.work, a.xs, a.funs, a.nits, a.statuses = (d_work.data_ptr(), xs.data_ptr(), funs.data_ptr(), nits.data_ptr(),
-                                                    statuses.data_ptr())
-        a.nfevs, a.sigmas, a.xmeans, a.dvecs, a.vvecs = (nfevs.data_ptr(), sigmas.data_ptr(), xmeans.data_ptr(),
-                                                         dvecs.data_ptr(), vvecs.data_ptr())
-        a.R, a.P, a.n, a.mu, a.fun_id, a.maxiter = R, P, n, mu, _lib.FUN_IDS[objective], maxiter
-        a.ilim = int(10.0 + 30.0 * n / P)
-        a.mueff, a.cc, a.c1, a.cmu = mueff, cc, c1, cmu
-        a.cs, a.ds, a.wsum = 0.3, float(np.sqrt(n)), float(w.sum())
-        a.sigma = a.insigma = sigma
-        a.xtol, a.ftol = xtol, ftol
-        _lib.check(ctx.L.sx_vd_runs_launch(C.byref(a), ctx.stream_ptr), "sx_vd_runs_launch")
-        out = dict(xs=xs, funs=funs, nits=nits, statuses=statuses, nfevs=nfevs, sigmas=sigmas, xmeans=xmeans, dvecs=dvecs,
-                   vvecs=vvecs)
-        out = {k: v.cpu().numpy() for k, v in out.items()}
+    batch = _runs_batch([int(s) for s in seeds], _lib.FUN_IDS[objective], lower, upper, x0, maxiter, P, sigma, muperc, xtol,
+                        ftol, outputs=("nfevs", "xmeans", "dvecs", "vvecs"))
+    fills = dict(dict.fromkeys(("xs", "funs", "sigmas", "xmeans", "dvecs", "vvecs"), FILL), nits=-7, nfevs=-7, statuses=77)
+    out = launch_filled(batch, fills)
     for k in ("xs", "xmeans", "dvecs", "vvecs", "sigmas"):
-        assert not (out[k] == fill).any(), k
+        assert not (out[k] == FILL).any(), k
     assert (out["nits"] > 0).all() and (out["nfevs"] == out["nits"] * P).all() and (out["statuses"] != 77).all()
     return out
 

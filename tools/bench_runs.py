@@ -1,23 +1,29 @@
 #!/usr/bin/env python3
-"""Throughput of many independent DE runs in one launch (options["runs"], csrc/sx_de_runs.hip) on one MI355X, next to the
-only way to do the same work without it: a Python loop of single minimize() calls.
+"""Throughput of many independent runs in one launch (options["runs"]; csrc/sx_de_runs.hip, sx_pso_runs.hip, sx_cma_runs.hip,
+sx_vd_runs.hip) on one MI355X, next to the only way to do the same work without it: a Python loop of single minimize() calls.
 
-Workload: rosenbrock, n = 32, popsize = 32, best1bin, maxiter = 200, tolerances that never trigger (every run does its 200
-generations), Philox draws, deferred updating.
-    runs R in {256, 4096, 16384}   ONE sx_de_runs_launch of R workgroups; time = device events around a round's launches
-                                   (each a whole batch from the initial population, repeated back to back for ~--window
-                                   seconds), divided by their number.  "call" is the wall time of one whole
-                                   minimize(..., runs=R) call on top: uploads, launch, results back on the host.
+Workloads (WORKLOADS below): maxiter = 200, xtol = 0 and ftol = -1 (rules 0 and 1 never trigger), Philox draws.
+    de            rosenbrock, n = 32, popsize = 32, best1bin, deferred updating
+    pso, cpso     ackley, n = 32, popsize = 32, deferred updating; cpso with competitivity 1
+    cmaes         rosenbrock, two shapes: n = 10, popsize = 10 (the reference's default population 4 + 3 ln n) and n = 32,
+                  popsize = 64; a run that another rule ends early is counted with the generations it did
+    vdcma         rosenbrock, two shapes: n = 64, popsize = 16 (the default population) and n = 256, popsize = 20
+Every run of de, pso, cpso and vdcma must do its 200 generations (checked).
+    runs R in {256, 4096, 16384}   ONE sx_*_runs_launch of R workgroups -- the batch minimize(..., runs=R) builds (each method's
+                                   _runs_batch), built once and launched again and again; time = device events around a
+                                   round's launches (each a whole batch from the start, back to back for ~--window seconds),
+                                   divided by their number.  "call" is the wall time of one whole minimize(..., runs=R) call on
+                                   top: the host's draws, uploads, launch, results back on the host.
     loop                           --loop-calls (64) single minimize() calls with the same settings and seeds s, s+1, ...,
                                    wall time with the stream drained at the end.  The loop's rate does not depend on how many
                                    runs are asked for: the figure beside R runs IS this rate, not a measurement of R calls.
 Everything is warmed up once, then the configurations take turns for --rounds rounds; a line gives the median and the spread
 (min .. max) of its rounds, in objective evaluations per second (nit x popsize per run).
 
-    python tools/bench_runs.py [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
+    python tools/bench_runs.py [--method de|pso|cpso|cmaes|vdcma ...] [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
 """
 import argparse
-import ctypes as C
+import importlib
 import json
 import os
 import sys
@@ -28,70 +34,86 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-N, P, MAXITER, SEED = 32, 32, 200, 3
+MAXITER, SEED = 200, 3
 RUNS = (256, 4096, 16384)
-OPTS = {"popsize": P, "maxiter": MAXITER, "strategy": "best1bin", "xtol": 0.0, "ftol": -1.0, "rng": "philox",
-        "updating": "deferred", "backend": "hip"}
-BOUNDS = [[-5.12, 5.12]] * N
+COMMON = {"maxiter": MAXITER, "xtol": 0.0, "ftol": -1.0, "rng": "philox", "backend": "hip"}
+PSO = (0.7298, 1.49618, 1.49618)  # inertia, cognitivity, sociability
+# module of stochopy_amd/optimize whose _runs_batch builds the batch; `own`: its arguments between popsize and xtol;
+# shapes: (ndim, popsize); half: the box is [-half, half]^ndim; full: every run must do all its generations
+WORKLOADS = {
+    "de": dict(module="_de", objective="rosenbrock", shapes=((32, 32),), half=5.12, full=True, warm_loop=8,
+               own=(0.5, 0.9, "best1bin", None), opts={"strategy": "best1bin", "updating": "deferred"}),
+    "pso": dict(module="_cpso", objective="ackley", shapes=((32, 32),), half=5.12, full=True, warm_loop=8,
+                own=PSO + (None, None), opts={"updating": "deferred"}),
+    "cpso": dict(module="_cpso", objective="ackley", shapes=((32, 32),), half=5.12, full=True, warm_loop=8,
+                 own=PSO + (1.0, None), opts={"updating": "deferred", "competitivity": 1.0}),
+    "cmaes": dict(module="_cmaes", objective="rosenbrock", shapes=((10, 10), (32, 64)), half=3.0, full=False, warm_loop=4,
+                  own=(0.1, 0.5), opts={"sigma": 0.1}),
+    "vdcma": dict(module="_vdcma", objective="rosenbrock", shapes=((64, 16), (256, 20)), half=3.0, full=True, warm_loop=4,
+                  own=(0.1, 0.5), opts={"sigma": 0.1}),
+}
 
 
-class DeviceBatch:
-    """The buffers and arguments of one batch, launched as optimize.minimize(..., runs=R) does."""
+class Config:
+    """One method at one shape: the minimize() calls, and the timed batch of R runs."""
 
-    def __init__(self, ctx, R):
-        from stochopy_amd import _device, _lib, _rng
+    def __init__(self, sa, method, n, P):
+        w = WORKLOADS[method]
+        self.sa, self.method, self.n, self.P, self.full = sa, method, n, P, w["full"]
+        self.fun, self.bounds = getattr(sa.factory, w["objective"]), [[-w["half"], w["half"]]] * n
+        self.options = dict(COMMON, popsize=P, **w["opts"])
 
-        t = _device.torch()
-        self.ctx, self.L, self.R = ctx, ctx.L, R
-        keys = np.array([_rng.philox_key(SEED + r) for r in range(R)], dtype=np.uint32)
-        self.dev = dev = {"keys": ctx.upload(keys.view(np.int32)), "lower": ctx.upload(np.full(N, -5.12)),
-                          "upper": ctx.upload(np.full(N, 5.12)), "xs": ctx.empty((R, N)), "funs": ctx.empty((R,)),
-                          "nits": ctx.empty((R,), dtype=t.int64), "statuses": ctx.empty((R,), dtype=t.int32)}
-        self.a = a = _lib.SxDeRunsArgs()
-        for name in dev:
-            setattr(a, name, _device.ptr(dev[name]))
-        a.R, a.P, a.x0_stride, a.n = R, P, 0, N
-        a.fun_id, a.strategy, a.constraints, a.maxiter = _lib.FUN_IDS["rosenbrock"], _lib.DE_STRATEGIES["best1bin"], 0, MAXITER
-        a.F, a.CR, a.xtol, a.ftol = 0.5, 0.9, OPTS["xtol"], OPTS["ftol"]
-        self.evals = R * MAXITER * P
-
-    def timed(self, launches=1):
-        """Seconds per launch (a whole batch), over `launches` launches back to back."""
+    def batch(self, R):
         from stochopy_amd import _lib
 
-        t = __import__("torch")
-        with t.cuda.stream(self.ctx.stream):
-            e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(launches):
-                _lib.check(self.L.sx_de_runs_launch(C.byref(self.a), self.ctx.stream_ptr), "sx_de_runs_launch")
-            e1.record()
-            e1.synchronize()
-        assert int(self.dev["nits"].min()) == MAXITER  # every run did all its generations
-        return e0.elapsed_time(e1) * 1e-3 / launches
+        w = WORKLOADS[self.method]
+        build = importlib.import_module("stochopy_amd.optimize." + w["module"])._runs_batch
+        return build([SEED + r for r in range(R)], _lib.FUN_IDS[w["objective"]], np.full(self.n, -w["half"]),
+                     np.full(self.n, w["half"]), None, MAXITER, self.P, *w["own"], COMMON["xtol"], COMMON["ftol"])
+
+    def minimize(self, **more):
+        return self.sa.optimize.minimize(self.fun, self.bounds, method=self.method, options=dict(self.options, **more))
+
+    def whole_call(self, R):
+        """Wall seconds of one minimize(..., runs=R) call."""
+        t0 = time.perf_counter()
+        res = self.minimize(seed=SEED, runs=R)
+        dt = time.perf_counter() - t0
+        assert res.nfev == int(res.nits.sum()) * self.P and (not self.full or res.nfev == R * MAXITER * self.P)
+        return dt
+
+    def loop_of_calls(self, ctx, calls):
+        """Wall seconds and evaluations of `calls` single minimize() calls, one after the other."""
+        t0 = time.perf_counter()
+        evals = 0
+        for r in range(calls):
+            res = self.minimize(seed=SEED + r)
+            assert not self.full or res.nit == MAXITER
+            evals += res.nfev
+        ctx.sync()
+        return time.perf_counter() - t0, evals
 
 
-def whole_call(sa, R):
-    """Wall seconds of one minimize(..., runs=R) call."""
-    t0 = time.perf_counter()
-    res = sa.optimize.minimize(sa.factory.rosenbrock, BOUNDS, method="de", options=dict(OPTS, seed=SEED, runs=R))
-    dt = time.perf_counter() - t0
-    assert res.nfev == R * MAXITER * P
-    return dt
-
-
-def loop_of_calls(sa, ctx, calls):
-    """Wall seconds per call of `calls` single minimize() calls, one after the other."""
-    t0 = time.perf_counter()
-    for r in range(calls):
-        res = sa.optimize.minimize(sa.factory.rosenbrock, BOUNDS, method="de", options=dict(OPTS, seed=SEED + r))
-        assert res.nit == MAXITER
-    ctx.sync()
-    return (time.perf_counter() - t0) / calls
+def timed(config, batch, launches=1):
+    """Seconds per launch (a whole batch), over `launches` launches back to back; the evaluations one launch did and the share
+    of its runs that did all their generations."""
+    t = __import__("torch")
+    with batch.stream():
+        e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            batch.launch()
+        e1.record()
+        e1.synchronize()
+    nits = batch.dev["nits"]
+    full = float((nits == MAXITER).double().mean())
+    assert not config.full or full == 1.0, "a run ended before its %d generations" % MAXITER
+    return e0.elapsed_time(e1) * 1e-3 / launches, int(nits.sum()) * config.P, full
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--method", nargs="+", choices=sorted(WORKLOADS), default=["de"])
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per timed round")
     ap.add_argument("--loop-calls", type=int, default=64)
@@ -101,39 +123,49 @@ def main():
     from stochopy_amd import _device
 
     ctx = _device.Context()
-    batches = [DeviceBatch(ctx, R) for R in RUNS]
+    configs = [Config(sa, method, n, P) for method in args.method for n, P in WORKLOADS[method]["shapes"]]
+    batches = [(c, R, c.batch(R)) for c in configs for R in RUNS]
     launches = {}
-    for b in batches:
-        b.timed()  # warm-up: code object load
-        launches[b.R] = max(1, int(round(args.window / b.timed())))
-        whole_call(sa, b.R)
-    loop_of_calls(sa, ctx, 8)  # warm-up: graphs of the chained kernel, allocator
-    times = {b.R: [] for b in batches}
-    calls = {b.R: [] for b in batches}
-    loop = []
+    for c, R, b in batches:
+        timed(c, b)  # warm-up: code object load
+        launches[b] = max(1, int(round(args.window / timed(c, b)[0])))
+        c.whole_call(R)
+    for c in configs:
+        c.loop_of_calls(ctx, WORKLOADS[c.method]["warm_loop"])  # warm-up: graphs and code objects of the single run, allocator
+    times, calls = {b: [] for _, _, b in batches}, {b: [] for _, _, b in batches}
+    loop = {c: [] for c in configs}
     for _ in range(args.rounds):
-        for b in batches:
-            times[b.R].append(b.timed(launches[b.R]))
-            calls[b.R].append(whole_call(sa, b.R))
-        loop.append(loop_of_calls(sa, ctx, args.loop_calls))
-    loop = np.array(loop)
-    per_call = MAXITER * P
-    loop_rate = per_call / float(np.median(loop))
-    lines = [{"config": "loop of single minimize() calls", "calls_timed": args.loop_calls, "rounds": args.rounds,
-              "seconds_per_call_median": float(np.median(loop)), "seconds_per_call_min": float(loop.min()),
-              "seconds_per_call_max": float(loop.max()), "us_per_generation": float(np.median(loop)) / MAXITER * 1e6,
-              "evals_per_s": loop_rate, "evals_per_s_spread": [per_call / float(loop.max()), per_call / float(loop.min())]}]
-    for b in batches:
-        ts, cs = np.array(times[b.R]), np.array(calls[b.R])
-        rate = b.evals / float(np.median(ts))
-        lines.append({"config": "runs", "runs": b.R, "ndim": N, "popsize": P, "maxiter": MAXITER, "rounds": args.rounds,
-                      "launches_per_round": launches[b.R], "seconds_median": float(np.median(ts)),
-                      "seconds_min": float(ts.min()), "seconds_max": float(ts.max()), "evals_per_s": rate,
-                      "evals_per_s_spread": [b.evals / float(ts.max()), b.evals / float(ts.min())],
-                      "call_seconds_median": float(np.median(cs)), "call_evals_per_s": b.evals / float(np.median(cs)),
-                      "loop_evals_per_s": loop_rate, "loop_seconds_for_these_runs_at_that_rate": b.R * float(np.median(loop)),
-                      "ratio_kernel_to_loop": rate / loop_rate,
-                      "ratio_call_to_loop": b.evals / float(np.median(cs)) / loop_rate})
+        for c, R, b in batches:
+            times[b].append(timed(c, b, launches[b]))
+            calls[b].append(c.whole_call(R))
+        for c in configs:
+            loop[c].append(c.loop_of_calls(ctx, args.loop_calls))
+    lines, loop_rate = [], {}
+    for c in configs:
+        secs = np.array([s for s, _ in loop[c]])
+        rates = np.array([e / s for s, e in loop[c]])
+        gens = np.array([e / c.P for _, e in loop[c]])
+        loop_rate[c] = float(np.median(rates))
+        lines.append({"config": "loop of single minimize() calls", "method": c.method, "ndim": c.n, "popsize": c.P,
+                      "calls_timed": args.loop_calls, "rounds": args.rounds,
+                      "seconds_per_call_median": float(np.median(secs)) / args.loop_calls,
+                      "seconds_per_call_min": float(secs.min()) / args.loop_calls,
+                      "seconds_per_call_max": float(secs.max()) / args.loop_calls,
+                      "us_per_generation": float(np.median(secs / gens)) * 1e6, "evals_per_s": loop_rate[c],
+                      "evals_per_s_spread": [float(rates.min()), float(rates.max())]})
+    for c, R, b in batches:
+        ts, cs = np.array([s for s, _, _ in times[b]]), np.array(calls[b])
+        _, evals, full = times[b][-1]
+        rate, lr = evals / float(np.median(ts)), loop_rate[c]
+        lines.append({"config": "runs", "method": c.method, "runs": R, "ndim": c.n, "popsize": c.P, "maxiter": MAXITER,
+                      "rounds": args.rounds, "launches_per_round": launches[b], "runs_that_did_all_generations": full,
+                      "evals_per_launch": evals, "seconds_median": float(np.median(ts)), "seconds_min": float(ts.min()),
+                      "seconds_max": float(ts.max()), "evals_per_s": rate,
+                      "evals_per_s_spread": [evals / float(ts.max()), evals / float(ts.min())],
+                      "call_seconds_median": float(np.median(cs)), "call_seconds_min": float(cs.min()),
+                      "call_seconds_max": float(cs.max()), "call_evals_per_s": evals / float(np.median(cs)),
+                      "loop_evals_per_s": lr, "loop_seconds_for_these_runs_at_that_rate": evals / lr,
+                      "ratio_kernel_to_loop": rate / lr, "ratio_call_to_loop": evals / float(np.median(cs)) / lr})
     for line in lines:
         print(json.dumps(line), flush=True)
     if args.out:
