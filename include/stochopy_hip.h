@@ -767,6 +767,15 @@ typedef struct sx_de_runs_args {
 
 /* all R runs, from the initial population to each run's own termination: one launch, R workgroups */
 int sx_de_runs_launch(const sx_de_runs_args *a, void *stream);
+/* the same launch with settings of run r's own (a sweep): F (mutation, de/_strategy.py:1-38; the reference admits [0, 2],
+ * de/_de.py:129-130), CR (recombination, de/_de.py:341-344; [0, 1], :132-133) and strategy (SX_DE_*, de/_strategy.py:41-46)
+ * are each DEVICE (R) or NULL; NULL: every run uses the struct's scalar (sx_de_runs_launch is the all-NULL case, the same
+ * kernel).  Run r IS the single run with element r of each array and keys[r], bit for bit.  The host cannot read the
+ * arrays: the caller keeps them in range.  A strategy element outside SX_DE_RAND1BIN .. SX_DE_BEST2BIN, or one that needs
+ * more than P - 1 donors, ends run r at once: funs[r] = NaN, nits[r] = 0, statuses[r] = SX_STATUS_NONE, xs[r] untouched.
+ * The struct's own F, CR and strategy are checked as in sx_de_runs_launch, whether or not an array replaces them. */
+int sx_de_runs_sweep_launch(const sx_de_runs_args *a, const double *F, const double *CR, const int32_t *strategy,
+                            void *stream);
 /* bytes of LDS one run of popsize P and row length n needs (host only, no device touched); negative when that is more
  * than a workgroup may declare (160 KiB on gfx950), n > sx_wide_from() or the shape is invalid */
 int64_t sx_de_runs_lds_bytes(int64_t P, int n);
@@ -814,6 +823,14 @@ typedef struct sx_pso_runs_args {
 
 /* all R runs, from the initial swarm to each run's own termination: one launch, R workgroups */
 int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream);
+/* the same launch with settings of run r's own (a sweep): w, c1, c2 (inertia, cognitivity, sociability of the velocity
+ * update, cpso/_cpso.py:324-329; the reference admits [0, 1], [0, 4], [0, 4], :127-134) and gamma (competitivity of the
+ * restart, :405-426; [0, 2], :136-137; 0: run r never restarts) are each DEVICE (R) or NULL; NULL: every run uses the
+ * struct's scalar (sx_pso_runs_launch is the all-NULL case, the same kernel).  `delta` stays the struct's: it depends on P
+ * and maxiter only (:215-216) and is read by the runs whose gamma is not 0.  Run r IS the single run with element r of
+ * each array and keys[r], bit for bit.  The host cannot read the arrays: the caller keeps them in range. */
+int sx_pso_runs_sweep_launch(const sx_pso_runs_args *a, const double *w, const double *c1, const double *c2,
+                             const double *gamma, void *stream);
 /* bytes of LDS one run of popsize P and row length n needs (host only, no device touched); negative when that is more
  * than a workgroup may declare (160 KiB on gfx950), n > sx_wide_from() or the shape is invalid */
 int64_t sx_pso_runs_lds_bytes(int64_t P, int n);
@@ -867,6 +884,11 @@ typedef struct sx_cma_runs_args {
 
 /* all R runs, from the first generation to each run's own stopping rule: one launch, R workgroups */
 int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream);
+/* the same launch with an initial step size of run r's own (a sweep): sigma (cmaes/_cmaes.py:222; > 0, :109-110) is
+ * DEVICE (R) or NULL; NULL: every run uses the struct's sigma and insigma (sx_cma_runs_launch is that case, the same
+ * kernel).  With an array, sigma[r] is both the step size run r starts from and the `insigma` its stopping rules -6 and
+ * -8 compare with (:418, :431), as in the single run.  The host cannot read the array: the caller keeps it positive. */
+int sx_cma_runs_sweep_launch(const sx_cma_runs_args *a, const double *sigma, void *stream);
 /* bytes of LDS one run of popsize P and dimension n needs (host only, no device touched; the layout is written out at
  * the head of csrc/sx_cma_runs.hip); negative when that is more than a workgroup may declare (160 KiB on gfx950),
  * n < 1, n > 32 or P < 2 */
@@ -922,6 +944,12 @@ typedef struct sx_vd_runs_args {
 
 /* all R runs, from the first generation to each run's own stopping rule: one launch, R workgroups */
 int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream);
+/* the same launch with an initial step size of run r's own (a sweep): sigma (vdcma/_vdcma.py:229; > 0, :110-111) is
+ * DEVICE (R) or NULL; NULL: every run uses the struct's sigma and insigma (sx_vd_runs_launch is that case, the same
+ * kernel).  With an array, sigma[r] is both the step size run r starts from and the `insigma` its stopping rules -6 and
+ * -8 compare with (cmaes/_cmaes.py:418, :431), as in the single run.  The host cannot read the array: the caller keeps it
+ * positive. */
+int sx_vd_runs_sweep_launch(const sx_vd_runs_args *a, const double *sigma, void *stream);
 /* sizeof(sx_vd_runs_args) as the library was built (sx_struct_size is not extended) */
 int sx_vd_runs_args_bytes(void);
 /* bytes of LDS one run of popsize P and dimension n needs (host only, no device touched; the layout is written out at

@@ -254,14 +254,18 @@ PROTOTYPES = {
     "sx_sample_fd_gradient": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
     "sx_sample_decide": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
+    "sx_de_runs_sweep_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp, vp, vp, vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_pso_runs_launch": (C.c_int, [C.POINTER(SxPsoRunsArgs), vp]),
+    "sx_pso_runs_sweep_launch": (C.c_int, [C.POINTER(SxPsoRunsArgs), vp, vp, vp, vp, vp]),
     "sx_pso_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_pso_runs_workspace_bytes": (i64, [i64, i64, C.c_int]),
     "sx_cma_runs_launch": (C.c_int, [C.POINTER(SxCmaRunsArgs), vp]),
+    "sx_cma_runs_sweep_launch": (C.c_int, [C.POINTER(SxCmaRunsArgs), vp, vp]),
     "sx_cma_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_cma_runs_workspace_bytes": (i64, [i64, i64]),
     "sx_vd_runs_launch": (C.c_int, [C.POINTER(SxVdRunsArgs), vp]),
+    "sx_vd_runs_sweep_launch": (C.c_int, [C.POINTER(SxVdRunsArgs), vp, vp]),
     "sx_vd_runs_args_bytes": (C.c_int, []),
     "sx_vd_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_vd_runs_workspace_bytes": (i64, [i64, i64]),

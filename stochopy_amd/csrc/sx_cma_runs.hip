@@ -92,7 +92,8 @@ __host__ __device__ inline RunsLayout runs_layout(int64_t P, int n) {
 #define SX_CMA_RUNS_WAVES 4
 #endif
 template <int FUN, int M2>
-__global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_runs_kernel(const sx_cma_runs_args a, const PlanArg plan) {
+__global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_runs_kernel(const sx_cma_runs_args a, const PlanArg plan,
+                                                                                         const SigmaSweep sw) {
     constexpr int NT = runs_threads<M2>(), NW = NT / kWave, LPR = kRunsLpr, RPP = NW * (kWave / LPR), LDJ = M2 + 1;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int64_t run = blockIdx.x;
@@ -131,7 +132,13 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
     const double kps = sqrt(cs * (2.0 - cs) * mueff), kpc = sqrt(cc * (2.0 - cc) * mueff);
     const double decay = 1.0 - c1 - cmu;
     const double tol = fmax(1.0e-14, (double)n * 1.1102230246251565e-16);  // as cma_model_update passes it
-    double sigma = a.sigma;  // (uniform: every thread works it out from the same LDS values)
+    // the run's own initial step size: a sweep's element `run`, else the struct's.  Rules -6 and -8 compare with it
+    // (`insigma`).  WHERE that value is read decides nothing but the register allocation of a kernel that sits at its SGPR and
+    // VGPR limits, and that is measurable: read at entry and kept over the generation loop for the narrow solver, read again
+    // where the rules use it for the wide one (either way alone costs one of the widths 2 ... 7 %)
+    constexpr bool kInsigmaAtEntry = M2 == 16;
+    const double insigma_entry = kInsigmaAtEntry ? run_setting(sw.sigma, run, a.insigma) : 0.0;
+    double sigma = run_setting(sw.sigma, run, a.sigma);  // (uniform: every thread works it out from the same LDS values)
     int64_t eigeneval = 0;
     __syncthreads();
 
@@ -353,6 +360,7 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
         const double dax = D[axis];
         double dx2 = 0.0, fail4 = 0.0, any5 = 0.0, dmax = -__builtin_inf(), dmin = __builtin_inf(), any8 = 0.0;
         double sdmax = -__builtin_inf(), fail10 = 0.0, nan_sd = 0.0, nan_d = 0.0;
+        const double insigma = kInsigmaAtEntry ? insigma_entry : run_setting(sw.sigma, run, a.insigma);
         if (lane < n) {
             const int e = lane;
             const double d = xold[e] - xmean[e];
@@ -363,10 +371,10 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
             const double de = D[e];
             dmax = fmax(dmax, de), dmin = fmin(dmin, de);  // (numpy's max/min propagate NaN; rule 6 then compares False either way)
             if (de != de) nan_d = 1.0;
-            if (sigma * sd > 1.0e3 * a.insigma) any8 = 1.0;
+            if (sigma * sd > 1.0e3 * insigma) any8 = 1.0;
             if (sd != sd) nan_sd = 1.0;
             sdmax = fmax(sdmax, sd);
-            if (!(sigma * fabs(pc[e]) < 1.0e-11 * a.insigma)) fail10 = 1.0;
+            if (!(sigma * fabs(pc[e]) < 1.0e-11 * insigma)) fail10 = 1.0;
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -395,7 +403,7 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
             status = -6;
         else if (gen > 2 && jmax - jmin < 1.0e-12)
             status = -7;
-        else if (fail10 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * a.insigma)
+        else if (fail10 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * insigma)
             status = -8;
         if (status != SX_STATUS_NONE) {  // (uniform) the run is over; the other runs' workgroups know nothing of it
             // the caller's result: best candidate of THIS generation, un-standardised (:345-353)
@@ -429,7 +437,7 @@ extern "C" int64_t sx_cma_runs_workspace_bytes(int64_t R, int64_t maxiter) {
     return R * maxiter * (int64_t)sizeof(double);
 }
 
-extern "C" int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream) {
+extern "C" int sx_cma_runs_sweep_launch(const sx_cma_runs_args *a, const double *sigma, void *stream) {
     SX_REQUIRE(a != nullptr, "sx_cma_runs_launch: null args");
     SX_REQUIRE(a->keys && a->xmean0 && a->xm && a->xstd && a->w && a->work && a->xs && a->funs && a->nits && a->statuses,
                "sx_cma_runs_launch: null device pointer");
@@ -444,9 +452,15 @@ extern "C" int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream) {
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
     SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_cma_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
+    const SigmaSweep sweep = {sigma};
     if (runs_m2(a->n) == 16) {
-        SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(cma_runs_kernel<FUN, 16>, *a, plan, runs_threads<16>(), lds, stream))
+        SX_DISPATCH_FUN(a->fun_id,
+                        return enqueue_runs(cma_runs_kernel<FUN, 16>, *a, plan, sweep, runs_threads<16>(), lds, stream))
     }
-    SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(cma_runs_kernel<FUN, 32>, *a, plan, runs_threads<32>(), lds, stream))
+    SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(cma_runs_kernel<FUN, 32>, *a, plan, sweep, runs_threads<32>(), lds, stream))
     return -1;
+}
+
+extern "C" int sx_cma_runs_launch(const sx_cma_runs_args *a, void *stream) {
+    return sx_cma_runs_sweep_launch(a, nullptr, stream);
 }

@@ -55,7 +55,8 @@ inline int runs_waves(int64_t P, int n) {
 #define SX_DE_RUNS_WAVES 4
 #endif
 template <int FUN, int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de_runs_kernel(const sx_de_runs_args a, const PlanArg plan) {
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de_runs_kernel(const sx_de_runs_args a, const PlanArg plan,
+                                                                                              const DeSweep sw) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int n = a.n, P = (int)a.P;
     const int S = gen_row_stride(n);
@@ -67,10 +68,19 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de
     const RowIds<LPR> id(a.P);  // wave / lane / l / slot only: the rows are this run's, taken in passes of `rpp`
     const int l = id.l, rpp = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
     const uint32_t key0 = a.keys[2 * run], key1 = a.keys[2 * run + 1];
-    const int strategy = a.strategy, k = donors_of(strategy);
+    // the run's own settings (uniform in the workgroup): element `run` of a sweep's arrays, else the struct's scalars
+    const int strategy = run_setting(sw.strategy, run, a.strategy), k = donors_of(strategy);
     const bool repair = a.constraints != 0;
     const bool use_best = strategy == SX_DE_BEST1BIN || strategy == SX_DE_BEST2BIN;
-    const double F = a.F, CR = a.CR;
+    const double F = run_setting(sw.F, run, a.F), CR = run_setting(sw.CR, run, a.CR);
+    if ((unsigned)strategy > (unsigned)SX_DE_BEST2BIN || k > P - 1) {  // an element the launch could not read: no run
+        if (threadIdx.x == 0) {
+            a.funs[run] = __builtin_nan("");
+            a.nits[run] = 0;
+            a.statuses[run] = SX_STATUS_NONE;
+        }
+        return;
+    }
 
     int it = 0;    // the generation the population holds (the reference's `it`); 0: nothing yet
     int gb = 0;    // its best row
@@ -210,7 +220,8 @@ extern "C" int64_t sx_de_runs_lds_bytes(int64_t P, int n) {
     return bytes <= kLdsLimit ? bytes : -1;
 }
 
-extern "C" int sx_de_runs_launch(const sx_de_runs_args *a, void *stream) {
+extern "C" int sx_de_runs_sweep_launch(const sx_de_runs_args *a, const double *F, const double *CR, const int32_t *strategy,
+                                       void *stream) {
     SX_REQUIRE(a != nullptr, "sx_de_runs_launch: null args");
     SX_REQUIRE(a->keys && a->lower && a->upper && a->xs && a->funs && a->nits && a->statuses,
                "sx_de_runs_launch: null device pointer");
@@ -225,6 +236,11 @@ extern "C" int sx_de_runs_launch(const sx_de_runs_args *a, void *stream) {
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     const int threads = runs_waves(a->P, a->n) * kWave;
-    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(de_runs_kernel<FUN, LPR>, *a, plan, threads, lds, stream)))
+    const DeSweep sweep = {F, CR, strategy};
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(de_runs_kernel<FUN, LPR>, *a, plan, sweep, threads, lds, stream)))
     return -1;
+}
+
+extern "C" int sx_de_runs_launch(const sx_de_runs_args *a, void *stream) {
+    return sx_de_runs_sweep_launch(a, nullptr, nullptr, nullptr, stream);
 }

@@ -129,7 +129,8 @@ __device__ __forceinline__ int runs_best_status(const double *fit, const int P, 
 #endif
 template <int FUN, int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void pso_runs_kernel(const sx_pso_runs_args a,
-                                                                                               const PlanArg plan) {
+                                                                                               const PlanArg plan,
+                                                                                               const PsoSweep sw) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int64_t run = blockIdx.x;
     const int n = a.n, P = (int)a.P;
@@ -148,7 +149,9 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void p
     const int l = id.l, rpp = (int)(blockDim.x >> 6) * RowIds<LPR>::RPW;
     const uint32_t key0 = a.keys[2 * run], key1 = a.keys[2 * run + 1];
     const bool shrink = a.constraints != 0;
-    const double w = a.w, c1 = a.c1, c2 = a.c2;
+    // the run's own settings (uniform in the workgroup): element `run` of a sweep's arrays, else the struct's scalars
+    const double w = run_setting(sw.w, run, a.w), c1 = run_setting(sw.c1, run, a.c1), c2 = run_setting(sw.c2, run, a.c2);
+    const double gamma = run_setting(sw.gamma, run, a.gamma);
 
     int it = 0;  // the generation the swarm holds (the reference's `it`); 0: nothing yet
     double bf = 0.0;
@@ -252,7 +255,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void p
 
         // ---- competitive restart (cpso/_cpso.py:405-426), for a run that goes on.  It follows a move (:296-300 is inside the
         //      generation loop): the initial swarm is not looked at
-        if (a.gamma != 0.0 && it >= 2) {  // (uniform)
+        if (gamma != 0.0 && it >= 2) {  // (uniform)
             for (int row = id.slot; row < P; row += rpp) {
                 // ||X_row - gbest||: the lane adds its elements l, l + LPR, ... in order, as pso_radius_kernel does
                 const double *xr = X + (size_t)row * S;
@@ -272,7 +275,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void p
             int64_t nw = 0;
             if (radius < a.delta) {
                 const double inorm = (double)it / (double)a.maxiter;
-                nw = (int64_t)(((double)P - 1.0) / (1.0 + exp(1.0 / 0.09 * (inorm - a.gamma + 0.5))));
+                nw = (int64_t)(((double)P - 1.0) / (1.0 + exp(1.0 / 0.09 * (inorm - gamma + 0.5))));
             }
             if (nw > 0) {  // (uniform: every wavefront holds the same radius)
                 unsigned long long mine = 0ull;  // bit k: the row of pass k restarts
@@ -336,7 +339,8 @@ extern "C" int64_t sx_pso_runs_workspace_bytes(int64_t R, int64_t P, int n) {
     return runs_v_in_lds(P, n) ? 0 : R * P * (int64_t)n * (int64_t)sizeof(double);
 }
 
-extern "C" int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream) {
+extern "C" int sx_pso_runs_sweep_launch(const sx_pso_runs_args *a, const double *w, const double *c1, const double *c2,
+                                        const double *gamma, void *stream) {
     SX_REQUIRE(a != nullptr, "sx_pso_runs_launch: null args");
     SX_REQUIRE(a->keys && a->lower && a->upper && a->xs && a->funs && a->nits && a->statuses,
                "sx_pso_runs_launch: null device pointer");
@@ -356,7 +360,12 @@ extern "C" int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream) {
     SX_REQUIRE((a->P + rpp - 1) / rpp <= kMaxPasses, "sx_pso_runs_launch: more passes over the rows than restart flags");
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(pso_runs_kernel<FUN, LPR>, args, plan,
+    const PsoSweep sweep = {w, c1, c2, gamma};
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(pso_runs_kernel<FUN, LPR>, args, plan, sweep,
                                                                          waves * kWave, lds, stream)))
     return -1;
+}
+
+extern "C" int sx_pso_runs_launch(const sx_pso_runs_args *a, void *stream) {
+    return sx_pso_runs_sweep_launch(a, nullptr, nullptr, nullptr, nullptr, stream);
 }

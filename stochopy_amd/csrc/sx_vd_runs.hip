@@ -130,7 +130,8 @@ __device__ __forceinline__ void block_reduce(double (&v)[K], const int (&kind)[K
 #define SX_VD_RUNS_WAVES 2
 #endif
 template <int FUN, int LPR>
-__global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_runs_kernel(const sx_vd_runs_args a, const PlanArg plan) {
+__global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_runs_kernel(const sx_vd_runs_args a, const PlanArg plan,
+                                                                                          const SigmaSweep sw) {
     constexpr int NT = LPR == 64 ? 512 : 256, NW = NT / kWave, RPP = NT / LPR;
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int64_t run = blockIdx.x;
@@ -178,7 +179,9 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         block_reduce<1, NW>(r1, k1, red);
         vmax = r1[0];
     }
-    double sigma = a.sigma, ps = 0.0;  // (uniform: every thread works them out from the same reduced values)
+    // the run's own initial step size (a sweep's element `run`; rules -6 and -8 then compare with it), else the struct's
+    const double insigma = run_setting(sw.sigma, run, a.insigma);
+    double sigma = run_setting(sw.sigma, run, a.sigma), ps = 0.0;  // (uniform: every thread works them out from the same reduced values)
     __syncthreads();
 
     for (int gen = 1; gen <= maxiter; ++gen) {  // (generation maxiter ends with status -1 at the latest)
@@ -452,10 +455,10 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
             dv[e] = de + up * pp[e];
             nv2n += vnew * vnew;
             if (0.2 * sigma * sd < 1.0e-10) any3 += 1.0;
-            if (sigma * sd > 1.0e3 * a.insigma) any6 += 1.0;
+            if (sigma * sd > 1.0e3 * insigma) any6 += 1.0;
             if (sd != sd) nan_sd += 1.0;
             sdmax = fmax(sdmax, sd);
-            if (!(sigma * fabs(pc[e]) < 1.0e-11 * a.insigma)) fail8 += 1.0;
+            if (!(sigma * fabs(pc[e]) < 1.0e-11 * insigma)) fail8 += 1.0;
         }
         double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
         if (gen >= a.ilim) {
@@ -495,7 +498,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
             status = -6;
         else if (gen > 2 && jmax - jmin < 1.0e-12)
             status = -7;
-        else if (fail8 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * a.insigma)
+        else if (fail8 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * insigma)
             status = -8;
         if (status != SX_STATUS_NONE) {  // (uniform) the run is over; the other runs' workgroups know nothing of it
             // the caller's result: best candidate of THIS generation, un-standardised
@@ -547,7 +550,7 @@ extern "C" int64_t sx_vd_runs_workspace_bytes(int64_t R, int64_t maxiter) {
     return R * maxiter * (int64_t)sizeof(double);
 }
 
-extern "C" int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream) {
+extern "C" int sx_vd_runs_sweep_launch(const sx_vd_runs_args *a, const double *sigma, void *stream) {
     SX_REQUIRE(a != nullptr, "sx_vd_runs_launch: null args");
     SX_REQUIRE(a->keys && a->xmean0 && a->vvec0 && a->xm && a->xstd && a->w && a->work && a->xs && a->funs && a->nits &&
                    a->statuses,
@@ -563,7 +566,12 @@ extern "C" int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream) {
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
     SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_vd_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
-    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(vd_runs_kernel<FUN, LPR>, *a, plan,
+    const SigmaSweep sweep = {sigma};
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(vd_runs_kernel<FUN, LPR>, *a, plan, sweep,
                                                                          vr_threads(a->n), lds, stream)))
     return -1;
+}
+
+extern "C" int sx_vd_runs_launch(const sx_vd_runs_args *a, void *stream) {
+    return sx_vd_runs_sweep_launch(a, nullptr, stream);
 }

@@ -80,7 +80,10 @@ def minimize(
     integers) with ``rng="philox"`` -- the same draws, the same arithmetic up to the order of its sums; ``x0`` is ``None``
     (every run draws its initial mean as the single run of its seed does), one ``(n,)`` point for all runs or ``(R, n)``.
     The result describes the best run (``np.argmin`` over the runs' ``fun``; ``run`` is its index, ``nfev`` the sum over all
-    runs) and carries ``xs``, ``funs``, ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  Needs
+    runs) and carries ``xs``, ``funs``, ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  With
+    ``runs=R``, ``sigma`` may be a sequence of R values, one per run (a sweep: run r starts from ``sigma[r]``, which is
+    also what its stopping rules -6 and -8 compare with, as in the single run); the result then has ``sweep``, the dict
+    ``{"sigma": the (R,) array used}``.  Needs
     ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, ``constraints=None``, the device
     eigensolver, ``ndim <= 32`` and a population that fits one workgroup's LDS (``sx_cma_runs_lds_bytes``).
     """
@@ -91,14 +94,15 @@ def minimize(
         if np.shape(x0) != (runs, len(bounds)):
             raise ValueError(f"x0 of shape {np.shape(x0)} with runs={runs}: expected ({len(bounds)},) for all runs or "
                              f"({runs}, {len(bounds)})")
-        _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback)
+        sigma = _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback, runs)
     else:
-        _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
+        sigma = _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback, runs)
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
     if batched_runs:
-        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(sigma), float(muperc),
-                              float(xtol), float(ftol), seed, rng, constraints, eigh, workers, return_all, callback)
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), _runs.setting(sigma),
+                              float(muperc), float(xtol), float(ftol), seed, rng, constraints, eigh, workers, return_all,
+                              callback)
     workers = _common.resolve_workers(workers, fun_id)
     if len(lower) > _lib.NARROW_DIM:
         # the one method that keeps a dimension cap: an n x n covariance, its eigenvectors and an O(n^3) decomposition per
@@ -158,12 +162,12 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
                          f"(mu = {mu}) needs 2 <= popsize, mu >= 1 and at most 160 KiB")
     batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol)
     batch.launch()
-    return _runs.result(batch.fetch(), P)
+    return _runs.result(batch.fetch(), P, sigma=sigma)
 
 
 def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, outputs=()):
     """The batch of one sx_cma_runs_launch; ``outputs``: of the optional ones, ``"nfevs"`` and ``"xmeans"`` (every run's
-    final mean, standardised)."""
+    final mean, standardised).  ``sigma``: a float or an (R,) array (run r starts from element r)."""
     n, R = len(lower), len(seeds)
     mu, w, *constants = _strategy_constants(n, P, muperc)
     xm, xstd, xmean0 = _runs.standardised(lower, upper, x0, R)
@@ -178,7 +182,8 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol
         batch.bind(xmean0=d_xmean0, xm=d_std[:n], xstd=d_std[n:], w=d_w,
                    work=ctx.empty((int(ctx.L.sx_cma_runs_workspace_bytes(R, maxiter)) // 8,)))
         batch.outputs(n, {"nfevs": ((R,), _device.torch().int64), "xmeans": ((R, n), None)}, outputs, extra=("sigmas",))
-    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, sigma, xtol, ftol)
+        own = batch.bind_sweep(sigma=sigma)
+    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, own["sigma"], xtol, ftol)
     a.mueff, a.cc, a.cs, a.c1, a.cmu, a.damps, a.chind = constants
     return batch
 

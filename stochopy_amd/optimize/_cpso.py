@@ -63,7 +63,10 @@ def minimize(
     (a sequence of R integers) with ``rng="philox", updating="deferred"``; ``x0`` is ``None``, one ``(P, n)`` swarm
     for all runs or ``(R, P, n)``, and is not modified.  The result describes the best run (``np.argmin`` over the runs'
     ``fun``; ``run`` is its index, ``nfev`` the sum over all runs) and carries ``xs``, ``funs``, ``nits``, ``statuses``
-    per run.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
+    per run.  With ``runs=R``, ``inertia``, ``cognitivity``, ``sociability`` and ``competitivity`` may each be a sequence of R
+    values, one per run (a sweep: run r is the single run with element r of each and seed r; a run whose ``competitivity``
+    is 0 never restarts); the result then has ``sweep``, a dict from the name of each such option to the ``(R,)`` array
+    used.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a swarm that fits one workgroup's LDS (``sx_pso_runs_lds_bytes``).
     """
     batched_runs = _runs.batched(runs)
@@ -80,14 +83,11 @@ def minimize(
         raise ValueError()
     if x0 is not None and np.ndim(x0) == 2 and len(x0) != popsize:
         raise ValueError()
-    if not 0.0 <= inertia <= 1.0:
-        raise ValueError()
-    if not 0.0 <= cognitivity <= 4.0:
-        raise ValueError()
-    if not 0.0 <= sociability <= 4.0:
-        raise ValueError()
-    if competitivity is not None and not 0.0 <= competitivity <= 2.0:
-        raise ValueError()
+    inertia = _runs.per_run("inertia", inertia, runs, 0.0, 1.0)
+    cognitivity = _runs.per_run("cognitivity", cognitivity, runs, 0.0, 4.0)
+    sociability = _runs.per_run("sociability", sociability, runs, 0.0, 4.0)
+    if competitivity is not None:
+        competitivity = _runs.per_run("competitivity", competitivity, runs, 0.0, 2.0)
     if updating not in {"immediate", "deferred"}:
         raise ValueError()
     if constraints not in (None, "Shrink"):
@@ -97,9 +97,9 @@ def minimize(
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
     if batched_runs:
-        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(inertia),
-                              float(cognitivity), float(sociability), competitivity, constraints, float(xtol), float(ftol),
-                              seed, rng, updating, strict_updating, workers, return_all, callback)
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), _runs.setting(inertia),
+                              _runs.setting(cognitivity), _runs.setting(sociability), competitivity, constraints,
+                              float(xtol), float(ftol), seed, rng, updating, strict_updating, workers, return_all, callback)
     workers = _common.resolve_workers(workers, fun_id)
     run = _PsoRun(fun_id, lower, upper, x0, int(maxiter), int(popsize), float(inertia), float(cognitivity),
                   float(sociability), competitivity, constraints, float(xtol), float(ftol), bool(return_all),
@@ -123,16 +123,20 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competiti
                          "variables is more than its 160 KiB hold")
     batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competitivity, constraints, xtol, ftol)
     batch.launch()
-    return _runs.result(batch.fetch(), P)
+    return _runs.result(batch.fetch(), P, inertia=w, cognitivity=c1, sociability=c2, competitivity=competitivity)
 
 
 def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competitivity, constraints, xtol, ftol, outputs=()):
     """The batch of one sx_pso_runs_launch; ``outputs``: of the optional ones, every run's last swarm -- ``"xfinal"``,
-    ``"pbest_final"``, ``"pbestfit_final"``."""
+    ``"pbest_final"``, ``"pbestfit_final"``.  ``w``, ``c1``, ``c2``, ``competitivity``: a float or an (R,) array (run r uses
+    element r)."""
     n = len(lower)
-    gamma = float(competitivity) if competitivity else 0.0
-    # cpso/_cpso.py:215-216 (depends on maxiter and the swarm's size)
-    delta = float(np.log(1.0 + 0.003 * P) / np.max((0.2, np.log(0.01 * maxiter)))) if gamma else 0.0
+    if _runs.is_swept(competitivity):
+        gamma = competitivity
+    else:
+        gamma = float(competitivity) if competitivity else 0.0
+    # cpso/_cpso.py:215-216 (depends on maxiter and the swarm's size; read by the runs whose gamma is not 0)
+    delta = float(np.log(1.0 + 0.003 * P) / np.max((0.2, np.log(0.01 * maxiter)))) if np.any(gamma) else 0.0
     batch = _runs.Batch("sx_pso_runs_launch", _lib.SxPsoRunsArgs(), seeds, P)
     a, ctx, R = batch.a, batch.ctx, batch.R
     with batch.stream():
@@ -148,9 +152,10 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competit
         vwork = int(ctx.L.sx_pso_runs_workspace_bytes(R, P, n))
         if vwork:
             batch.bind(vwork=ctx.empty((vwork // 8,)))
+        own = batch.bind_sweep(w=w, c1=c1, c2=c2, gamma=gamma)
     a.n, a.fun_id = n, fun_id
     a.constraints, a.maxiter = (1 if constraints == "Shrink" else 0), maxiter
-    a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = w, c1, c2, gamma, delta, xtol, ftol
+    a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = own["w"], own["c1"], own["c2"], own["gamma"], delta, xtol, ftol
     return batch
 
 

@@ -75,7 +75,9 @@ def minimize(
     (a sequence of R integers) with ``rng="philox", updating="deferred"``; ``x0`` is ``None``, one ``(P, n)`` population
     for all runs or ``(R, P, n)``, and is not modified.  The result describes the best run (``np.argmin`` over the runs'
     ``fun``; ``run`` is its index, ``nfev`` the sum over all runs) and carries ``xs``, ``funs``, ``nits``, ``statuses``
-    per run.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
+    per run.  With ``runs=R``, ``mutation``, ``recombination`` and ``strategy`` may each be a sequence of R values, one per
+    run (a sweep: run r is the single run with element r of each and seed r); the result then has ``sweep``, a dict from
+    the name of each such option to the ``(R,)`` array used.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a population whose two generations fit one workgroup's LDS (``sx_de_runs_lds_bytes``).
     """
     batched_runs = _runs.batched(runs)
@@ -92,14 +94,11 @@ def minimize(
         raise ValueError()
     if x0 is not None and np.ndim(x0) == 2 and len(x0) != popsize:
         raise ValueError()
-    if not 0.0 <= mutation <= 2.0:
-        raise ValueError()
-    if not 0.0 <= recombination <= 1.0:
-        raise ValueError()
+    mutation = _runs.per_run("mutation", mutation, runs, 0.0, 2.0)
+    recombination = _runs.per_run("recombination", recombination, runs, 0.0, 1.0)
     if updating not in {"immediate", "deferred"}:
         raise ValueError()
-    if strategy not in _lib.DE_STRATEGIES:
-        raise KeyError(strategy)
+    strategy = _runs.per_run_names("strategy", strategy, runs, _lib.DE_STRATEGIES)
     if constraints not in (None, "Random"):
         raise KeyError(constraints)
     if callback is not None and not hasattr(callback, "__call__"):
@@ -107,10 +106,15 @@ def minimize(
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
     if batched_runs:
-        if popsize - 1 < _lib.DE_DONORS[strategy]:
+        if _runs.is_swept(strategy):
+            most = max(strategy, key=_lib.DE_DONORS.get)
+            if popsize - 1 < _lib.DE_DONORS[most]:
+                raise ValueError(f"runs={runs}: strategy names {most!r}, which draws {_lib.DE_DONORS[most]} donors: popsize "
+                                 f"{popsize} is too small")
+        elif popsize - 1 < _lib.DE_DONORS[strategy]:
             raise ValueError()
-        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(mutation),
-                              float(recombination), strategy, constraints, float(xtol), float(ftol), seed, rng, updating,
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), _runs.setting(mutation),
+                              _runs.setting(recombination), strategy, constraints, float(xtol), float(ftol), seed, rng, updating,
                               strict_updating, workers, return_all, callback)
     workers = _common.resolve_workers(workers, fun_id)
     if popsize - 1 < _lib.DE_DONORS[strategy]:
@@ -138,12 +142,17 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, con
                          "is more than its 160 KiB hold")
     batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol)
     batch.launch()
-    return _runs.result(batch.fetch(), P)
+    return _runs.result(batch.fetch(), P, mutation=F, recombination=CR, strategy=strategy)
 
 
 def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol, outputs=()):
-    """The batch of one sx_de_runs_launch; ``outputs``: of the optional ones, ``"xfinal"`` (every run's last population)."""
+    """The batch of one sx_de_runs_launch; ``outputs``: of the optional ones, ``"xfinal"`` (every run's last population).
+    ``F``, ``CR``: a float or an (R,) array, ``strategy``: a name or an (R,) array of names (run r uses element r)."""
     n = len(lower)
+    if _runs.is_swept(strategy):
+        strategy = np.array([_lib.DE_STRATEGIES[name] for name in strategy], dtype=np.int32)
+    else:
+        strategy = _lib.DE_STRATEGIES[strategy]
     batch = _runs.Batch("sx_de_runs_launch", _lib.SxDeRunsArgs(), seeds, P)
     a, ctx, R = batch.a, batch.ctx, batch.R
     with batch.stream():
@@ -154,9 +163,10 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, co
             batch.bind(x0=ctx.upload(np.array(x0, dtype=np.float64)))
             a.x0_stride = P * n if batch.dev["x0"].dim() == 3 else 0
         batch.outputs(n, {"xfinal": ((R, P, n), None)}, outputs)
-    a.n, a.fun_id, a.strategy = n, fun_id, _lib.DE_STRATEGIES[strategy]
+        own = batch.bind_sweep(F=F, CR=CR, strategy=strategy)
+    a.n, a.fun_id, a.strategy = n, fun_id, own["strategy"]
     a.constraints, a.maxiter = (1 if constraints == "Random" else 0), maxiter
-    a.F, a.CR, a.xtol, a.ftol = F, CR, xtol, ftol
+    a.F, a.CR, a.xtol, a.ftol = own["F"], own["CR"], xtol, ftol
     return batch
 
 

@@ -11,23 +11,24 @@ import os
 import numpy as np
 
 from .. import _device, _lib, _rng
-from . import _common
+from . import _common, _runs
 from ._helpers import OptimizeResult
 
 
-def check_arguments(bounds, x0, sigma, muperc, constraints, callback):
-    """What both front ends refuse (cmaes/_cmaes.py:142-160, vdcma/_vdcma.py:143-161)."""
+def check_arguments(bounds, x0, sigma, muperc, constraints, callback, runs=None):
+    """What both front ends refuse (cmaes/_cmaes.py:142-160, vdcma/_vdcma.py:143-161).  Returns ``sigma``: as given, or --
+    a sequence with ``runs=R``, one step size per run -- as an (R,) array."""
     if x0 is not None:
         if np.ndim(x0) != 1 or len(x0) != len(bounds):
             raise ValueError()
-    if sigma <= 0.0:
-        raise ValueError()
+    sigma = _runs.per_run("sigma", sigma, runs, positive=True)
     if not 0.0 < muperc <= 1.0:
         raise ValueError()
     if constraints not in (None, "Penalize"):
         raise KeyError(constraints)
     if callback is not None and not hasattr(callback, "__call__"):
         raise ValueError()
+    return sigma
 
 
 def device_loop_serves(fun_id, rng, n, popsize, constraints):

@@ -19,6 +19,78 @@ def batched(runs):
     return runs is not None and runs > 1
 
 
+def per_run(name, value, runs, lo=None, hi=None, positive=False):
+    """A hyperparameter that one run of a batch may have to itself.  A scalar (a 0-d array, a numpy scalar) gets the
+    reference's check -- a bare ValueError, where the caller stands in the order of checks -- and comes back as it is.  A
+    sequence is a sweep: ``runs`` values, run r uses element r; it comes back as an ``(R,)`` float64 array, or the
+    ValueError names ``runs``, the option and, where one element is at fault, its index."""
+    if _is_scalar(value):
+        if (value <= 0.0) if positive else (not lo <= value <= hi):
+            raise ValueError()
+        return value
+    values = _sweep_elements(name, value, runs)
+    allowed = "> 0" if positive else f"in [{lo:g}, {hi:g}]"
+    out = np.empty(len(values))
+    for r, v in enumerate(values):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"runs={runs}: {name}[{r}] = {v!r} is not a number")
+        if not np.isfinite(v):
+            raise ValueError(f"runs={runs}: {name}[{r}] = {v!r} is not finite")
+        if (v <= 0.0) if positive else (not lo <= v <= hi):
+            raise ValueError(f"runs={runs}: {name}[{r}] = {v!r}: expected a value {allowed}")
+        out[r] = v
+    return out
+
+
+def per_run_names(name, value, runs, table):
+    """``per_run`` for an option that is a name out of ``table`` (DE's ``strategy``): a KeyError for an unknown name, as for
+    the scalar; a sequence comes back as an ``(R,)`` array of names."""
+    if _is_scalar(value):
+        if value not in table:
+            raise KeyError(value)
+        return value
+    values = _sweep_elements(name, value, runs)
+    for v in values:
+        if not isinstance(v, str) or v not in table:
+            raise KeyError(v)
+    return np.array([str(v) for v in values])
+
+
+def _is_scalar(value):
+    """Not a sequence: what the reference's own comparison is left to deal with (a ragged list has no shape: a sequence)."""
+    try:
+        return np.ndim(value) == 0
+    except ValueError:
+        return False
+
+
+def _sweep_elements(name, value, runs):
+    """The R elements of a per-run option as Python / numpy scalars, or a ValueError that names ``runs`` and the option."""
+    if not batched(runs):
+        raise ValueError(f"{name} is a sequence, one value per run: that needs runs >= 2 (runs={runs!r}); a single run takes "
+                         "a scalar")
+    try:
+        shape = np.shape(value)
+    except ValueError:
+        shape = None
+    if shape is None or len(shape) != 1:
+        raise ValueError(f"runs={runs}: {name} must be a scalar or a 1-D sequence of {runs} values, one per run"
+                         + ("" if shape is None else f" (its shape is {shape})"))
+    if shape[0] != runs:
+        raise ValueError(f"runs={runs}: {name} has {shape[0]} values, expected one per run")
+    return list(value)
+
+
+def is_swept(value):
+    """Did ``per_run`` / ``per_run_names`` hand back a sweep?"""
+    return isinstance(value, np.ndarray) and value.ndim == 1
+
+
+def setting(value):
+    """What a method's ``_minimize_runs`` takes for a hyperparameter: a float, or the sweep's ``(R,)`` array."""
+    return value if is_swept(value) else float(value)
+
+
 def refuse_common(rng, fun_id, workers, callback, return_all):
     """What no batched method serves: a run lives in one kernel on one GPU."""
     if rng != "philox":
@@ -89,10 +161,14 @@ class Batch:
     """R runs for one ``sx_*_runs_launch``: the device context, the argument struct ``a`` and ``dev``, the device tensors its
     pointers name (inputs, outputs, workspace).  Pointers that are never bound stay NULL."""
 
+    # the per-run arrays of sx_*_runs_sweep_launch, in the order of its arguments
+    SWEEP = {"sx_de_runs_launch": ("F", "CR", "strategy"), "sx_pso_runs_launch": ("w", "c1", "c2", "gamma"),
+             "sx_cma_runs_launch": ("sigma",), "sx_vd_runs_launch": ("sigma",)}
+
     def __init__(self, entry, args, seeds, P):
         self.entry, self.a, self.seeds, self.R, self.P = entry, args, seeds, len(seeds), P
         self.ctx = _device.Context()
-        self.dev, self.out = {}, ()
+        self.dev, self.out, self.sweep = {}, (), {}
         args.R, args.P = self.R, P
 
     def stream(self):
@@ -103,6 +179,22 @@ class Batch:
         for name, tensor in tensors.items():
             self.dev[name] = tensor
             setattr(self.a, name, tensor.data_ptr())
+
+    def bind_sweep(self, **settings):
+        """Of ``settings`` (argument name of the ``_sweep_`` entry -> float, or (R,) array), upload the arrays: run r reads
+        element r of those, and the struct's scalar for the rest.  Returns the scalars, for the struct -- of a swept
+        setting, run 0's: the launch checks the struct's fields whether or not an array replaces them."""
+        scalars = {}
+        for name, value in settings.items():
+            if is_swept(value):
+                if name not in self.SWEEP[self.entry] or value.shape != (self.R,):
+                    raise ValueError(f"{self.entry}: no per-run {name} of shape {value.shape} for {self.R} runs")
+                dtype = np.int32 if name == "strategy" else np.float64
+                self.sweep[name] = self.ctx.upload_async(np.ascontiguousarray(value, dtype=dtype))
+                scalars[name] = value[0].item()
+            else:
+                scalars[name] = value
+        return scalars
 
     def upload_keys(self):
         keys = np.array([_rng.philox_key(s) for s in self.seeds], dtype=np.uint32)
@@ -120,7 +212,12 @@ class Batch:
         self.out = ("xs", "funs", "nits", "statuses", *extra, *wanted)
 
     def launch(self):
-        _lib.check(getattr(self.ctx.L, self.entry)(C.byref(self.a), self.ctx.stream_ptr), self.entry)
+        if not self.sweep:
+            _lib.check(getattr(self.ctx.L, self.entry)(C.byref(self.a), self.ctx.stream_ptr), self.entry)
+            return
+        entry = self.entry.replace("_launch", "_sweep_launch")
+        arrays = [self.sweep[name].data_ptr() if name in self.sweep else None for name in self.SWEEP[self.entry]]
+        _lib.check(getattr(self.ctx.L, entry)(C.byref(self.a), *arrays, self.ctx.stream_ptr), entry)
 
     def fetch(self):
         """The outputs as numpy arrays, by name."""
@@ -128,8 +225,12 @@ class Batch:
             return {name: self.dev[name].cpu().numpy() for name in self.out}
 
 
-def result(out, P):
-    """The best run (``np.argmin``) as the result, with every run's outputs beside it."""
+def result(out, P, **settings):
+    """The best run (``np.argmin``) as the result, with every run's outputs beside it; ``sweep``: of ``settings`` (option
+    name -> what ``_minimize_runs`` got), those that were per run, if any."""
+    sweep = {name: np.array(value) for name, value in settings.items() if is_swept(value)}
+    if sweep:
+        out = dict(out, sweep=sweep)
     xs, funs, nits, statuses = out["xs"], out["funs"], out["nits"], out["statuses"]
     best = int(np.argmin(funs))
     status = int(statuses[best])

@@ -60,7 +60,10 @@ def minimize(
     (every run draws its initial mean as the single run of its seed does), one ``(n,)`` point for all runs or ``(R, n)``; the
     initial direction of run r is drawn right after its mean, as the single run draws it.  The result describes the best run
     (``np.argmin`` over the runs' ``fun``; ``run`` is its index, ``nfev`` the sum over all runs) and carries ``xs``, ``funs``,
-    ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  Needs ``rng="philox"``, a factory objective, one
+    ``nits``, ``statuses`` and ``sigmas`` (the final step sizes) per run.  With ``runs=R``, ``sigma`` may be a sequence of R
+    values, one per run (a sweep: run r starts from ``sigma[r]``, which is also what its stopping rules -6 and -8 compare
+    with, as in the single run); the result then has ``sweep``, the dict ``{"sigma": the (R,) array used}``.  Needs
+    ``rng="philox"``, a factory objective, one
     GPU, no callback, no ``return_all``, ``constraints=None``, ``ndim >= 6`` and a shape that fits one workgroup's LDS
     (``sx_vd_runs_lds_bytes``: popsize 10 up to ndim 512 and beyond)."""
     batched_runs = _runs.batched(runs)
@@ -70,14 +73,15 @@ def minimize(
         if np.shape(x0) != (runs, len(bounds)):
             raise ValueError(f"x0 of shape {np.shape(x0)} with runs={runs}: expected ({len(bounds)},) for all runs or "
                              f"({runs}, {len(bounds)})")
-        _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback)
+        sigma = _evolution.check_arguments(bounds, None, sigma, muperc, constraints, callback, runs)
     else:
-        _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback)
+        sigma = _evolution.check_arguments(bounds, x0, sigma, muperc, constraints, callback, runs)
     _common.resolve_backend(backend, fun_id)
     rng = _common.resolve_rng(rng)
     if batched_runs:
-        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), float(sigma), float(muperc),
-                              float(xtol), float(ftol), seed, rng, constraints, workers, return_all, callback)
+        return _minimize_runs(int(runs), fun_id, lower, upper, x0, int(maxiter), int(popsize), _runs.setting(sigma),
+                              float(muperc), float(xtol), float(ftol), seed, rng, constraints, workers, return_all,
+                              callback)
     workers = _common.resolve_workers(workers, fun_id)
     if _evolution.device_loop_serves(fun_id, rng, len(lower), popsize, constraints):
         # the whole loop (and the history) stays on the device -- since round 3 including constraints="Penalize"
@@ -130,7 +134,7 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol,
                          "160 KiB")
     batch = _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol)
     batch.launch()
-    return _runs.result(batch.fetch(), P)
+    return _runs.result(batch.fetch(), P, sigma=sigma)
 
 
 def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol, ftol, outputs=()):
@@ -158,7 +162,8 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, sigma, muperc, xtol
         vec = ((R, n), None)
         batch.outputs(n, {"nfevs": ((R,), _device.torch().int64), "xmeans": vec, "dvecs": vec, "vvecs": vec}, outputs,
                       extra=("sigmas",))
-    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, sigma, xtol, ftol)
+        own = batch.bind_sweep(sigma=sigma)
+    _runs.set_model_scalars(a, n, mu, fun_id, maxiter, own["sigma"], xtol, ftol)
     a.mueff, a.cc, a.c1, a.cmu = mueff, cc, c1, cmu
     a.cs, a.ds, a.wsum = 0.3, float(np.sqrt(n)), float(w.sum())
     return batch

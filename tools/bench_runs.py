@@ -17,10 +17,15 @@ Every run of de, pso, cpso and vdcma must do its 200 generations (checked).
     loop                           --loop-calls (64) single minimize() calls with the same settings and seeds s, s+1, ...,
                                    wall time with the stream drained at the end.  The loop's rate does not depend on how many
                                    runs are asked for: the figure beside R runs IS this rate, not a measurement of R calls.
+    --sweep                        the same batches once more with their per-run arrays bound (sx_*_runs_sweep_launch): every
+                                   hyperparameter of SWEEPS below spread evenly, run 0 to run R - 1, over the stated interval
+                                   around the workload's scalar.  Their lines ("runs, swept") stand beside the uniform ones and
+                                   are not compared with them: other settings end other runs at other generations (the share
+                                   that did all of them is recorded, not required).
 Everything is warmed up once, then the configurations take turns for --rounds rounds; a line gives the median and the spread
 (min .. max) of its rounds, in objective evaluations per second (nit x popsize per run).
 
-    python tools/bench_runs.py [--method de|pso|cpso|cmaes|vdcma ...] [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
+    python tools/bench_runs.py [--method de|pso|cpso|cmaes|vdcma ...] [--sweep] [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
 """
 import argparse
 import importlib
@@ -52,6 +57,15 @@ WORKLOADS = {
     "vdcma": dict(module="_vdcma", objective="rosenbrock", shapes=((64, 16), (256, 20)), half=3.0, full=True, warm_loop=4,
                   own=(0.1, 0.5), opts={"sigma": 0.1}),
 }
+# --sweep: index into `own` -> (option, lowest, highest): run r of R uses lowest + (highest - lowest) r / (R - 1)
+SWEEPS = {
+    "de": {0: ("mutation", 0.4, 0.6), 1: ("recombination", 0.8, 1.0)},
+    "pso": {0: ("inertia", 0.6, 0.8), 1: ("cognitivity", 1.3, 1.7), 2: ("sociability", 1.3, 1.7)},
+    "cpso": {0: ("inertia", 0.6, 0.8), 1: ("cognitivity", 1.3, 1.7), 2: ("sociability", 1.3, 1.7),
+             3: ("competitivity", 0.8, 1.2)},
+    "cmaes": {0: ("sigma", 0.05, 0.2)},
+    "vdcma": {0: ("sigma", 0.05, 0.2)},
+}
 
 
 class Config:
@@ -63,13 +77,17 @@ class Config:
         self.fun, self.bounds = getattr(sa.factory, w["objective"]), [[-w["half"], w["half"]]] * n
         self.options = dict(COMMON, popsize=P, **w["opts"])
 
-    def batch(self, R):
+    def batch(self, R, swept=False):
         from stochopy_amd import _lib
 
         w = WORKLOADS[self.method]
+        own = list(w["own"])
+        if swept:
+            for k, (_, lo, hi) in SWEEPS[self.method].items():
+                own[k] = np.linspace(lo, hi, R)
         build = importlib.import_module("stochopy_amd.optimize." + w["module"])._runs_batch
         return build([SEED + r for r in range(R)], _lib.FUN_IDS[w["objective"]], np.full(self.n, -w["half"]),
-                     np.full(self.n, w["half"]), None, MAXITER, self.P, *w["own"], COMMON["xtol"], COMMON["ftol"])
+                     np.full(self.n, w["half"]), None, MAXITER, self.P, *own, COMMON["xtol"], COMMON["ftol"])
 
     def minimize(self, **more):
         return self.sa.optimize.minimize(self.fun, self.bounds, method=self.method, options=dict(self.options, **more))
@@ -94,7 +112,7 @@ class Config:
         return time.perf_counter() - t0, evals
 
 
-def timed(config, batch, launches=1):
+def timed(config, batch, launches=1, swept=False):
     """Seconds per launch (a whole batch), over `launches` launches back to back; the evaluations one launch did and the share
     of its runs that did all their generations."""
     t = __import__("torch")
@@ -107,13 +125,14 @@ def timed(config, batch, launches=1):
         e1.synchronize()
     nits = batch.dev["nits"]
     full = float((nits == MAXITER).double().mean())
-    assert not config.full or full == 1.0, "a run ended before its %d generations" % MAXITER
+    assert swept or not config.full or full == 1.0, "a run ended before its %d generations" % MAXITER
     return e0.elapsed_time(e1) * 1e-3 / launches, int(nits.sum()) * config.P, full
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--method", nargs="+", choices=sorted(WORKLOADS), default=["de"])
+    ap.add_argument("--sweep", action="store_true", help="also time every batch with its per-run arrays bound")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per timed round")
     ap.add_argument("--loop-calls", type=int, default=64)
@@ -125,19 +144,25 @@ def main():
     ctx = _device.Context()
     configs = [Config(sa, method, n, P) for method in args.method for n, P in WORKLOADS[method]["shapes"]]
     batches = [(c, R, c.batch(R)) for c in configs for R in RUNS]
+    swept = [(c, R, c.batch(R, swept=True)) for c in configs for R in RUNS] if args.sweep else []
     launches = {}
+    for c, R, b in swept:
+        timed(c, b, swept=True)
+        launches[b] = max(1, int(round(args.window / timed(c, b, swept=True)[0])))
     for c, R, b in batches:
         timed(c, b)  # warm-up: code object load
         launches[b] = max(1, int(round(args.window / timed(c, b)[0])))
         c.whole_call(R)
     for c in configs:
         c.loop_of_calls(ctx, WORKLOADS[c.method]["warm_loop"])  # warm-up: graphs and code objects of the single run, allocator
-    times, calls = {b: [] for _, _, b in batches}, {b: [] for _, _, b in batches}
+    times, calls = {b: [] for _, _, b in batches + swept}, {b: [] for _, _, b in batches}
     loop = {c: [] for c in configs}
     for _ in range(args.rounds):
         for c, R, b in batches:
             times[b].append(timed(c, b, launches[b]))
             calls[b].append(c.whole_call(R))
+        for c, R, b in swept:
+            times[b].append(timed(c, b, launches[b], swept=True))
         for c in configs:
             loop[c].append(c.loop_of_calls(ctx, args.loop_calls))
     lines, loop_rate = [], {}
@@ -166,6 +191,15 @@ def main():
                       "call_seconds_max": float(cs.max()), "call_evals_per_s": evals / float(np.median(cs)),
                       "loop_evals_per_s": lr, "loop_seconds_for_these_runs_at_that_rate": evals / lr,
                       "ratio_kernel_to_loop": rate / lr, "ratio_call_to_loop": evals / float(np.median(cs)) / lr})
+    for c, R, b in swept:
+        ts = np.array([s for s, _, _ in times[b]])
+        _, evals, full = times[b][-1]
+        lines.append({"config": "runs, swept", "method": c.method, "runs": R, "ndim": c.n, "popsize": c.P, "maxiter": MAXITER,
+                      "sweep": {name: [lo, hi] for name, lo, hi in SWEEPS[c.method].values()},
+                      "rounds": args.rounds, "launches_per_round": launches[b], "runs_that_did_all_generations": full,
+                      "evals_per_launch": evals, "seconds_median": float(np.median(ts)), "seconds_min": float(ts.min()),
+                      "seconds_max": float(ts.max()), "evals_per_s": evals / float(np.median(ts)),
+                      "evals_per_s_spread": [evals / float(ts.max()), evals / float(ts.min())]})
     for line in lines:
         print(json.dumps(line), flush=True)
     if args.out:
