@@ -59,7 +59,8 @@ const char *sx_last_error(void);
 int sx_device_count(void);
 /* sizeof(sx_state / sx_de_args / sx_pso_args / sx_xchg_args) as compiled: lets a binding check its struct
  * mirror (which: 0 state, 1 DE args, 2 PSO args, 3 exchange args, 4 CMA state, 5 CMA args, 6 VD-CMA args, 7 sampler args,
- * 8 DE-runs args, 9 PSO-runs args, 10 CMA-runs args; -1 otherwise) */
+ * 8 DE-runs args, 9 PSO-runs args, 10 CMA-runs args, 12 row-wise runs args; -1 otherwise, 11 included: the VD-CMA runs'
+ * struct is checked through sx_vd_runs_args_bytes) */
 int sx_struct_size(int which);
 
 /* ------------------------------------------------------------------------- *
@@ -959,6 +960,95 @@ int64_t sx_vd_runs_lds_bytes(int64_t P, int n);
 /* bytes of device workspace (sx_vd_runs_args.work) R runs of at most maxiter generations need: R*maxiter*8 (host
  * only); negative for R < 1 or maxiter < 1 */
 int64_t sx_vd_runs_workspace_bytes(int64_t R, int64_t maxiter);
+
+/* ------------------------------------------------------------------------- *
+ * DE and PSO, many independent runs around a CALLER-SUPPLIED ROW-WISE objective (csrc/sx_runs_unfused.hip): the batched
+ * counterpart of sx_de_propose / sx_pso_move / sx_rows_select / sx_select_finalize above.  The objective cannot be fused,
+ * so the R populations live in device memory -- three (R,P,n) arrays -- and a generation of ALL runs is
+ *   sx_runs_rowwise_de_propose / _pso_move -> the caller's objective, once, on the stacked (R*P, n) rows ->
+ *   sx_runs_rowwise_select -> sx_runs_rowwise_finalize.
+ * Row r*P + i is individual i of run r.  Stacking is only correct for an objective whose value of a row depends on that row
+ * alone (factory.batched(f, rowwise=True)).
+ * Geometry: the row geometry of the single-run kernels (sx_rows_per_workgroup(n) rows a workgroup), and a workgroup never
+ * spans two runs: a run takes sx_runs_rowwise_partials(P, n) = ceil(P / sx_rows_per_workgroup(n)) workgroups, workgroup b
+ * serves run b / that number, so a run's (part_f, part_i) records are those of the single run.  Run r draws with keys[r]; the
+ * Philox counters are those of the single-run kernels (row = the row within the run, generation = state[r].it + 1), the
+ * arithmetic and the orders of summation too: given the same objective values, run r IS the single run of its key -- same
+ * population, best, nit and status, bit for bit.  In-kernel draws only.  A run that has ended (state[r].done) is frozen: every
+ * kernel returns at entry for its workgroups, so its rows of the stacked tensor keep their last contents.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_runs_rowwise_args {
+    const uint32_t *keys;   /* DEVICE (R,2) Philox key (key0, key1) of run r                               */
+    const double *lower;    /* DEVICE (n)                                                                  */
+    const double *upper;    /* DEVICE (n)                                                                  */
+    const double *x0;       /* DEVICE initial populations, (P,n) each, run stride x0_stride; NULL: run r draws the
+                               Latin hypercube of sx_philox_lhs with keys[r] (_common.py:109-120)          */
+    double *pop0;           /* DEVICE (R,P,n)  DE: population buffer 0 (generation g of run r lives in buffer g & 1, g =
+                               state[r].it, as in sx_de_args)           PSO: X, the rows the objective is handed   */
+    double *pop1;           /* DEVICE (R,P,n)  DE: population buffer 1                       PSO: V                */
+    double *pop2;           /* DEVICE (R,P,n)  DE: cand, the rows the objective is handed    PSO: pbest            */
+    double *fit;            /* DEVICE (R*P)    DE: fitness of the current rows               PSO: pbestfit         */
+    double *candfit;        /* DEVICE (R*P)    the values of the last evaluated rows (as sx_de_args.candfit)      */
+    const double *f;        /* DEVICE (R*P)    IN what the objective returned for the rows it was handed: read by _start
+                               and _select only, and may point elsewhere in every call (NULL for the others)       */
+    sx_state *state;        /* DEVICE (R)      run r's generation state (64 bytes each)                            */
+    double *gbest;          /* DEVICE (R,n)    run r's best row                                                    */
+    double *part_f;         /* DEVICE (R, sx_runs_rowwise_partials(P,n)) per-workgroup records of the selection    */
+    int64_t *part_i;        /* DEVICE (same)   their rows, within the run                                          */
+    double *xs;             /* DEVICE (R,n) OUT best individual of run r, written when the run ends                */
+    double *funs;           /* DEVICE (R)   OUT its value                                                          */
+    int64_t *nits;          /* DEVICE (R)   OUT generations (the reference's `it`; the initial one counts)         */
+    int32_t *statuses;      /* DEVICE (R)   OUT -1 / 0 / 1 (_common.py:134-158)                                    */
+    int32_t *ended;         /* DEVICE (1)   IN/OUT number of runs that have ended (zeroed by the caller; a run adds
+                               one when it ends): what the host reads to learn whether any run is still active     */
+    int64_t R;
+    int64_t P;              /* >= 2; R*P < 2^31                                                                    */
+    int64_t x0_stride;      /* 0 (one population shared by all runs) or P*n                                        */
+    int32_t n;              /* 1 ... sx_wide_from()                                                                */
+    int32_t method;         /* 0 DE, 1 PSO                                                                         */
+    int32_t strategy;       /* DE                                                                                  */
+    int32_t constraints;    /* 0 none, 1 Random (DE) / Shrink (PSO)                                                */
+    int32_t maxiter;        /* <= 1: one generation is still run                                                   */
+    int32_t pad;
+    double F, CR;           /* DE                                                                                  */
+    double w, c1, c2;       /* PSO                                                                                 */
+    double xtol, ftol;
+} sx_runs_rowwise_args;
+
+/* records (= workgroups) per run: ceil(P / sx_rows_per_workgroup(n)), as sx_num_partials for one run (host only, no device
+ * touched); negative for P < 2, n < 1 or n > sx_wide_from() */
+int64_t sx_runs_rowwise_partials(int64_t P, int n);
+/* the initial populations: with x0 == NULL every run's Latin hypercube under its own key (_common.py:109-120), else x0.
+ * replaces: de/_de.py:208-211 (DE: into buffer 1 and into cand, so the objective never sees memory nobody wrote) and
+ *           cpso/_cpso.py:219-232 (PSO: X, V = 0, pbest = X).  Touches neither state nor f. */
+int sx_runs_rowwise_init(const sx_runs_rowwise_args *a, void *stream);
+/* after the objective has evaluated the initial rows (a->f).  replaces: de/_de.py:212-218, cpso/_cpso.py:233-247: fit (DE) /
+ * pbestfit (PSO) and candfit <- f; per run the first-minimum argmin of its P values (np.argmin's rules for NaN, +-inf
+ * and ties, as sx_argmin); state[r] = {it 1, gbidx, gfit, dx 0, SX_STATUS_NONE, done 0}; gbest[r] <- the best row.
+ * strategy: DEVICE (R) or NULL, as in sx_runs_rowwise_de_propose; an element outside SX_DE_RAND1BIN .. SX_DE_BEST2BIN, or one
+ * that needs more than P - 1 donors, ends run r here as sx_de_runs_sweep_launch documents (funs[r] = NaN, nits[r] = 0,
+ * statuses[r] = SX_STATUS_NONE, xs[r] untouched; counted in *ended). */
+int sx_runs_rowwise_start(const sx_runs_rowwise_args *a, const int32_t *strategy, void *stream);
+/* DE: pop2 (cand) <- the trial vectors of every running run's generation state[r].it + 1.
+ * replaces: de/_de.py:314-351 de_sync up to the candidates (:333-344), de/_strategy.py:1-46, de/_constraints.py:13-28 --
+ * sx_de_propose's in-kernel-draw branch per run: donors from the run's own P rows, the best row from gbest[r].  F, CR,
+ * strategy: DEVICE (R) or NULL (every run uses the struct's scalar), as in sx_de_runs_sweep_launch. */
+int sx_runs_rowwise_de_propose(const sx_runs_rowwise_args *a, const double *F, const double *CR, const int32_t *strategy,
+                               void *stream);
+/* PSO: pop1 (V) and pop0 (X) of every running run updated in place.
+ * replaces: cpso/_cpso.py:324-329 (mutation, left to right), cpso/_constraints.py:4-10, 44-53 (NoConstraint / Shrink, sync
+ * form) -- sx_pso_move's in-kernel-draw branch per run; with Shrink the raw velocities wait in the workgroup's LDS for the
+ * row-wide beta.  w, c1, c2: DEVICE (R) or NULL, as in sx_pso_runs_sweep_launch. */
+int sx_runs_rowwise_pso_move(const sx_runs_rowwise_args *a, const double *w, const double *c1, const double *c2,
+                             void *stream);
+/* selection after the evaluation (a->f), per running run.  replaces: _common.py:123-130 selection_sync, strict <:
+ * DE writes the winner or the old row into the other population buffer; PSO updates pbest in place; candfit <- f; one
+ * (part_f, part_i) record per workgroup -- sx_rows_select per run. */
+int sx_runs_rowwise_select(const sx_runs_rowwise_args *a, void *stream);
+/* best and termination of that generation, one workgroup of 256 threads per run.  replaces: _common.py:131-158 (argmin, the
+ * step of the best, the status ladder) -- sx_select_finalize per run, its dx summed in the same order: gbest[r] and state[r]
+ * updated; a run that ends writes xs[r], funs[r], nits[r], statuses[r] and adds one to *ended. */
+int sx_runs_rowwise_finalize(const sx_runs_rowwise_args *a, void *stream);
 
 #ifdef __cplusplus
 }

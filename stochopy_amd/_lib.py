@@ -171,6 +171,17 @@ class SxVdRunsArgs(C.Structure):
     ]
 
 
+class SxRunsRowwiseArgs(C.Structure):
+    _fields_ = [
+        ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("pop0", vp), ("pop1", vp), ("pop2", vp), ("fit", vp),
+        ("candfit", vp), ("f", vp), ("state", vp), ("gbest", vp), ("part_f", vp), ("part_i", vp), ("xs", vp), ("funs", vp),
+        ("nits", vp), ("statuses", vp), ("ended", vp),
+        ("R", i64), ("P", i64), ("x0_stride", i64),
+        ("n", i32), ("method", i32), ("strategy", i32), ("constraints", i32), ("maxiter", i32), ("pad", i32),
+        ("F", f64), ("CR", f64), ("w", f64), ("c1", f64), ("c2", f64), ("xtol", f64), ("ftol", f64),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/stochopy_hip.h declares
 PROTOTYPES = {
     "sx_abi_version": (C.c_int, []),
@@ -269,6 +280,13 @@ PROTOTYPES = {
     "sx_vd_runs_args_bytes": (C.c_int, []),
     "sx_vd_runs_lds_bytes": (i64, [i64, C.c_int]),
     "sx_vd_runs_workspace_bytes": (i64, [i64, i64]),
+    "sx_runs_rowwise_partials": (i64, [i64, C.c_int]),
+    "sx_runs_rowwise_init": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp]),
+    "sx_runs_rowwise_start": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp, vp]),
+    "sx_runs_rowwise_de_propose": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp, vp, vp, vp]),
+    "sx_runs_rowwise_pso_move": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp, vp, vp, vp]),
+    "sx_runs_rowwise_select": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp]),
+    "sx_runs_rowwise_finalize": (C.c_int, [C.POINTER(SxRunsRowwiseArgs), vp]),
     "sx_mt_create": (vp, [C.c_uint32]),
     "sx_mt_destroy": (None, [vp]),
     "sx_mt_seed": (None, [vp, C.c_uint32]),
@@ -315,7 +333,9 @@ def lib():
     if handle.sx_abi_version() != 1:
         raise HipLibraryError("ABI version mismatch; rebuild the library")
     for which, mirror in enumerate((SxState, SxDeArgs, SxPsoArgs, SxXchgArgs, SxCmaState, SxCmaArgs, SxVdArgs,
-                                    SxSampleArgs, SxDeRunsArgs, SxPsoRunsArgs, SxCmaRunsArgs)):
+                                    SxSampleArgs, SxDeRunsArgs, SxPsoRunsArgs, SxCmaRunsArgs, None, SxRunsRowwiseArgs)):
+        if mirror is None:  # (11: no struct; sx_vd_runs_args has sx_vd_runs_args_bytes, below)
+            continue
         if handle.sx_struct_size(which) != C.sizeof(mirror):  # (a library built against another layout of the structs)
             raise HipLibraryError(f"{LIB_PATH}: struct {which} is {handle.sx_struct_size(which)} bytes, its mirror "
                                   f"{C.sizeof(mirror)}; rebuild the library")

@@ -37,6 +37,7 @@ extern "C" int sx_struct_size(int which) {
         case 8: return (int)sizeof(sx_de_runs_args);
         case 9: return (int)sizeof(sx_pso_runs_args);
         case 10: return (int)sizeof(sx_cma_runs_args);
+        case 12: return (int)sizeof(sx_runs_rowwise_args);  // (11 stays -1: the VD-CMA runs' struct has sx_vd_runs_args_bytes)
     }
     return -1;
 }
@@ -715,21 +716,7 @@ extern "C" int sx_cmaes_eval_penalized(int fun_id, const double *X, int64_t P, i
 // ---------------------------------------------------------------------------
 // argmin: stage 1 (grid) -> partials, stage 2 (one workgroup) -> result
 // ---------------------------------------------------------------------------
-constexpr int kFinalThreads = 256;
-
-__device__ __forceinline__ void block_argmin(double &bf, int64_t &bi, double *sf, int64_t *si) {
-    wave_argmin_all(bf, bi);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        sf[w] = bf;
-        si[w] = bi;
-    }
-    __syncthreads();
-    bf = sf[0];
-    bi = si[0];
-    for (int k = 1; k < kFinalThreads / kWave; ++k) argmin_combine(bf, bi, sf[k], si[k]);
-    __syncthreads();
-}
+constexpr int kFinalThreads = kFinalWorkgroup;  // block_argmin, scan_records: sx_rowops.hpp (shared with sx_runs_unfused.hip)
 
 __global__ __launch_bounds__(kFinalThreads) void argmin_stage1(const double *__restrict__ f, int64_t P,
                                                                double *__restrict__ part_f,
@@ -780,41 +767,7 @@ extern "C" int sx_argmin(const double *f, int64_t P, double *ws_f, int64_t *ws_i
 // ---------------------------------------------------------------------------
 // Best-of-generation + termination (stochopy/optimize/_common.py:131-158)
 // ---------------------------------------------------------------------------
-// best of the per-workgroup records, 8 records per thread and trip so their loads overlap
-template <int kScan>
-__device__ __forceinline__ void scan_records_n(const double *__restrict__ part_f, const int64_t *__restrict__ part_i,
-                                               int64_t npart, double &bf, int64_t &bi) {
-    for (int64_t k0 = threadIdx.x; k0 < npart; k0 += (int64_t)kFinalThreads * kScan) {
-        double f[kScan];
-        int64_t i[kScan];
-#pragma unroll
-        for (int u = 0; u < kScan; ++u) {
-            const int64_t k = k0 + (int64_t)u * kFinalThreads;
-            f[u] = k < npart ? part_f[k] : __builtin_huge_val();
-            i[u] = k < npart ? part_i[k] : INT64_MAX;
-        }
-        // this trip's minimum in np.argmin's order (a tree), then the first record that holds it (k grows with u), then
-        // one lexicographic step into the running pair: a chain of 8 compare-and-select steps otherwise
-        double m = f[0];
-#pragma unroll
-        for (int u = 1; u < kScan; ++u) m = best_min(m, f[u]);  // (the minimum is the same in any order)
-        int64_t first = i[0];
-        double fm = f[0];  // (its own bits: the sign of a zero)
-#pragma unroll
-        for (int u = kScan - 1; u >= 0; --u)
-            if (best_tie(f[u], m)) first = i[u], fm = f[u];
-        argmin_combine(bf, bi, fm, first);
-    }
-}
-// 8 records per thread and trip; all of config 5 on one GPU (131 072 rows = 16 384 records, 64 per thread) 32: two trips
-// instead of eight dependent ones
-__device__ __forceinline__ void scan_records(const double *__restrict__ part_f, const int64_t *__restrict__ part_i,
-                                             int64_t npart, double &bf, int64_t &bi) {
-    if (npart > (int64_t)kFinalThreads * 16)
-        scan_records_n<32>(part_f, part_i, npart, bf, bi);
-    else
-        scan_records_n<8>(part_f, part_i, npart, bf, bi);
-}
+// (the best of the per-workgroup records: scan_records, sx_rowops.hpp)
 
 // dst[e] = src[e] / sum of (a[e] - b[e])^2 over the elements of this thread (e = thread, thread + 256, ...: in that order), eight
 // loads in flight per thread: the one-workgroup steps of the sharded path walk whole rows (up to 262 144 elements) with these

@@ -407,6 +407,60 @@ __device__ __forceinline__ void block_partial(double val, const RowIds<LPR> &id,
     }
 }
 
+// ---- the one-workgroup steps behind a generation (sx_core.hip: argmin, best / termination; sx_runs_unfused.hip: one such
+//      workgroup per run): kFinalWorkgroup threads reduce records by np.argmin's first-minimum rule
+constexpr int kFinalWorkgroup = 256;
+
+__device__ __forceinline__ void block_argmin(double &bf, int64_t &bi, double *sf, int64_t *si) {
+    wave_argmin_all(bf, bi);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        sf[w] = bf;
+        si[w] = bi;
+    }
+    __syncthreads();
+    bf = sf[0];
+    bi = si[0];
+    for (int k = 1; k < kFinalWorkgroup / kWave; ++k) argmin_combine(bf, bi, sf[k], si[k]);
+    __syncthreads();
+}
+
+// best of the per-workgroup records, 8 records per thread and trip so their loads overlap
+template <int kScan>
+__device__ __forceinline__ void scan_records_n(const double *__restrict__ part_f, const int64_t *__restrict__ part_i,
+                                               int64_t npart, double &bf, int64_t &bi) {
+    for (int64_t k0 = threadIdx.x; k0 < npart; k0 += (int64_t)kFinalWorkgroup * kScan) {
+        double f[kScan];
+        int64_t i[kScan];
+#pragma unroll
+        for (int u = 0; u < kScan; ++u) {
+            const int64_t k = k0 + (int64_t)u * kFinalWorkgroup;
+            f[u] = k < npart ? part_f[k] : __builtin_huge_val();
+            i[u] = k < npart ? part_i[k] : INT64_MAX;
+        }
+        // this trip's minimum in np.argmin's order (a tree), then the first record that holds it (k grows with u), then
+        // one lexicographic step into the running pair: a chain of 8 compare-and-select steps otherwise
+        double m = f[0];
+#pragma unroll
+        for (int u = 1; u < kScan; ++u) m = best_min(m, f[u]);  // (the minimum is the same in any order)
+        int64_t first = i[0];
+        double fm = f[0];  // (its own bits: the sign of a zero)
+#pragma unroll
+        for (int u = kScan - 1; u >= 0; --u)
+            if (best_tie(f[u], m)) first = i[u], fm = f[u];
+        argmin_combine(bf, bi, fm, first);
+    }
+}
+// 8 records per thread and trip; all of config 5 on one GPU (131 072 rows = 16 384 records, 64 per thread) 32: two trips
+// instead of eight dependent ones
+__device__ __forceinline__ void scan_records(const double *__restrict__ part_f, const int64_t *__restrict__ part_i,
+                                             int64_t npart, double &bf, int64_t &bi) {
+    if (npart > (int64_t)kFinalWorkgroup * 16)
+        scan_records_n<32>(part_f, part_i, npart, bf, bi);
+    else
+        scan_records_n<8>(part_f, part_i, npart, bf, bi);
+}
+
 // ---- DE donor rows (shared by the synchronous and the sequential kernels)
 constexpr int kMaxDonors = 5;
 

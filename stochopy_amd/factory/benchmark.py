@@ -78,16 +78,26 @@ class batched:
 
     This package itself never evaluates an objective on the host.  A caller whose objective only exists as
     numpy code can do the round trip inside ``fun`` (``X.cpu().numpy()`` in, a tensor on ``X.device`` out) -- it is
-    then their code that is slow, visibly, and the generations are launched one by one instead of as a graph."""
+    then their code that is slow, visibly, and the generations are launched one by one instead of as a graph.
 
-    def __init__(self, fun):
+    ``rowwise=True`` is the caller's promise that the value of a row depends on that row only, so rows of several
+    independent runs may be handed over in one call: ``fun`` does not look across rows or at ``X.shape[0]``.  Only an
+    objective declared this way is served with ``options["runs"] = R`` (de, pso): ``fun`` then receives the stacked
+    ``(R * P, n)`` tensor -- row ``r * P + i`` is individual i of run r -- once per generation and returns ``(R * P,)``; a run
+    that has ended is frozen, and ``fun`` still receives its last candidate rows until every run has ended.  Single runs and
+    the samplers ignore the flag."""
+
+    def __init__(self, fun, *, rowwise=False):
         if not hasattr(fun, "__call__"):
             raise TypeError()
+        if not isinstance(rowwise, bool):
+            raise TypeError(f"rowwise={rowwise!r}: expected True or False")
         self.fun = fun
+        self.rowwise = rowwise
         self.__name__ = getattr(fun, "__name__", "objective")
 
     def __repr__(self):
-        return f"<stochopy_amd device-batched objective {self.__name__}>"
+        return f"<stochopy_amd device-batched objective {self.__name__}{', rowwise=True' if self.rowwise else ''}>"
 
     def __call__(self, *a, **k):
         return self.fun(*a, **k)

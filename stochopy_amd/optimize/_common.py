@@ -45,10 +45,13 @@ def resolve_backend(backend, fun_id=None):
 class External:
     """A caller-supplied objective as the generation loops use it: ``ext(ctx, X)`` -> (P,) device tensor."""
 
+    rowwise = False  # factory.batched(f, rowwise=True): rows of several runs may be handed over in one call (_runs.py)
+
     def __init__(self, tagged, args):
         self.fun = tagged.fun
         self.args = tuple(args) if args not in ((), None) else ()
         self.name = tagged.__name__
+        self.rowwise = bool(getattr(tagged, "rowwise", False))
 
     def __call__(self, ctx, X):
         t = __import__("torch")

@@ -68,6 +68,14 @@ def minimize(
     is 0 never restarts); the result then has ``sweep``, a dict from the name of each such option to the ``(R,)`` array
     used.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a swarm that fits one workgroup's LDS (``sx_pso_runs_lds_bytes``).
+    A caller's own objective is served with ``runs=R`` when it is declared row-wise, ``factory.batched(f, rowwise=True)``
+    (the value of a row depends on that row only), and no run can restart (``competitivity`` ``None`` or 0, for every
+    run): the R swarms then live in device memory (csrc/sx_runs_unfused.hip; no LDS limit, ``popsize * R < 2**31``) and
+    ``f(X, *args)`` is called ONCE per generation on the stacked ``(R * P, n)`` float64 tensor -- row ``r * P + i`` is
+    particle i of run r -- returning ``(R * P,)``.  Run r is, bit for bit, the run ``minimize(factory.batched(f), ...)``
+    performs with seed r, ``rng="philox", updating="deferred"``; the other limits and the result are those above.  A run
+    that has ended is frozen; ``f`` still receives its last rows until every run has ended.  An undeclared
+    ``factory.batched(f)`` is refused with ``runs``.
     """
     batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
@@ -113,11 +121,21 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competiti
     """``runs=R``: R independent deferred-updating runs, one workgroup each, one launch (csrc/sx_pso_runs.hip).  Everything
     that can be refused is refused before the device is touched."""
     n = len(lower)
-    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all, serves_rowwise=True)
+    if _runs.rowwise(fun_id) and competitivity is not None and np.any(competitivity):
+        raise ValueError(f"runs > 1 around a factory.batched(f, rowwise=True) objective serves PSO, i.e. competitivity None "
+                         f"or 0 for every run (competitivity={competitivity!r}): the competitive restart is not part of "
+                         "that path")
     _runs.refuse_immediate(updating, strict_updating, "cpso/_cpso.py:147-150")
     seeds = _runs.seeds_of(R, seed)
     if n > _lib.wide_from():
         raise ValueError(f"runs > 1 serves rows of up to {_lib.wide_from()} elements (n = {n})")
+    if _runs.rowwise(fun_id):  # the caller's own objective: the swarms live in device memory, no LDS limit
+        if R * P >= 1 << 31:
+            raise ValueError(f"runs={R} x popsize {P}: the objective is handed all runs' rows at once, fewer than 2^31")
+        batch = _rowwise_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, constraints, xtol, ftol)
+        batch.launch()
+        return _runs.result(batch.fetch(), P, inertia=w, cognitivity=c1, sociability=c2, competitivity=competitivity)
     if int(_lib.lib().sx_pso_runs_lds_bytes(P, n)) < 0:
         raise ValueError(f"runs > 1 keeps a run's swarm (X and pbest at the least) in one workgroup's LDS: popsize {P} x {n} "
                          "variables is more than its 160 KiB hold")
@@ -156,6 +174,18 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, w, c1, c2, competit
     a.n, a.fun_id = n, fun_id
     a.constraints, a.maxiter = (1 if constraints == "Shrink" else 0), maxiter
     a.w, a.c1, a.c2, a.gamma, a.delta, a.xtol, a.ftol = own["w"], own["c1"], own["c2"], own["gamma"], delta, xtol, ftol
+    return batch
+
+
+def _rowwise_batch(seeds, external, lower, upper, x0, maxiter, P, w, c1, c2, constraints, xtol, ftol):
+    """The device-memory batch around a caller's row-wise objective (csrc/sx_runs_unfused.hip): PSO's struct fields and sweep
+    arrays.  pop0 is X -- the rows the objective is handed --, pop1 V and pop2 pbest.  ``w``, ``c1``, ``c2``: as in
+    ``_runs_batch``."""
+    batch = _runs.RowwiseBatch("sx_runs_rowwise_pso_move", external, seeds, lower, upper, x0, maxiter, P,
+                               constraints == "Shrink", xtol, ftol)
+    with batch.stream():
+        own = batch.bind_sweep(w=w, c1=c1, c2=c2)
+    batch.a.w, batch.a.c1, batch.a.c2 = own["w"], own["c1"], own["c2"]
     return batch
 
 

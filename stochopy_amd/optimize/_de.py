@@ -79,6 +79,13 @@ def minimize(
     run (a sweep: run r is the single run with element r of each and seed r); the result then has ``sweep``, a dict from
     the name of each such option to the ``(R,)`` array used.  Needs ``rng="philox"``, a factory objective, one GPU, no callback, no ``return_all``, rows of at most
     ``sx_wide_from()`` elements and a population whose two generations fit one workgroup's LDS (``sx_de_runs_lds_bytes``).
+    A caller's own objective is served with ``runs=R`` when it is declared row-wise, ``factory.batched(f, rowwise=True)``
+    (the value of a row depends on that row only): the R populations then live in device memory (csrc/sx_runs_unfused.hip;
+    no LDS limit, ``popsize * R < 2**31``) and ``f(X, *args)`` is called ONCE per generation on the stacked ``(R * P, n)``
+    float64 tensor -- row ``r * P + i`` is individual i of run r -- returning ``(R * P,)``.  Run r is, bit for bit, the run
+    ``minimize(factory.batched(f), ...)`` performs with seed r, ``rng="philox", updating="deferred"``; the other limits
+    and the result are those above.  A run that has ended is frozen; ``f`` still receives its last candidate rows until
+    every run has ended.  An undeclared ``factory.batched(f)`` is refused with ``runs``.
     """
     batched_runs = _runs.batched(runs)
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
@@ -132,11 +139,17 @@ def _minimize_runs(R, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, con
     """``runs=R``: R independent deferred-updating runs, one workgroup each, one launch (csrc/sx_de_runs.hip).  Everything
     that can be refused is refused before the device is touched."""
     n = len(lower)
-    _runs.refuse_common(rng, fun_id, workers, callback, return_all)
+    _runs.refuse_common(rng, fun_id, workers, callback, return_all, serves_rowwise=True)
     _runs.refuse_immediate(updating, strict_updating, "de/_de.py:142-145")
     seeds = _runs.seeds_of(R, seed)
     if n > _lib.wide_from():
         raise ValueError(f"runs > 1 serves rows of up to {_lib.wide_from()} elements (n = {n})")
+    if _runs.rowwise(fun_id):  # the caller's own objective: the populations live in device memory, no LDS limit
+        if R * P >= 1 << 31:
+            raise ValueError(f"runs={R} x popsize {P}: the objective is handed all runs' rows at once, fewer than 2^31")
+        batch = _rowwise_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol)
+        batch.launch()
+        return _runs.result(batch.fetch(), P, mutation=F, recombination=CR, strategy=strategy)
     if int(_lib.lib().sx_de_runs_lds_bytes(P, n)) < 0:
         raise ValueError(f"runs > 1 keeps a run's two generations in one workgroup's LDS: popsize {P} x {n} variables "
                          "is more than its 160 KiB hold")
@@ -167,6 +180,22 @@ def _runs_batch(seeds, fun_id, lower, upper, x0, maxiter, P, F, CR, strategy, co
     a.n, a.fun_id, a.strategy = n, fun_id, own["strategy"]
     a.constraints, a.maxiter = (1 if constraints == "Random" else 0), maxiter
     a.F, a.CR, a.xtol, a.ftol = own["F"], own["CR"], xtol, ftol
+    return batch
+
+
+def _rowwise_batch(seeds, external, lower, upper, x0, maxiter, P, F, CR, strategy, constraints, xtol, ftol):
+    """The device-memory batch around a caller's row-wise objective (csrc/sx_runs_unfused.hip): DE's struct fields and sweep
+    arrays.  Generation g of a run lives in pop0 / pop1 by parity, the objective is handed pop2 (the candidates).  ``F``,
+    ``CR``, ``strategy``: as in ``_runs_batch``."""
+    if _runs.is_swept(strategy):
+        strategy = np.array([_lib.DE_STRATEGIES[name] for name in strategy], dtype=np.int32)
+    else:
+        strategy = _lib.DE_STRATEGIES[strategy]
+    batch = _runs.RowwiseBatch("sx_runs_rowwise_de_propose", external, seeds, lower, upper, x0, maxiter, P,
+                               constraints == "Random", xtol, ftol)
+    with batch.stream():
+        own = batch.bind_sweep(F=F, CR=CR, strategy=strategy)
+    batch.a.strategy, batch.a.F, batch.a.CR = own["strategy"], own["F"], own["CR"]
     return batch
 
 

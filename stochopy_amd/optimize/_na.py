@@ -13,7 +13,7 @@ makes a run reproduce the reference bit for bit (numpy-legacy draws; ``+ - *`` o
 import numpy as np
 
 from .. import _device, _lib, _rng
-from . import _common
+from . import _common, _runs
 from ._helpers import OptimizeResult, register
 
 __all__ = ["minimize"]
@@ -40,10 +40,15 @@ def minimize(
     rng=None,
     host_workers=None,
     host_backend=None,
+    runs=None,
 ):
     """Minimize an objective function using the Neighbourhood Algorithm on MI355X (reference na/_na.py:11-27; its
     ``callback=True`` default -- which makes a direct call raise -- is not copied: ``None`` here, as through
-    ``stochopy.optimize.minimize``).  One GPU (``workers=1``): the model store is shared by all walks."""
+    ``stochopy.optimize.minimize``).  One GPU (``workers=1``): the model store is shared by all walks.  ``runs`` > 1 (many
+    independent runs in one launch: de, pso / cpso, cmaes, vdcma) is refused."""
+    if _runs.batched(runs):
+        raise ValueError(f"runs={runs}: method 'na' performs one run a call (every walk reads the run's whole model store); "
+                         "runs > 1 is served by de, pso / cpso, cmaes and vdcma")
     fun_id = _common.resolve_objective(fun, args, workers, backend, host_workers, host_backend)
     lower, upper = _common.as_bounds(bounds)
     if x0 is not None:

@@ -1,6 +1,7 @@
 """``options["runs"] = R``: the host path the batched methods share (de, pso / cpso, cmaes, vdcma) -- the option's
 validation, the refusals, the seed rule, the batch that one ``sx_*_runs_launch`` takes, and the result.  A method module
 keeps the one function that builds its batch (its constants, its inputs, its struct fields) and its own refusals.
+``RowwiseBatch`` is the device-memory batch DE and PSO share around a caller's row-wise objective.
 """
 import ctypes as C
 import warnings
@@ -91,13 +92,26 @@ def setting(value):
     return value if is_swept(value) else float(value)
 
 
-def refuse_common(rng, fun_id, workers, callback, return_all):
-    """What no batched method serves: a run lives in one kernel on one GPU."""
+def rowwise(fun_id):
+    """Is the objective a caller's own that declared ``factory.batched(f, rowwise=True)``?"""
+    return not isinstance(fun_id, int) and getattr(fun_id, "rowwise", False) is True
+
+
+def refuse_common(rng, fun_id, workers, callback, return_all, serves_rowwise=False):
+    """What no batched method serves: a run lives in one kernel on one GPU.  ``serves_rowwise``: the calling method has a
+    device-memory path around a caller's row-wise objective (de, pso: ``RowwiseBatch``); the others refuse those too."""
     if rng != "philox":
         raise ValueError('runs > 1 needs rng="philox": a run is told apart by its Philox key (in-kernel, counter-based draws)')
     if not isinstance(fun_id, int):
-        raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
-                         "(factory.batched and plain callables run between kernels)")
+        if not rowwise(fun_id):
+            raise ValueError("runs > 1 needs a stochopy_amd.factory objective: it is evaluated inside the run's kernel "
+                             "(factory.batched and plain callables run between kernels) -- or, for de and pso, an objective "
+                             "declared factory.batched(f, rowwise=True): the rows of all runs are handed over in one call, "
+                             "which is only correct when the value of a row depends on that row alone")
+        if not serves_rowwise:
+            raise ValueError("runs > 1 around a factory.batched(f, rowwise=True) objective is served by de and pso (cpso: "
+                             "without the competitive restart); this method needs a stochopy_amd.factory objective, which "
+                             "is evaluated inside the run's kernel")
     if workers not in (None, 1):
         raise ValueError(f"runs > 1 uses one GPU (workers={workers})")
     if callback is not None:
@@ -223,6 +237,72 @@ class Batch:
         """The outputs as numpy arrays, by name."""
         with self.stream():
             return {name: self.dev[name].cpu().numpy() for name in self.out}
+
+
+class RowwiseBatch(Batch):
+    """R runs of DE or PSO around a caller's row-wise objective (``factory.batched(f, rowwise=True)``), in device memory
+    (csrc/sx_runs_unfused.hip): three ``(R, P, n)`` populations, the per-run states and best rows, the records of the
+    selection.  There is no LDS limit.  A generation of ALL runs is the method's propose / move kernel, ONE call of the
+    objective on the stacked ``(R * P, n)`` rows, the selection kernel and one best / termination workgroup per run.  A run
+    that has ended is frozen -- its workgroups return at entry -- and the objective still receives its last candidate rows
+    until every run has ended.  ``entry`` is the method's propose / move entry point; a method module sets its own struct
+    fields and sweep arrays, then ``launch()`` and ``fetch()`` as with a ``Batch``."""
+
+    # the per-run arrays of the propose / move entries, in the order of their arguments
+    SWEEP = {"sx_runs_rowwise_de_propose": ("F", "CR", "strategy"), "sx_runs_rowwise_pso_move": ("w", "c1", "c2")}
+    # entry -> (sx_runs_rowwise_args.method, the population the objective is handed: DE's candidates, PSO's positions)
+    KINDS = {"sx_runs_rowwise_de_propose": (0, "pop2"), "sx_runs_rowwise_pso_move": (1, "pop0")}
+
+    def __init__(self, entry, external, seeds, lower, upper, x0, maxiter, P, constrained, xtol, ftol):
+        super().__init__(entry, _lib.SxRunsRowwiseArgs(), seeds, P)
+        a, ctx, R, t = self.a, self.ctx, self.R, _device.torch()
+        n = self.n = len(lower)
+        self.external, self.maxiter = external, maxiter
+        per_run = int(ctx.L.sx_runs_rowwise_partials(P, n))
+        with self.stream():
+            self.upload_keys()
+            d_bounds = ctx.upload_async(np.concatenate([lower, upper]))
+            self.bind(lower=d_bounds[:n], upper=d_bounds[n:])
+            if x0 is not None:
+                self.bind(x0=ctx.upload(np.array(x0, dtype=np.float64)))
+                a.x0_stride = P * n if self.dev["x0"].dim() == 3 else 0
+            self.bind(pop0=ctx.empty((R, P, n)), pop1=ctx.empty((R, P, n)), pop2=ctx.empty((R, P, n)),
+                      fit=ctx.empty((R * P,)), candfit=ctx.empty((R * P,)), state=ctx.zeros((R, 8), dtype=t.int64),
+                      gbest=ctx.empty((R, n)), part_f=ctx.empty((R, per_run)), part_i=ctx.empty((R, per_run), dtype=t.int64),
+                      ended=ctx.zeros((1,), dtype=t.int32))
+            self.outputs(n, {}, ())
+        a.n, a.method, a.constraints, a.maxiter, a.xtol, a.ftol = n, self.KINDS[entry][0], int(constrained), maxiter, xtol, ftol
+
+    def _evaluate(self, X):
+        """One call of the objective on all runs' rows; the kernels read its values where it left them (no copy)."""
+        f = self.dev["f"] = self.external(self.ctx, X)  # (kept until the next call: the kernels that read it are enqueued by then)
+        self.a.f = f.data_ptr()
+
+    def launch(self):
+        """All runs, from the initial populations to each run's own termination.  Generations are enqueued eagerly on the
+        engine stream, ``_PopulationRun.CHECK_EVERY`` at a time (fewer when ``maxiter`` leaves fewer); then one 4-byte
+        read-back tells whether any run is still active."""
+        from ._population import _PopulationRun
+
+        L, a, sp, R, move = self.ctx.L, C.byref(self.a), self.ctx.stream_ptr, self.R, self.entry
+        X = self.dev[self.KINDS[move][1]].view(R * self.P, self.n)
+        sweep = [self.sweep[name].data_ptr() if name in self.sweep else None for name in self.SWEEP[move]]
+        strategy = self.sweep["strategy"].data_ptr() if "strategy" in self.sweep else None
+        with self.stream():
+            _lib.check(L.sx_runs_rowwise_init(a, sp), "sx_runs_rowwise_init")
+            self._evaluate(X)
+            _lib.check(L.sx_runs_rowwise_start(a, strategy, sp), "sx_runs_rowwise_start")
+            it = 1  # the generation every run that is still active holds
+            while True:
+                # maxiter <= 1: the reference still runs one generation before it tests `it >= maxiter`
+                for _ in range(min(max(self.maxiter - it, 1), _PopulationRun.CHECK_EVERY)):
+                    _lib.check(getattr(L, move)(a, *sweep, sp), move)
+                    self._evaluate(X)
+                    _lib.check(L.sx_runs_rowwise_select(a, sp), "sx_runs_rowwise_select")
+                    _lib.check(L.sx_runs_rowwise_finalize(a, sp), "sx_runs_rowwise_finalize")
+                    it += 1
+                if int(self.dev["ended"].cpu()[0]) >= R:  # (generations enqueued for a run that has ended are no-ops)
+                    break
 
 
 def result(out, P, **settings):

@@ -25,7 +25,12 @@ Every run of de, pso, cpso and vdcma must do its 200 generations (checked).
 Everything is warmed up once, then the configurations take turns for --rounds rounds; a line gives the median and the spread
 (min .. max) of its rounds, in objective evaluations per second (nit x popsize per run).
 
-    python tools/bench_runs.py [--method de|pso|cpso|cmaes|vdcma ...] [--sweep] [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
+    --rowwise                      instead of all that (--method de, pso): runs=R around a caller's own row-wise device
+                                   objective, factory.batched(f, rowwise=True) -- csrc/sx_runs_unfused.hip -- as whole-call wall
+                                   times next to the loop of single minimize(factory.batched(f)) calls and, where it fits, the
+                                   resident factory batch (rowwise_main below; shapes: ROWWISE_SHAPES).
+
+    python tools/bench_runs.py [--method de|pso|cpso|cmaes|vdcma ...] [--sweep | --rowwise] [--rounds 5] [--window 0.25] [--loop-calls 64] [--out FILE]
 """
 import argparse
 import importlib
@@ -129,10 +134,102 @@ def timed(config, batch, launches=1, swept=False):
     return e0.elapsed_time(e1) * 1e-3 / launches, int(nits.sum()) * config.P, full
 
 
+# --rowwise: (ndim, popsize, runs, maxiter): README's own shape, and one large shape the resident path refuses
+ROWWISE_SHAPES = ((32, 32, 4096, MAXITER), (128, 1024, 64, 50))
+
+
+def rowwise_objectives(sa, name):
+    """objective name -> (device function, factory objective with the same values or None): the library's own sx_eval wrapped
+    as a caller's device function (tests/test_gpu_sample_batched.py device_objective), and a quadratic written in torch."""
+    import ctypes as C
+
+    t = __import__("torch")
+    from stochopy_amd import _lib
+
+    L, fid = _lib.lib(), _lib.FUN_IDS[name]
+
+    def sx_eval(X):
+        P, n = X.shape
+        f = t.empty((P,), dtype=t.float64, device=X.device)
+        assert L.sx_eval(fid, X.data_ptr(), P, n, n, None, None, f.data_ptr(), None, None,
+                         C.c_void_p(t.cuda.current_stream().cuda_stream)) == 0
+        return f
+
+    def torch_quadratic(X):
+        return (X * X).sum(dim=1)
+
+    return {"sx_eval " + name: (sx_eval, getattr(sa.factory, name)), "torch quadratic": (torch_quadratic, None)}
+
+
+def rowwise_main(args, sa, ctx):
+    """--rowwise: whole-call wall times (ending in a synchronise, after a warm-up, the forms alternated) of
+        rowwise    minimize(factory.batched(f, rowwise=True), ..., runs=R): R populations in device memory, f once a generation
+        loop       --loop-calls single minimize(factory.batched(f)) calls, seeds s, s + 1, ...; the loop's time for R runs is
+                   R times its time per call (a rate, as above: not a measurement of R calls)
+        resident   with the sx_eval wrapper, where the shape fits the LDS: minimize(factory.<objective>, ..., runs=R), the
+                   fused resident batch -- the difference to `rowwise` is the price of unfusing."""
+    lines = []
+    for method in args.method:
+        if method not in ("de", "pso"):
+            raise SystemExit("--rowwise serves --method de and --method pso")
+        w = WORKLOADS[method]
+        for n, P, R, maxiter in ROWWISE_SHAPES:
+            bounds = [[-w["half"], w["half"]]] * n
+            base = dict(COMMON, popsize=P, maxiter=maxiter, **w["opts"])
+            for label, (fun, fused) in rowwise_objectives(sa, w["objective"]).items():
+                forms = {"rowwise": lambda: sa.optimize.minimize(sa.factory.batched(fun, rowwise=True), bounds, method=method,
+                                                                 options=dict(base, seed=SEED, runs=R))}
+                if fused is not None:
+                    try:
+                        sa.optimize.minimize(fused, bounds, method=method, options=dict(base, seed=SEED, runs=R))
+                        forms["resident"] = lambda: sa.optimize.minimize(fused, bounds, method=method,
+                                                                         options=dict(base, seed=SEED, runs=R))
+                    except ValueError:  # the shape does not fit the LDS
+                        pass
+
+                def loop():
+                    for r in range(args.loop_calls):
+                        sa.optimize.minimize(sa.factory.batched(fun), bounds, method=method, options=dict(base, seed=SEED + r))
+
+                forms["loop"] = loop
+                for form in forms.values():  # warm-up: code objects, graphs, allocator
+                    form()
+                ctx.sync()
+                secs = {name: [] for name in forms}
+                for _ in range(args.rounds):
+                    for name, form in forms.items():
+                        t0 = time.perf_counter()
+                        res = form()
+                        ctx.sync()
+                        secs[name].append(time.perf_counter() - t0)
+                        assert name == "loop" or (res.nits == maxiter).all()
+                evals = R * maxiter * P
+                line = {"config": "rowwise", "method": method, "objective": label, "ndim": n, "popsize": P, "runs": R,
+                        "maxiter": maxiter, "rounds": args.rounds, "loop_calls_timed": args.loop_calls}
+                for name, s in secs.items():
+                    s = np.array(s) * (R / args.loop_calls if name == "loop" else 1.0)
+                    line.update({name + "_seconds_median": float(np.median(s)), name + "_seconds_min": float(s.min()),
+                                 name + "_seconds_max": float(s.max()), name + "_evals_per_s": evals / float(np.median(s))})
+                # ratios of median seconds: how many times as long as the row-wise batch the loop takes (above 1: the batch is
+                # faster), and how many times as long as the resident batch the row-wise one takes (the price of unfusing)
+                line["loop_seconds_over_rowwise_seconds"] = line["loop_seconds_median"] / line["rowwise_seconds_median"]
+                if "resident" in secs:
+                    line["rowwise_seconds_over_resident_seconds"] = (line["rowwise_seconds_median"]
+                                                                     / line["resident_seconds_median"])
+                lines.append(line)
+                print(json.dumps(line), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--method", nargs="+", choices=sorted(WORKLOADS), default=["de"])
     ap.add_argument("--sweep", action="store_true", help="also time every batch with its per-run arrays bound")
+    ap.add_argument("--rowwise", action="store_true",
+                    help="time runs=R around a caller's row-wise device objective instead (de, pso): see rowwise_main")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per timed round")
     ap.add_argument("--loop-calls", type=int, default=64)
@@ -142,6 +239,8 @@ def main():
     from stochopy_amd import _device
 
     ctx = _device.Context()
+    if args.rowwise:
+        return rowwise_main(args, sa, ctx)
     configs = [Config(sa, method, n, P) for method in args.method for n, P in WORKLOADS[method]["shapes"]]
     batches = [(c, R, c.batch(R)) for c in configs for R in RUNS]
     swept = [(c, R, c.batch(R, swept=True)) for c in configs for R in RUNS] if args.sweep else []
