@@ -732,6 +732,40 @@ int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, co
                      const double *k0, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Parallel tempering (replica exchange) for the Metropolis-Hastings chains (csrc/sx_sample_temper.hip): C ladders of K
+ * device-resident replicas.  No counterpart in the reference.  Replica q = c K + k is rung k of ladder c and samples
+ * p^(beta[k]), beta[k] = 1 / T_k with 1 = T_0 < T_1 < ...: sx_sample_run's mcmc sample with d = (fcur - fprop) * beta[k]
+ * and every draw keyed by q in the place of the chain index (beta[0] = 1.0: the cold rung's rule is sx_sample_run's,
+ * bit for bit).  After sample it >= 1 with it % swap_every == 0 the exchange event j = it / swap_every pairs rungs
+ * (0,1), (2,3), ... (odd j) or (1,2), (3,4), ... (even j); a rung without a partner sits out.  The pair (k, k+1)
+ * exchanges its STATES (cur and fcur; rungs stay) when  min(0, d) > log(u),  d = (beta[k] - beta[k+1]) (f_k - f_{k+1})
+ * (a NaN d exchanges), u = first double of Philox (slot 0, row = replica of rung k, gen = it, purpose 14).  Sample `it`
+ * of a replica is its state after the event; an arriving state is compared with facc / iacc / xbest and fmin / imin as
+ * an accepted proposal of sample `it` is, and moves neither nacc nor nfeas.
+ * One ladder lives inside one workgroup (an exchange is two workgroup barriers and a row copy in LDS): one launch per
+ * run, nothing passes between workgroups, a ladder's run does not depend on C or on the launch geometry.
+ * ------------------------------------------------------------------------- */
+/* a->C = C*K replicas (every per-chain array that long); a->xall / funall: (C, maxiter, n) / (C, maxiter), cold rungs only;
+   beta (K) DEVICE; nswap (C*K) DEVICE int64: accepted exchanges of the pair whose LOWER rung this replica is, carried across
+   launches (written by the launch that generates sample 0).  method = SX_SAMPLE_MCMC, rng = SX_RNG_PHILOX. */
+int sx_sample_tempered_run(const sx_sample_args *a, const double *beta, int K, int64_t swap_every, int64_t *nswap,
+                           int64_t it0, int64_t steps, void *stream);
+/* the largest K of a row length: K rows of the mcmc kernel's LDS fit the 160 KiB of a workgroup and its row limit
+ * (16 rows, 8 wavefronts); -1 for a row length the samplers do not serve */
+int sx_sample_tempered_max_rungs(int n);
+/* Around a caller-supplied objective (csrc/sx_sample_unfused.hip), sample `it` of a tempered run:
+ *   sx_sample_propose -> fprop = fun(prop) -> sx_sample_decide_tempered -> on an event: sx_sample_swap
+ * With bit-identical objective values this is sx_sample_tempered_run's run, bit for bit.
+ * sx_sample_decide_tempered: sx_sample_decide for mcmc with beta (K) DEVICE; cold rungs write row `it` of xall / funall at
+ * their ladder's index when record != 0 -- pass record = 0 when an odd event follows (sx_sample_swap then writes it). */
+int sx_sample_decide_tempered(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
+                              const double *beta, int K, int record, void *stream);
+/* exchange event j (= it / swap_every >= 1) after sample `it`: one row group per pair, the states in device memory (cur,
+ * fcur and the best values of a->..., nswap as above).  At odd j it writes row `it` of xall / funall (the state of rung 0
+ * after the event).  No launch when no rung has a partner (K = 2, even j). */
+int sx_sample_swap(const sx_sample_args *a, int64_t it, int64_t j, const double *beta, int K, int64_t *nswap, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).
  * replaces: R calls of de/_de.py:176-301 (`de`: initial population :208-218, the generation loop :236-283) with
  *           de_sync (:314-351), the strategies (de/_strategy.py:1-46), Random (de/_constraints.py:13-28),

@@ -264,6 +264,10 @@ PROTOTYPES = {
     "sx_sample_fd_rows": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
     "sx_sample_fd_gradient": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
     "sx_sample_decide": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, vp, vp]),
+    "sx_sample_tempered_run": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, i64, vp, i64, i64, vp]),
+    "sx_sample_tempered_max_rungs": (C.c_int, [C.c_int]),
+    "sx_sample_decide_tempered": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "sx_sample_swap": (C.c_int, [C.POINTER(SxSampleArgs), i64, i64, vp, C.c_int, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_sweep_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp, vp, vp, vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),

@@ -177,6 +177,7 @@ enum : uint32_t {
     kPurposeSampleMomentum = 11, // hmc: the momentum normal of element e, same halves
     kPurposeSampleAccept = 12,   // the acceptance uniform: slot 0, first double of the call
     kPurposeSampleInit = 13,     // the initial point (gen 0): the uniform of element e
+    kPurposeSampleSwap = 14,     // parallel tempering: the exchange uniform of a pair: slot 0, row = the LOWER rung's replica, first double
 };
 
 // Element e of a row sits in lane l = e % LPR of the row's lanes at step q = e / LPR (LPR a power of two).

@@ -20,23 +20,6 @@ int make_plan_arg(int fun_id, int n, PlanArg *out);
 
 namespace {
 
-enum { kMcmc = 0, kHmcFd = 1, kHmcAnalytic = 2 };  // kernel variants
-
-// doubles of LDS one chain needs
-__host__ __device__ inline int sample_row_doubles(int variant, int n) {
-    const int S = gen_row_stride(n);
-    return variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S;
-}
-// waves per workgroup: the largest power of two with <= 16 chains and <= 64 KiB of LDS; one wave may need more than that
-// (hmc with finite differences on rows of ~2 048 elements: the launch then raises the kernel's dynamic-LDS limit)
-inline int sample_waves(int variant, int n) {
-    const int rpw = kWave / lanes_per_row(n);
-    const int fit = (64 * 1024) / (8 * sample_row_doubles(variant, n) * rpw);
-    int w = 1;
-    while (2 * w <= fit && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w <= kMaxWavesPerBlock) w *= 2;
-    return w;
-}
-
 // f(e, dF/dx_e) for every element this lane owns; Q complete and fenced by the caller
 template <int FUN, int LPR, class F>
 __device__ __forceinline__ void grad_apply(const double *Q, int n, int l, F &&f) {

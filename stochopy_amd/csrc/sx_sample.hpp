@@ -1,11 +1,29 @@
 // Device helpers the sampler kernels share: the resident chain kernels (sx_sample.hip) and the kernels around a
 // caller-supplied objective (sx_sample_unfused.hip) compile the SAME expressions from here -- with bit-identical objective
-// (and gradient) values the two paths give the same run, bit for bit.
+// (and gradient) values the two paths give the same run, bit for bit.  The tempered ladders (sx_sample_temper.hip, and their
+// decide / swap kernels in sx_sample_unfused.hip) share them too, with the exchange rule at the end of this file.
 #pragma once
 #include "sx_rowops.hpp"
 
 namespace sx {
 namespace {
+
+enum { kMcmc = 0, kHmcFd = 1, kHmcAnalytic = 2 };  // kernel variants
+
+// doubles of LDS one chain needs (the resident kernels: sx_sample.hip, sx_sample_temper.hip)
+__host__ __device__ inline int sample_row_doubles(int variant, int n) {
+    const int S = gen_row_stride(n);
+    return variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S;
+}
+// waves per workgroup: the largest power of two with <= 16 chains and <= 64 KiB of LDS; one wave may need more than that
+// (hmc with finite differences on rows of ~2 048 elements: the launch then raises the kernel's dynamic-LDS limit)
+inline int sample_waves(int variant, int n) {
+    const int rpw = kWave / lanes_per_row(n);
+    const int fit = (64 * 1024) / (8 * sample_row_doubles(variant, n) * rpw);
+    int w = 1;
+    while (2 * w <= fit && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w <= kMaxWavesPerBlock) w *= 2;
+    return w;
+}
 
 template <int LPR>
 __device__ __forceinline__ double row_prod(double v) {
@@ -65,7 +83,30 @@ struct ChainState {
         arg_best = best_before(f, fmin);
         if (arg_best) fmin = f, imin = it;
     }
+    // parallel tempering: a state of value f ARRIVES by an exchange at sample `it` -- compared as an accepted sample is, but an
+    // exchange is no proposal (nacc and nfeas stay)
+    __device__ __forceinline__ void arrive(double f, int64_t it, bool &acc_best) {
+        fcur = f;
+        acc_best = f < facc;
+        if (acc_best) facc = f, iacc = it;
+        if (best_before(f, fmin)) fmin = f, imin = it;
+    }
 };
+
+// parallel tempering, the exchange of rungs (kl, kl + 1) of a ladder after sample `it`: both replicas exchange their states when
+// this holds.  fl / fu their current values, bl / bu their inverse temperatures, ql the LOWER rung's replica index.
+__device__ __forceinline__ bool tempered_swap(double fl, double fu, double bl, double bu, uint32_t ql, uint32_t it, uint32_t k0,
+                                              uint32_t k1) {
+    const U4 w = philox4x32_10(0u, ql, it, kPurposeSampleSwap, k0, k1);
+    const double d = (bl - bu) * (fl - fu);
+    return (d < 0.0 ? d : 0.0) > log(u53(w.x, w.y));  // (a NaN d exchanges, as a NaN d accepts)
+}
+// the lower rung of the pair rung `rung` belongs to at exchange event j (odd j: (0,1), (2,3), ...; even j: (1,2), (3,4), ...),
+// or -1 when the rung sits this event out
+__device__ __forceinline__ int tempered_pair(int rung, int K, int64_t j) {
+    const int kl = (rung & 1) == (int)((j + 1) & 1) ? rung : rung - 1;
+    return kl >= 0 && kl + 1 < K ? kl : -1;
+}
 
 // the initial sample (mcmc/_mcmc.py:93, hmc/_hmc.py:124): the given x0, or uniform(lower, upper) = lower + (upper - lower) * u
 template <int LPR>

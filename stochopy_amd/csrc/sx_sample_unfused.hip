@@ -7,7 +7,10 @@
 // expressions under -ffp-contract=off): given bit-identical objective / gradient values the run is the resident run, bit for
 // bit.  State lives in sx_sample_args' per-chain arrays, which the resident kernels round-trip from launch to launch too.
 //
-// One geometry for all five kernels: one row group of lanes_per_row(n) lanes per chain, lane l owns elements l, l + LPR, ...;
+// Parallel tempering (sx_sample_temper.hip) around such an objective: propose kernel -> caller's objective -> decide_tempered
+// kernel -> on an exchange event the swap kernel (one row group per pair of neighbouring rungs, the states in device memory).
+//
+// One geometry for all these kernels: one row group of lanes_per_row(n) lanes per chain, lane l owns elements l, l + LPR, ...;
 // padding row groups shadow the last chain for loads and store nothing; no LDS, no barrier, no atomics.  Philox draws only.
 //
 // Reference code replaced (paths relative to the reference checkout):
@@ -17,6 +20,7 @@
 //   stochopy/sample/hmc/_hmc.py:143-155          leap-frog steps
 //   stochopy/sample/hmc/_hmc.py:157-172          decision and bookkeeping
 //   stochopy/sample/hmc/_hmc.py:217-233          numerical_gradient (in-place perturb / restore)
+#include "sx_enqueue.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
 #include "sx_sample.hpp"
@@ -211,6 +215,100 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
     }
 }
 
+// Parallel tempering (sx_sample_temper.hip) around a caller's objective: the decision of replica c = ladder * K + rung with
+// d = (fcur - fprop) * beta[rung].  record = 0: row `it` of xall / funall is left to sample_swap_kernel (an exchange of
+// rungs (0, 1) follows); else the cold rungs write it at their LADDER's index.  mcmc only.
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_tempered_kernel(const sx_sample_args a, int64_t it,
+                                                                                          const double *__restrict__ prop,
+                                                                                          const double *__restrict__ fprop,
+                                                                                          const double *__restrict__ beta, int K,
+                                                                                          int record) {
+    const RowIds<LPR> id(a.C);
+    const int n = a.n, l = id.l;
+    const int64_t c = id.rowc;
+    const int rung = (int)(c % K);
+    const double *U = prop + c * n;
+    double *X = a.cur + c * n;
+    const double fU = fprop[c];
+    ChainState st;
+    bool accept = false, xbest_changed = false;
+    if (it == 0) {
+        st.start(fU);
+        accept = true;  // (cur = the initial point)
+        xbest_changed = true;
+    } else {
+        st.load(a, c);
+        const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
+        if (feasible) {
+            st.nfeas += 1;
+            const double logu = philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
+            const double d = (st.fcur - fU) * beta[rung];
+            accept = (d < 0.0 ? d : 0.0) > logu;
+        }
+        if (accept) {
+            bool arg_best;
+            st.accept(fU, it, xbest_changed, arg_best);
+        }
+    }
+    if (!id.active) return;
+    const int64_t ladder = c / K;
+    double *all = (a.xall != nullptr && record && rung == 0) ? a.xall + (ladder * a.maxiter + it) * n : nullptr;
+    for (int e = l; e < n; e += LPR) {
+        const double v = accept ? U[e] : X[e];
+        if (accept) X[e] = v;
+        if (all != nullptr) st_stream(all + e, v);
+        if (xbest_changed) a.xbest[c * n + e] = v;
+    }
+    if (l == 0) {
+        if (all != nullptr) st_stream(a.funall + ladder * a.maxiter + it, st.fcur);
+        st.store(a, c);
+    }
+}
+
+// Exchange event j after sample `it`: one row group per PAIR (pairs = ladders * pairs_per_ladder; the lower rungs are
+// first, first + 2, ...), the states in device memory.  The pair of rungs (0, 1) writes row `it` of xall / funall.
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_swap_kernel(const sx_sample_args a, int64_t it,
+                                                                               const double *__restrict__ beta, int K,
+                                                                               int first, int pairs_per_ladder, int64_t pairs,
+                                                                               int64_t *__restrict__ nswap) {
+    const RowIds<LPR> id(pairs);
+    if (!id.active) return;
+    const int n = a.n, l = id.l;
+    const int64_t ladder = id.row / pairs_per_ladder;
+    const int kl = first + 2 * (int)(id.row - ladder * pairs_per_ladder);
+    const int64_t ql = ladder * K + kl, qu = ql + 1;
+    const double fl = a.fcur[ql], fu = a.fcur[qu];
+    const bool swap = tempered_swap(fl, fu, beta[kl], beta[kl + 1], (uint32_t)ql, (uint32_t)it, a.key0, a.key1);
+    double *Xl = a.cur + ql * n, *Xu = a.cur + qu * n;
+    bool best_l = false, best_u = false;
+    if (swap) {
+        ChainState sl, su;
+        sl.load(a, ql);
+        su.load(a, qu);
+        sl.arrive(fu, it, best_l);
+        su.arrive(fl, it, best_u);
+        if (l == 0) {
+            sl.store(a, ql);
+            su.store(a, qu);
+            nswap[ql] += 1;
+        }
+    }
+    double *all = (a.xall != nullptr && kl == 0) ? a.xall + (ladder * a.maxiter + it) * n : nullptr;
+    for (int e = l; e < n; e += LPR) {
+        const double vl = Xl[e], vu = Xu[e];
+        if (swap) {
+            Xl[e] = vu;
+            Xu[e] = vl;
+            if (best_l) a.xbest[ql * n + e] = vu;
+            if (best_u) a.xbest[qu * n + e] = vl;
+        }
+        if (all != nullptr) st_stream(all + e, swap ? vu : vl);
+    }
+    if (all != nullptr && l == 0) st_stream(a.funall + ladder * a.maxiter + it, swap ? fu : fl);
+}
+
 // sx_sample_run's conditions on the arguments these kernels read
 int check_args(const sx_sample_args *a, int64_t it) {
     SX_REQUIRE(a != nullptr, "sx_sample (unfused): null args");
@@ -289,4 +387,34 @@ extern "C" int sx_sample_decide(const sx_sample_args *a, int64_t it, const doubl
                                              (hipStream_t)stream, *a, it, prop, fprop, pmom, k0))
     SX_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int sx_sample_decide_tempered(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
+                                         const double *beta, int K, int record, void *stream) {
+    if (check_args(a, it)) return -1;
+    SX_REQUIRE(prop && fprop && beta, "sx_sample_decide_tempered: null proposal / value / beta array");
+    SX_REQUIRE(a->method == SX_SAMPLE_MCMC, "sx_sample_decide_tempered: mcmc only");
+    SX_REQUIRE(K >= 2 && a->C % K == 0, "sx_sample_decide_tempered: C is ladders x K replicas, K >= 2");
+    const Geometry g = chain_geometry(a->C, a->n);
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_decide_tempered_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
+                                          fprop, beta, K, record))
+    return -1;
+}
+
+extern "C" int sx_sample_swap(const sx_sample_args *a, int64_t it, int64_t j, const double *beta, int K, int64_t *nswap,
+                              void *stream) {
+    if (check_args(a, it)) return -1;
+    SX_REQUIRE(beta && nswap, "sx_sample_swap: null beta / nswap array");
+    SX_REQUIRE(a->method == SX_SAMPLE_MCMC, "sx_sample_swap: mcmc only");
+    SX_REQUIRE(K >= 2 && a->C % K == 0 && it >= 1 && j >= 1, "sx_sample_swap: C is ladders x K replicas, K >= 2; it, j >= 1");
+    const int first = (int)((j + 1) & 1);
+    const int pairs_per_ladder = (K - first) / 2;
+    if (pairs_per_ladder == 0) return 0;  // (K = 2 at an even event: nobody has a partner)
+    const int64_t pairs = (a->C / K) * pairs_per_ladder;
+    const Geometry g = chain_geometry(pairs, a->n);
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_swap_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0, *a, it, beta, K, first,
+                                          pairs_per_ladder, pairs, nswap))
+    return -1;
 }

@@ -66,6 +66,9 @@ class Setup:
     external = None  # a factory.batched objective: optimize._common.External (the chain kernels then run unfused)
     gradient = None  # hmc with such an objective: Gradient / AutogradGradient, or None for finite differences
 
+    temperatures = None  # parallel tempering (mcmc, _temper.py): the ladder as float64 (K,), and
+    swap_every = None    # the samples between two exchange events
+
     def __init__(self, fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                  backend, nleap=None):
         if not hasattr(fun, "__call__"):

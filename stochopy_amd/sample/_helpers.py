@@ -12,7 +12,8 @@ _sampler_map = {}
 
 class SampleResult(OptimizeResult):
     """Sampling result: keys x, fun, nit, accept_ratio (+ nfev for hmc, xall / funall with ``return_all``, and
-    accept_ratios with more than one chain)."""
+    accept_ratios with more than one chain; with ``temperatures``: accept_ratios per ladder and rung, temperatures and
+    swap_ratios)."""
 
 
 def register(name, sample):
@@ -39,6 +40,11 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
     - ``rng``: ``"numpy-legacy"`` (default) replays the reference's own global MT19937 stream and needs
       ``chains == 1``; ``"philox"`` makes every draw inside the kernel and serves any ``chains``.
     - ``backend="hip"``: accepted, the only backend.
+    - ``temperatures`` / ``swap_every`` (``method="mcmc"``, ``rng="philox"``): parallel tempering.  ``temperatures`` is a
+      ladder ``1 = T_0 < T_1 < ... < T_{K-1}`` and ``chains = C`` the number of ladders of K replicas; neighbouring rungs
+      exchange their states every ``swap_every`` samples (default 1).  The result holds the cold rungs (``xall``,
+      ``funall``, ``x``, ``fun``, ``accept_ratio``), ``accept_ratios (C, K)``, ``temperatures (K,)`` and
+      ``swap_ratios (C, K-1)``; the callback's ``xk`` is the ``(C, ndim)`` cold states.  See ``sample.mcmc``.
 
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """

@@ -24,6 +24,8 @@ def sample(
     chains=1,
     rng="numpy-legacy",
     backend="hip",
+    temperatures=None,
+    swap_every=None,
 ):
     """Sample the variable space with Hamiltonian Monte-Carlo (``hmc/_hmc.py:13-200``), ``chains`` independent
     chains in one kernel.
@@ -48,7 +50,11 @@ def sample(
     - ``constraints="Reject"``: the reference's feasibility helper returns ``None`` for it, so every proposal is
       rejected.  Here a trajectory that ends outside ``[lower, upper]`` is rejected, without an acceptance draw.  The
       draw sequence then depends on the data, so it needs ``rng="philox"``.
+    - ``temperatures`` / ``swap_every`` (parallel tempering, see ``sample.mcmc``) are refused: tempering the potential
+      and its gradient is not built.
     """
+    if temperatures is not None or swap_every is not None:
+        raise ValueError('temperatures / swap_every (parallel tempering) are served by method="mcmc" only')
     run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                         backend, nleap=nleap)
     external = run.external is not None

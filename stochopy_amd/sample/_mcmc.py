@@ -21,6 +21,8 @@ def sample(
     chains=1,
     rng="numpy-legacy",
     backend="hip",
+    temperatures=None,
+    swap_every=None,
 ):
     """Sample the variable space with the Metropolis-Hastings algorithm (``mcmc/_mcmc.py:13-161``), ``chains``
     independent chains in one kernel.
@@ -39,7 +41,35 @@ def sample(
       an acceptance draw.  The draw sequence then depends on the data, so it needs ``rng="philox"``.
     - a ``k`` that does not divide ``ndim``: the reference raises a broadcasting error on the last block.  Here the
       last block is the shorter one.
+
+    Parallel tempering (no counterpart in the reference; ``rng="philox"``): ``temperatures`` is a ladder
+    ``1 = T_0 < T_1 < ... < T_{K-1}`` and ``chains = C`` the number of LADDERS, each of K replicas that live in one
+    workgroup; ``swap_every`` (integer >= 1, default 1) is the number of samples between two exchange events.  Replica
+    ``q = c K + k`` (rung k of ladder c) samples ``p^(1/T_k)`` -- the rule above with ``d = (fcur - fprop) / T_k``, draws
+    keyed by q -- and after sample ``it >= 1`` with ``it % swap_every == 0`` neighbouring rungs ((0,1), (2,3), ... at odd
+    events ``it // swap_every``, (1,2), (3,4), ... at even ones) exchange their states with probability
+    ``min(1, exp((1/T_k - 1/T_{k+1}) (f_k - f_{k+1})))``.  The result holds the cold rungs (``T = 1``, correct samplers of
+    ``p`` that visit every mode): ``xall (C, maxiter, ndim)`` / ``funall`` (squeezed for ``C = 1``), ``x`` / ``fun`` and
+    ``accept_ratio`` (and ``nreject``) over the cold rungs, with an arriving state compared as an accepted sample is;
+    ``accept_ratios (C, K)``, ``temperatures (K,)`` and ``swap_ratios (C, K-1)``: accepted exchanges of a pair over the
+    events it took part in (0.0 where it had none).  ``x0`` is ``None`` (every replica draws its own point),
+    ``(ndim,)`` (shared) or ``(C, ndim)`` (one point per ladder, shared by its rungs); the callback's ``xk`` is the
+    ``(C, ndim)`` cold states.  K is at most ``sx_sample_tempered_max_rungs(ndim)`` (16 up to ndim 128).  Not served:
+    ``method="hmc"``, exchanging temperatures instead of states, adaptive ladders, the hot rungs' trajectories.
     """
+    if temperatures is not None or swap_every is not None:
+        from . import _temper
+
+        ladder, every = _temper.check_ladder(temperatures, swap_every, rng)
+        run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
+                            backend)
+        if not 0.0 <= perc <= 1.0:
+            raise ValueError()
+        _temper.check_rungs(ladder, run.ndim)
+        run.temperatures, run.swap_every = ladder, every
+        run.method = _lib.SX_SAMPLE_MCMC
+        run.k = max(1, int(perc * run.ndim))
+        return _temper.run(run)
     run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                         backend)
     if not 0.0 <= perc <= 1.0:

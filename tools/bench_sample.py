@@ -14,6 +14,13 @@ CPU side: the reference package when it is importable, else its numpy restatemen
 calls per sample -- with the same settings and ONE chain, on one core.
 
     python tools/bench_sample.py [--rounds 5] [--chains 16384] [--window 0.25] [--no-cpu] [--out FILE]
+
+--tempered: what parallel tempering costs (csrc/sx_sample_temper.hip).  The `mcmc` configuration above (the plain kernel:
+the baseline of the session) takes turns, by the same protocol, with the same --chains replicas as chains / 16 ladders of 16
+rungs (temperatures geomspace(1, 64, 16)), exchanging after every sample (swap_every 1) and after every 10th; samples / s
+counts every replica's samples, `vs_plain` is the ratio of the medians.  No CPU side.
+
+    python tools/bench_sample.py --tempered [--rounds 5] [--out profiles/sample_temper_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -65,19 +72,42 @@ class DeviceRun:
         self.samples = chains * self.m
         self.stored = chains * self.m * (ndim + 1) * 8 if o["return_all"] else 0
 
-    def timed(self, launches=1):
-        """Seconds per launch (a whole run from sample 0), over `launches` launches back to back."""
+    def launch(self):
         from stochopy_amd import _lib
 
+        _lib.check(self.L.sx_sample_run(C.byref(self.a), 0, self.m, self.ctx.stream_ptr), "sx_sample_run")
+
+    def timed(self, launches=1):
+        """Seconds per launch (a whole run from sample 0), over `launches` launches back to back."""
         t = __import__("torch")
         with t.cuda.stream(self.ctx.stream):
             e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(launches):
-                _lib.check(self.L.sx_sample_run(C.byref(self.a), 0, self.m, self.ctx.stream_ptr), "sx_sample_run")
+                self.launch()
             e1.record()
             e1.synchronize()
         return e0.elapsed_time(e1) * 1e-3 / launches
+
+
+class TemperedRun(DeviceRun):
+    """The same replicas as ladders of K rungs, launched as stochopy_amd.sample does with temperatures=..."""
+
+    def __init__(self, ctx, ndim, replicas, K, swap_every, o):
+        from stochopy_amd import _device
+
+        super().__init__(ctx, "mcmc", ndim, replicas, o)
+        t = _device.torch()
+        self.K, self.swap_every = K, swap_every
+        self.beta = ctx.upload(1.0 / np.geomspace(1.0, 64.0, K))
+        self.nswap = ctx.zeros((replicas,), dtype=t.int64)
+
+    def launch(self):
+        from stochopy_amd import _device, _lib
+
+        _lib.check(self.L.sx_sample_tempered_run(C.byref(self.a), _device.ptr(self.beta), self.K, self.swap_every,
+                                                 _device.ptr(self.nswap), 0, self.m, self.ctx.stream_ptr),
+                   "sx_sample_tempered_run")
 
 
 def cpu_rate(method, ndim, o):
@@ -112,11 +142,20 @@ def main():
     ap.add_argument("--window", type=float, default=0.25, help="seconds of back-to-back launches per timed round")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--out")
+    ap.add_argument("--tempered", action="store_true", help="the plain mcmc kernel next to ladders of 16 replicas")
     args = ap.parse_args()
     from stochopy_amd import _device
 
     ctx = _device.Context()
-    runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o)) for tag, method, ndim, o in CONFIGS]
+    if args.tempered:
+        args.no_cpu = True
+        tag, method, ndim, o = CONFIGS[0]
+        runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o))]
+        for every in (1, 10):
+            runs.append((f"tempered K=16 swap_every={every}", method, ndim, dict(o, ladders=args.chains // 16, K=16, swap_every=every),
+                         TemperedRun(ctx, ndim, args.chains // 16 * 16, 16, every, o)))
+    else:
+        runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o)) for tag, method, ndim, o in CONFIGS]
     launches = {}
     for tag, *_, r in runs:
         r.timed()  # warm-up: code object load, first touch of xall
@@ -132,6 +171,9 @@ def main():
                 "seconds_median": float(np.median(ts)), "seconds_min": float(ts.min()), "seconds_max": float(ts.max()),
                 "samples_per_s": r.samples / float(np.median(ts)),
                 "samples_per_s_spread": [r.samples / float(ts.max()), r.samples / float(ts.min())], "rounds": args.rounds, "launches_per_round": launches[tag]}
+        if args.tempered:
+            line.update({k: o[k] for k in ("ladders", "K", "swap_every") if k in o})
+            line["vs_plain"] = float(np.median(times[runs[0][0]])) / float(np.median(ts)) * r.samples / runs[0][4].samples
         if r.stored:
             line["stored_bytes_per_s"] = r.stored / float(np.median(ts))
             line["share_of_hbm_peak"] = line["stored_bytes_per_s"] / HBM_PEAK
