@@ -429,12 +429,13 @@ class PenalizeState:
 # --------------------------------------------------------------------------- #
 # NA  (na/_na.py:131-262 loop, :265-305 mutation)
 # --------------------------------------------------------------------------- #
-def na_walk(models, k, u_row, free):
+def na_walk(models, k, u_row, free, probe=None):
     """One new sample (na/_na.py:275-303): start at model k, then axis by axis draw uniformly inside the Voronoi
     cell of k restricted to the current axis line.  `u_row[j]` is the [0,1) double behind np.random.uniform(low,
     high) (:298).  The cell-distance bookkeeping `d1` is SCALAR arithmetic in the reference: numpy scalars `** 2`,
     i.e. libm pow (not always the correctly rounded square) -- kept as numpy scalars here; `d2` is array arithmetic
-    (`** 2` on arrays is an exact square)."""
+    (`** 2` on arrays is an exact square).  `probe(j, lim, x_j)` (tests): the walls of every free axis j as the walk
+    computed them and the coordinate they are compared with, before the draw."""
     n = models.shape[1]
     centre = models[k]
     x = centre.copy()
@@ -447,6 +448,8 @@ def na_walk(models, k, u_row, free):
             continue
         with np.errstate(divide="ignore", invalid="ignore"):
             lim = 0.5 * (centre[j] + others[:, j] + (d1 - d2) / (centre[j] - others[:, j]))   # :288
+        if probe is not None:
+            probe(j, lim.copy(), float(x[j]))
         below = lim <= x[j]
         low = max(lim[below].max(), 0.0) if below.sum() else 0.0                   # :290-291
         above = lim >= x[j]

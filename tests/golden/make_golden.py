@@ -606,6 +606,74 @@ def na():
     print("wrote na_xall.npz", os.path.getsize(os.path.join(HERE, "na_xall.npz")))
 
 
+# --------------------------------------------------------------------------- #
+# 8b. Neighbourhood Algorithm at the edges of the cell walk (na/_na.py:265-305): a fixed axis first, last, next to
+#     another one; initial populations with duplicate rows and a constant column, or all rows equal (0 / 0 and x / 0
+#     walls); more samples than one workgroup of the device's draw step serves; a single axis.
+# --------------------------------------------------------------------------- #
+NA_EDGE_BOUNDS = (
+    ("fixed_first", [[1.5, 1.5], [-2.0, 3.0], [-1.0, 1.0], [-5.0, 5.0]]),
+    ("fixed_last", [[-2.0, 3.0], [-1.0, 1.0], [-5.0, 5.0], [0.5, 0.5]]),
+    ("fixed_adjacent", [[-2.0, 3.0], [1.0, 1.0], [2.0, 2.0], [-5.0, 5.0]]),
+    ("fixed_leading_pair", [[1.0, 1.0], [2.0, 2.0], [-1.0, 2.0]]),
+)
+
+
+def na_edges_x0():
+    """The two degenerate initial populations (popsize 12, 3 axes in [-5.12, 5.12])."""
+    a = np.random.RandomState(21).uniform(-5.12, 5.12, (12, 3))
+    a[:, 1] = 0.75
+    a[5] = a[7] = a[2]
+    b = np.tile(np.random.RandomState(22).uniform(-5.12, 5.12, 3), (12, 1))
+    return a, b
+
+
+def save_npz_reproducibly(name, arrays):
+    """np.savez_compressed stamps every member with the time of day; these members carry a fixed date, so that the same
+    arrays give the same bytes."""
+    import io
+    import zipfile
+
+    path = os.path.join(HERE, name)
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+    print("wrote", name, os.path.getsize(path), "bytes")
+
+
+def na_edges():
+    out = dict(STAMP)
+    cases = []
+    arrays = {}
+
+    def add(tag, fun, n, opts, bounds=None, x0=None):
+        entry, res, pops = run_ref(fun, n, "na", dict(opts, return_all=True), x0=x0, bounds=bounds, full=True)
+        entry["tag"] = tag
+        arrays[tag + "__xall"] = res.xall
+        arrays[tag + "__funall"] = res.funall
+        cases.append(entry)
+        print(" ", tag, "fun", float(res.fun), "nit", res.nit, "status", res.status)
+
+    for k, (name, bounds) in enumerate(NA_EDGE_BOUNDS):
+        add("na_" + name, ("sphere", "rosenbrock")[k % 2], len(bounds),
+            {"maxiter": 15, "popsize": 12, "seed": 31 + k, "nrperc": 0.5}, bounds=bounds)
+    dup, equal = na_edges_x0()
+    add("na_x0_duplicates_flat_column", "rosenbrock", 3, {"maxiter": 15, "popsize": 12, "seed": 41, "nrperc": 0.5}, x0=dup)
+    add("na_x0_all_equal", "sphere", 3, {"maxiter": 15, "popsize": 12, "seed": 42, "nrperc": 0.5}, x0=equal)
+    add("na_rosen_n3_p70", "rosenbrock", 3, {"maxiter": 12, "popsize": 70, "seed": 43, "nrperc": 0.3})
+    add("na_sphere_n1_p12", "sphere", 1, {"maxiter": 10, "popsize": 12, "seed": 44, "nrperc": 0.5})
+    out["cases"] = cases
+    total = sum(a.size for a in arrays.values())
+    assert total < 10000, total
+    dump("na_edges.json", out)
+    save_npz_reproducibly("na_edges_xall.npz", arrays)
+
+
 
 # --------------------------------------------------------------------------- #
 # 8. non-finite objective values: np.argmin takes the first NaN (any sign bit), np.argsort puts NaN last, np.max
@@ -714,11 +782,13 @@ def nonfinite():
     print("wrote nonfinite_xall.npz", os.path.getsize(os.path.join(HERE, "nonfinite_xall.npz")), "bytes")
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["rng", "factory", "suite", "configs", "penalize", "vdcma", "immediate", "na", "nonfinite"]
+    which = sys.argv[1:] or ["rng", "factory", "suite", "configs", "penalize", "vdcma", "immediate", "na", "na_edges", "nonfinite"]
     if "nonfinite" in which:
         nonfinite()
     if "na" in which:
         na()
+    if "na_edges" in which:
+        na_edges()
     if "immediate" in which:
         immediate()
     if "vdcma" in which:

@@ -265,11 +265,10 @@ def test_philox_stream_properties():
 NA_CASES = load_golden("na.json")["cases"]
 
 
-@pytest.mark.parametrize("case", NA_CASES, ids=lambda c: c["tag"])
-def test_na_oracle_matches_reference_bit_for_bit(case):
-    """Neighbourhood Algorithm (na/_na.py:131-305): result, per-generation best-f, the full history and the
-    populations handed to the callback equal the reference's, bit for bit -- including the reference's scalar
-    `** 2` (libm pow) in the cell walk, the normalised rows it stores at iteration 1, and fixed axes."""
+NA_EDGE_CASES = load_golden("na_edges.json")["cases"]
+
+
+def _na_oracle_equals_reference(case, npz):
     trace, pops = [], []
     res = oracle.minimize(case["objective"], case_bounds(case), x0=case["x0"], method="na", options=dict(case["options"]),
                           callback=lambda X, r: (trace.append(float(r.fun)), pops.append(np.array(X, copy=True))))
@@ -278,7 +277,7 @@ def test_na_oracle_matches_reference_bit_for_bit(case):
         ref["nit"], ref["nfev"], ref["status"], ref["success"], ref["message"])
     assert np.array_equal(res.x, unhex(ref["x"])) and res.fun == unhex(ref["fun"])
     assert np.array_equal(np.array(trace), unhex(case["fun_trace"]))
-    arrays = np.load(os.path.join(GOLDEN, "na_xall.npz"))
+    arrays = np.load(os.path.join(GOLDEN, npz))
     assert np.array_equal(res.xall, arrays[case["tag"] + "__xall"])
     assert np.array_equal(res.funall, arrays[case["tag"] + "__funall"])
     import hashlib
@@ -286,6 +285,22 @@ def test_na_oracle_matches_reference_bit_for_bit(case):
     assert hashlib.sha256(np.ascontiguousarray(pops[-1]).tobytes()).hexdigest() == case["pop_last_sha"]
     if "xref_from_reference_tests" in case:
         assert np.allclose(case["xref_from_reference_tests"], res.x)
+
+
+@pytest.mark.parametrize("case", NA_CASES, ids=lambda c: c["tag"])
+def test_na_oracle_matches_reference_bit_for_bit(case):
+    """Neighbourhood Algorithm (na/_na.py:131-305): result, per-generation best-f, the full history and the
+    populations handed to the callback equal the reference's, bit for bit -- including the reference's scalar
+    `** 2` (libm pow) in the cell walk, the normalised rows it stores at iteration 1, and fixed axes."""
+    _na_oracle_equals_reference(case, "na_xall.npz")
+
+
+@pytest.mark.parametrize("case", NA_EDGE_CASES, ids=lambda c: c["tag"])
+def test_na_oracle_matches_reference_at_the_walk_edges(case):
+    """The same, where the cell walk is degenerate (tests/golden/make_golden.py na_edges): a fixed axis first, last,
+    next to another one; an initial population with duplicate rows and a constant column, or with all rows equal (walls
+    that are NaN or infinite, axes without any wall); 70 samples a generation; a single axis."""
+    _na_oracle_equals_reference(case, "na_edges_xall.npz")
 
 
 @pytest.mark.parametrize("method", ["de", "pso", "cpso"])
