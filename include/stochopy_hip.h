@@ -732,6 +732,44 @@ int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, co
                      const double *k0, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Per-chain step-size adaptation in a warm-up, and recording with a burn-in and thinning.  No counterpart in the
+ * reference.  sx_sample_args stays what it is; the options travel in a second struct, and the *_adapt entry points take the
+ * arguments of sx_sample_run / _propose / _leap / _decide with it behind `a`.  rng must be SX_RNG_PHILOX.
+ *
+ * Chain c carries a multiplier s_c (1.0 at the start): wherever a sample reads step[e] it reads s_c * step[e], formed first
+ * (mcmc: v + z * (s step[e]); hmc: p - (coef * (s step[e])) * g and q + (s step[e]) * p); with s = 1.0 that is
+ * sx_sample_run's arithmetic bit for bit.  After the decision of sample `it`, 1 <= it <= warmup, with t = (double)it and d the
+ * sample's own d (mcmc fcur - fprop, hmc U0 - U + K0 - K) -- dual averaging (Hoffman & Gelman 2014):
+ *     alpha   = infeasible (reject) ? 0 : d < 0 ? exp(d) : d >= 0 ? 1 : 0       (a NaN d counts as 0 HERE; it still accepts)
+ *     eta     = 1 / (t + 10);   hbar = (1 - eta) * hbar + eta * (target - alpha)
+ *     logs    = log(10) - (sqrt(t) / 0.05) * hbar
+ *     w       = 1 / (sqrt(t) * sqrt(sqrt(t)))
+ *     logsbar = w * logs + (1 - w) * logsbar
+ *     s       = it < warmup ? exp(logs) : exp(logsbar)                          (frozen from sample warmup + 1 on)
+ * and at it == warmup nacc is copied to nacc_warm.  The accept / reject decision is not changed.
+ * Recording: sample `it` goes to row (it - rec_start) / rec_every of xall (C, rec_rows, n) / funall (C, rec_rows) when
+ * it >= rec_start and (it - rec_start) % rec_every == 0; rec_rows = ceil((maxiter - rec_start) / rec_every).
+ * With warmup = 0, rec_start = 0, rec_every = 1 every output is sx_sample_run's, bit for bit.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_sample_adapt {
+    double *scale, *hbar, *logsbar; /* DEVICE (C): s_c and the two averages; written by the launch that generates sample 0 */
+    int64_t *nacc_warm;             /* DEVICE (C): nacc after sample `warmup`.  All four may be NULL when warmup == 0 */
+    int64_t warmup;                 /* 0 <= warmup <= maxiter - 1 */
+    int64_t rec_start, rec_every;   /* 0 <= rec_start <= maxiter - 1, 1 <= rec_every < 2^31 */
+    int64_t rec_rows;               /* rows of xall / funall per chain */
+    double target;                  /* the acceptance the rule steers to, in (0, 1) (read when warmup > 0) */
+} sx_sample_adapt;
+/* sizeof(sx_sample_adapt) as the library was built (sx_struct_size is not extended) */
+int sx_sample_adapt_bytes(void);
+int sx_sample_run_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it0, int64_t steps, void *stream);
+int sx_sample_propose_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop, double *pmom,
+                            double *k0, void *stream);
+int sx_sample_leap_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q, double *pmom,
+                         const double *G, void *stream);
+int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
+                           const double *fprop, const double *pmom, const double *k0, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Parallel tempering (replica exchange) for the Metropolis-Hastings chains (csrc/sx_sample_temper.hip): C ladders of K
  * device-resident replicas.  No counterpart in the reference.  Replica q = c K + k is rung k of ladder c and samples
  * p^(beta[k]), beta[k] = 1 / T_k with 1 = T_0 < T_1 < ...: sx_sample_run's mcmc sample with d = (fcur - fprop) * beta[k]

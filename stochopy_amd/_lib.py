@@ -128,6 +128,16 @@ class SxSampleArgs(C.Structure):
     ]
 
 
+class SxSampleAdapt(C.Structure):
+    """sx_sample_adapt: per-chain step-size adaptation in a warm-up, burn-in and thinning (its size is checked against
+    sx_sample_adapt_bytes; sx_struct_size is not extended)."""
+    _fields_ = [
+        ("scale", vp), ("hbar", vp), ("logsbar", vp), ("nacc_warm", vp),
+        ("warmup", i64), ("rec_start", i64), ("rec_every", i64), ("rec_rows", i64),
+        ("target", f64),
+    ]
+
+
 class SxDeRunsArgs(C.Structure):
     _fields_ = [
         ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("xs", vp), ("funs", vp), ("nits", vp), ("statuses", vp),
@@ -264,6 +274,11 @@ PROTOTYPES = {
     "sx_sample_fd_rows": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
     "sx_sample_fd_gradient": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, C.c_int, vp, vp]),
     "sx_sample_decide": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, vp, vp]),
+    "sx_sample_adapt_bytes": (C.c_int, []),
+    "sx_sample_run_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), i64, i64, vp]),
+    "sx_sample_propose_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), i64, vp, vp, vp, vp]),
+    "sx_sample_leap_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), f64, C.c_int, vp, vp, vp, vp]),
+    "sx_sample_decide_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), i64, vp, vp, vp, vp, vp]),
     "sx_sample_tempered_run": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, i64, vp, i64, i64, vp]),
     "sx_sample_tempered_max_rungs": (C.c_int, [C.c_int]),
     "sx_sample_decide_tempered": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -346,6 +361,9 @@ def lib():
     if handle.sx_vd_runs_args_bytes() != C.sizeof(SxVdRunsArgs):
         raise HipLibraryError(f"{LIB_PATH}: sx_vd_runs_args is {handle.sx_vd_runs_args_bytes()} bytes, its mirror "
                               f"{C.sizeof(SxVdRunsArgs)}; rebuild the library")
+    if handle.sx_sample_adapt_bytes() != C.sizeof(SxSampleAdapt):
+        raise HipLibraryError(f"{LIB_PATH}: sx_sample_adapt is {handle.sx_sample_adapt_bytes()} bytes, its mirror "
+                              f"{C.sizeof(SxSampleAdapt)}; rebuild the library")
     _lib = handle
     return _lib
 

@@ -47,9 +47,11 @@ __device__ __forceinline__ void grad_apply(const double *Q, int n, int l, F &&f)
 // (the last block is the shorter one when k does not divide n): randn(kb) * step, then rand() for the decision.
 // LDS per chain: X[n] (current sample) | U[gen_row_stride(n)] (proposal, in the objective's layout).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int FUN, int LPR>
+// ADAPT (sx_sample_adapt): the chain's multiplier of a.step adapts during the warm-up and xall / funall take the recorded
+// rows only; without it `ad` is an empty struct that is never read, and the kernel is the plain one.
+template <int FUN, int LPR, bool ADAPT>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx_sample_args a, const PlanArg plan,
-                                                                        int64_t it0, int64_t it1) {
+                                                                        int64_t it0, int64_t it1, const AdaptArg<ADAPT> ad) {
     extern __shared__ double lds[];
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l, k = a.k;
@@ -59,10 +61,20 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
     const bool host = a.rng == SX_RNG_HOST;
     const int nblocks = (n + k - 1) / k;
     ChainState st;
+    AdaptState as;
     if (it0 > 0) {
         st.load(a, c);
+        if constexpr (ADAPT) as.load(ad, c);
         for (int e = l; e < n; e += LPR) X[e] = a.cur[c * n + e];
     }
+    const auto step = [&](int e) {
+        if constexpr (ADAPT)
+            return as.s * a.step[e];
+        else
+            return a.step[e];
+    };
+    int64_t rec_next = 0, rec_row = 0;  // (ADAPT) the next recorded sample and its row: no division per sample
+    if constexpr (ADAPT) adapt_first_record(ad, it0, rec_next, rec_row);
     for (int64_t it = it0; it < it1; ++it) {
         int j0 = 0, j1 = 0;
         if (it == 0) {
@@ -81,10 +93,10 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
                     philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
                 }
                 const double v0 = X[e0];
-                U[e0] = in0 ? v0 + z0 * a.step[e0] : v0;
+                U[e0] = in0 ? v0 + z0 * step(e0) : v0;
                 if (e1 < n) {
                     const double v1 = X[e1];
-                    U[e1] = in1 ? v1 + z1 * a.step[e1] : v1;
+                    U[e1] = in1 ? v1 + z1 * step(e1) : v1;
                 }
             }
         }
@@ -93,25 +105,35 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
         bool xbest_changed = false;
         if (it == 0) {
             st.start(fU);
+            if constexpr (ADAPT) as.start();
             for (int e = l; e < n; e += LPR) X[e] = U[e];
             xbest_changed = true;  // x = xall[0] while nothing was accepted
         } else {
             const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
             bool accept = false;
+            double dstat = 0.0;
             if (feasible) {
                 st.nfeas += 1;
                 const double logu = host ? a.logu[it] : philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
                 const double d = st.fcur - fU;
                 accept = (d < 0.0 ? d : 0.0) > logu;  // Python's min(0.0, d): a NaN d gives 0.0
+                dstat = d;
             }
             if (accept) {
                 bool arg_best;
                 st.accept(fU, it, xbest_changed, arg_best);
                 for (int e = l + ((j0 - l + LPR - 1) / LPR) * LPR; e < j1; e += LPR) X[e] = U[e];
             }
+            if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, dstat, st.nacc);
         }
         if (id.active) {
-            if (a.xall != nullptr) {
+            if constexpr (ADAPT) {
+                if (a.xall != nullptr && it == rec_next) {
+                    double *dst = a.xall + (c * ad.rec_rows + rec_row) * n;
+                    for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
+                    if (l == 0) st_stream(a.funall + c * ad.rec_rows + rec_row, st.fcur);
+                }
+            } else if (a.xall != nullptr) {
                 double *dst = a.xall + (c * a.maxiter + it) * n;
                 for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
                 if (l == 0) st_stream(a.funall + c * a.maxiter + it, st.fcur);
@@ -119,10 +141,15 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
             if (xbest_changed)
                 for (int e = l; e < n; e += LPR) a.xbest[c * n + e] = X[e];
         }
+        if constexpr (ADAPT)
+            if (it == rec_next) rec_next += ad.rec_every, rec_row += 1;
     }
     if (id.active) {
         for (int e = l; e < n; e += LPR) a.cur[c * n + e] = X[e];
-        if (l == 0) st.store(a, c);
+        if (l == 0) {
+            st.store(a, c);
+            if constexpr (ADAPT) as.store(ad, c);
+        }
     }
 }
 
@@ -135,9 +162,9 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void mcmc_kernel(const sx
 // LDS per chain: X[n] current sample | Q[S] position | P[n] momentum | finite differences: X1[S] | X2[S]
 // (S = gen_row_stride(n): the objective's layout).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int FUN, int LPR, bool ANALYTIC>
+template <int FUN, int LPR, bool ANALYTIC, bool ADAPT>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_sample_args a, const PlanArg plan,
-                                                                       int64_t it0, int64_t it1) {
+                                                                       int64_t it0, int64_t it1, const AdaptArg<ADAPT> ad) {
     extern __shared__ double lds[];
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l, S = gen_row_stride(n);
@@ -149,10 +176,20 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
     const bool host = a.rng == SX_RNG_HOST;
     const double h = a.fd_step;
     ChainState st;
+    AdaptState as;
     if (it0 > 0) {
         st.load(a, c);
+        if constexpr (ADAPT) as.load(ad, c);
         for (int e = l; e < n; e += LPR) X[e] = a.cur[c * n + e];
     }
+    const auto step = [&](int e) {
+        if constexpr (ADAPT)
+            return as.s * a.step[e];
+        else
+            return a.step[e];
+    };
+    int64_t rec_next = 0, rec_row = 0;  // (ADAPT) the next recorded sample and its row: no division per sample
+    if constexpr (ADAPT) adapt_first_record(ad, it0, rec_next, rec_row);
     for (int64_t it = it0; it < it1; ++it) {
         double K0 = 0.0, K = 0.0;
         if (it == 0) {
@@ -183,7 +220,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
                 const double coef = (g == 0 || g == a.nleap + 1) ? 0.5 : 1.0;
                 lds_wave_fence();  // Q complete
                 if constexpr (ANALYTIC) {
-                    grad_apply<FUN, LPR>(Q, n, l, [&](int e, double gv) { Pm[e] = Pm[e] - (coef * a.step[e]) * gv; });
+                    grad_apply<FUN, LPR>(Q, n, l, [&](int e, double gv) { Pm[e] = Pm[e] - (coef * step(e)) * gv; });
                 } else {
                     for (int e = l; e < n; e += LPR) X1[e] = X2[e] = Q[e];
 #pragma unroll 1
@@ -198,14 +235,14 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
                         for (int w = 0; w < 2; ++w) fv[w] = row_objective<FUN, LPR, 0, 0>(w ? X1 : X2, n, plan, l);
                         const double gv = (0.5 * (fv[0] - fv[1])) / h;
                         if (own) {
-                            Pm[i] = Pm[i] - (coef * a.step[i]) * gv;
+                            Pm[i] = Pm[i] - (coef * step(i)) * gv;
                             X1[i] = X1[i] + h;
                             X2[i] = X2[i] - h;
                         }
                     }
                 }
                 if (g <= a.nleap)
-                    for (int e = l; e < n; e += LPR) Q[e] = Q[e] + a.step[e] * Pm[e];
+                    for (int e = l; e < n; e += LPR) Q[e] = Q[e] + step(e) * Pm[e];
             }
             s = 0.0;
             for (int e = l; e < n; e += LPR) s += Pm[e] * Pm[e];
@@ -215,25 +252,35 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
         bool xbest_changed = false;
         if (it == 0) {
             st.start(fQ);
+            if constexpr (ADAPT) as.start();
             for (int e = l; e < n; e += LPR) X[e] = Q[e];
             xbest_changed = true;
         } else {
             const bool feasible = !a.reject || row_in_box<LPR>(a, Q, n, l);
             bool accept = false;
+            double dstat = 0.0;
             if (feasible) {
                 st.nfeas += 1;
                 const double logu = host ? a.logu[it] : philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
                 const double d = ((st.fcur - fQ) + K0) - K;
                 accept = (d < 0.0 ? d : 0.0) > logu;
+                dstat = d;
             }
             if (accept) {
                 bool acc_best;
                 st.accept(fQ, it, acc_best, xbest_changed);
                 for (int e = l; e < n; e += LPR) X[e] = Q[e];
             }
+            if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, dstat, st.nacc);
         }
         if (id.active) {
-            if (a.xall != nullptr) {
+            if constexpr (ADAPT) {
+                if (a.xall != nullptr && it == rec_next) {
+                    double *dst = a.xall + (c * ad.rec_rows + rec_row) * n;
+                    for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
+                    if (l == 0) st_stream(a.funall + c * ad.rec_rows + rec_row, st.fcur);
+                }
+            } else if (a.xall != nullptr) {
                 double *dst = a.xall + (c * a.maxiter + it) * n;
                 for (int e = l; e < n; e += LPR) st_stream(dst + e, X[e]);
                 if (l == 0) st_stream(a.funall + c * a.maxiter + it, st.fcur);
@@ -241,10 +288,15 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void hmc_kernel(const sx_
             if (xbest_changed)
                 for (int e = l; e < n; e += LPR) a.xbest[c * n + e] = X[e];
         }
+        if constexpr (ADAPT)
+            if (it == rec_next) rec_next += ad.rec_every, rec_row += 1;
     }
     if (id.active) {
         for (int e = l; e < n; e += LPR) a.cur[c * n + e] = X[e];
-        if (l == 0) st.store(a, c);
+        if (l == 0) {
+            st.store(a, c);
+            if constexpr (ADAPT) as.store(ad, c);
+        }
     }
 }
 
@@ -264,23 +316,26 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void gradient_kernel(cons
     });
 }
 
-using sample_kernel_t = void (*)(const sx_sample_args, const PlanArg, int64_t, int64_t);
+template <bool ADAPT>
+using sample_kernel_t = void (*)(const sx_sample_args, const PlanArg, int64_t, int64_t, const AdaptArg<ADAPT>);
 using gradient_kernel_t = void (*)(const double *, int64_t, int, double *);
 
-template <int FUN, int LPR>
-sample_kernel_t pick_variant(int variant) {
-    return variant == kMcmc ? mcmc_kernel<FUN, LPR> : variant == kHmcFd ? hmc_kernel<FUN, LPR, false> : hmc_kernel<FUN, LPR, true>;
+template <int FUN, int LPR, bool ADAPT>
+sample_kernel_t<ADAPT> pick_variant(int variant) {
+    return variant == kMcmc    ? mcmc_kernel<FUN, LPR, ADAPT>
+           : variant == kHmcFd ? hmc_kernel<FUN, LPR, false, ADAPT>
+                               : hmc_kernel<FUN, LPR, true, ADAPT>;
 }
-template <int LPR>
-sample_kernel_t pick_sample(int fun_id, int variant) {
+template <int LPR, bool ADAPT>
+sample_kernel_t<ADAPT> pick_sample(int fun_id, int variant) {
     switch (fun_id) {
-        case SX_FUN_ACKLEY: return pick_variant<SX_FUN_ACKLEY, LPR>(variant);
-        case SX_FUN_GRIEWANK: return pick_variant<SX_FUN_GRIEWANK, LPR>(variant);
-        case SX_FUN_QUARTIC: return pick_variant<SX_FUN_QUARTIC, LPR>(variant);
-        case SX_FUN_RASTRIGIN: return pick_variant<SX_FUN_RASTRIGIN, LPR>(variant);
-        case SX_FUN_ROSENBROCK: return pick_variant<SX_FUN_ROSENBROCK, LPR>(variant);
-        case SX_FUN_SPHERE: return pick_variant<SX_FUN_SPHERE, LPR>(variant);
-        default: return pick_variant<SX_FUN_STYBLINSKI_TANG, LPR>(variant);
+        case SX_FUN_ACKLEY: return pick_variant<SX_FUN_ACKLEY, LPR, ADAPT>(variant);
+        case SX_FUN_GRIEWANK: return pick_variant<SX_FUN_GRIEWANK, LPR, ADAPT>(variant);
+        case SX_FUN_QUARTIC: return pick_variant<SX_FUN_QUARTIC, LPR, ADAPT>(variant);
+        case SX_FUN_RASTRIGIN: return pick_variant<SX_FUN_RASTRIGIN, LPR, ADAPT>(variant);
+        case SX_FUN_ROSENBROCK: return pick_variant<SX_FUN_ROSENBROCK, LPR, ADAPT>(variant);
+        case SX_FUN_SPHERE: return pick_variant<SX_FUN_SPHERE, LPR, ADAPT>(variant);
+        default: return pick_variant<SX_FUN_STYBLINSKI_TANG, LPR, ADAPT>(variant);
     }
 }
 template <int LPR>
@@ -308,7 +363,8 @@ extern "C" int sx_sample_chains_per_workgroup(int method, int jac, int n) {
     return sample_waves(variant_of(method, jac), n) * (kWave / lanes_per_row(n));
 }
 
-extern "C" int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *stream) {
+namespace {
+int check_run_args(const sx_sample_args *a, int64_t it0, int64_t steps) {
     SX_REQUIRE(a != nullptr, "sx_sample_run: null args");
     SX_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
                "sx_sample_run: null state pointer");
@@ -328,19 +384,48 @@ extern "C" int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps
         SX_REQUIRE(a->k >= 1 && a->k <= a->n, "sx_sample_run: block length outside [1, n]");
     else
         SX_REQUIRE(a->nleap >= 1 && (a->jac == SX_JAC_ANALYTIC || a->fd_step != 0.0), "sx_sample_run: bad nleap / step");
+    return 0;
+}
+}  // namespace
+
+extern "C" int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *stream) {
+    if (check_run_args(a, it0, steps)) return -1;
     if (steps == 0) return 0;
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     const int variant = variant_of(a->method, a->jac);
-    sample_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = pick_sample<LPR>(a->fun_id, variant))
+    sample_kernel_t<false> kern = nullptr;
+    SX_DISPATCH_LPR(a->n, kern = (pick_sample<LPR, false>(a->fun_id, variant)))
     const int waves = sample_waves(variant, a->n);
     const int chains = waves * (kWave / lanes_per_row(a->n));
     const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
     if (lds > 64 * 1024)  // one wave's chains need more than the default limit (gfx950: 160 KiB per workgroup)
         SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, (hipStream_t)stream,
-                       *a, plan, it0, it0 + steps);
+                       *a, plan, it0, it0 + steps, NoAdapt{});
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sx_sample_adapt_bytes(void) { return (int)sizeof(sx_sample_adapt); }
+
+// sx_sample_run with the adapting / thinning kernels (the same geometry and LDS)
+extern "C" int sx_sample_run_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it0, int64_t steps,
+                                   void *stream) {
+    if (check_run_args(a, it0, steps) || check_adapt(a, ad)) return -1;
+    if (steps == 0) return 0;
+    PlanArg plan;
+    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
+    const int variant = variant_of(a->method, a->jac);
+    sample_kernel_t<true> kern = nullptr;
+    SX_DISPATCH_LPR(a->n, kern = (pick_sample<LPR, true>(a->fun_id, variant)))
+    const int waves = sample_waves(variant, a->n);
+    const int chains = waves * (kWave / lanes_per_row(a->n));
+    const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
+    if (lds > 64 * 1024)
+        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, (hipStream_t)stream,
+                       *a, plan, it0, it0 + steps, *ad);
     SX_LAUNCH_CHECK();
     return 0;
 }

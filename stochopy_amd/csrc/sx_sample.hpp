@@ -3,6 +3,9 @@
 // (and gradient) values the two paths give the same run, bit for bit.  The tempered ladders (sx_sample_temper.hip, and their
 // decide / swap kernels in sx_sample_unfused.hip) share them too, with the exchange rule at the end of this file.
 #pragma once
+#include <type_traits>
+
+#include "sx_host.hpp"
 #include "sx_rowops.hpp"
 
 namespace sx {
@@ -92,6 +95,83 @@ struct ChainState {
         if (best_before(f, fmin)) fmin = f, imin = it;
     }
 };
+
+// Step-size adaptation in a warm-up (sx_sample_adapt; dual averaging, Hoffman & Gelman 2014, on a per-chain MULTIPLIER of
+// a.step): the constants of the rule.  They are fixed, not options.
+constexpr double kAdaptT0 = 10.0;                  // eta = 1 / (t + t0): the early samples count less
+constexpr double kAdaptGamma = 0.05;               // logs = mu - (sqrt(t) / gamma) * hbar
+constexpr double kAdaptLogMu = 2.302585092994046;  // mu = log(10): the multiplier is drawn towards 10 x its start, 1.0
+// (the averaging weight t^(-kappa), kappa = 3/4, is formed as 1 / (sqrt(t) * sqrt(sqrt(t))): no pow)
+
+// the adaptation scalars of one chain (identical in every lane of its row group), carried like ChainState.  With warmup == 0
+// nothing adapts and the arrays may be NULL: s stays 1.0 and 1.0 * step is step, bit for bit.
+struct AdaptState {
+    double s, hbar, logsbar;  // the multiplier in use, the averaged (target - alpha), the averaged log multiplier
+    int64_t nacc_warm;        // nacc after sample `warmup`
+    __device__ __forceinline__ void load(const sx_sample_adapt &ad, int64_t c) {
+        start();
+        if (ad.warmup > 0) s = ad.scale[c], hbar = ad.hbar[c], logsbar = ad.logsbar[c], nacc_warm = ad.nacc_warm[c];
+    }
+    __device__ __forceinline__ void store(const sx_sample_adapt &ad, int64_t c) const {
+        if (ad.warmup > 0) ad.scale[c] = s, ad.hbar[c] = hbar, ad.logsbar[c] = logsbar, ad.nacc_warm[c] = nacc_warm;
+    }
+    __device__ __forceinline__ void start() { s = 1.0, hbar = 0.0, logsbar = 0.0, nacc_warm = 0; }
+};
+
+// the adapting kernels' last argument; the plain kernels take an empty struct in its place, which they never read
+struct NoAdapt {};
+template <bool ADAPT>
+using AdaptArg = std::conditional_t<ADAPT, sx_sample_adapt, NoAdapt>;
+
+// After the decision of sample `it` >= 1 (d its own log acceptance ratio; feasible: it passed the box test; nacc the count
+// with this sample): one step of the rule for it <= warmup, the averaged multiplier frozen at it == warmup.  The decision
+// itself accepts a NaN d; HERE a NaN d counts as alpha = 0, so that a diverged trajectory shrinks the step.
+__device__ __forceinline__ void adapt_update(AdaptState &ad, int64_t warmup, double target, int64_t it, bool feasible, double d,
+                                             int64_t nacc) {
+    if (it > warmup) return;
+    const double t = (double)it;
+    const double alpha = !feasible ? 0.0 : d < 0.0 ? exp(d) : d >= 0.0 ? 1.0 : 0.0;
+    const double eta = 1.0 / (t + kAdaptT0);
+    ad.hbar = (1.0 - eta) * ad.hbar + eta * (target - alpha);
+    const double rt = sqrt(t);
+    const double logs = kAdaptLogMu - (rt / kAdaptGamma) * ad.hbar;
+    const double w = 1.0 / (rt * sqrt(rt));
+    ad.logsbar = w * logs + (1.0 - w) * ad.logsbar;
+    ad.s = it < warmup ? exp(logs) : exp(ad.logsbar);
+    if (it == warmup) ad.nacc_warm = nacc;
+}
+// thinning: is sample `it` recorded, and in which row of xall / funall (rec_every < 2^31, it < maxiter < 2^31)
+__device__ __forceinline__ bool adapt_record(const sx_sample_adapt &ad, int64_t it, int64_t &row) {
+    if (it < ad.rec_start) return false;
+    const uint32_t off = (uint32_t)(it - ad.rec_start), every = (uint32_t)ad.rec_every;
+    row = (int64_t)(off / every);
+    return off % every == 0u;
+}
+
+// what every *_adapt entry point requires of `ad` next to its own checks of `a` (which come first: a is not null here)
+inline int check_adapt(const sx_sample_args *a, const sx_sample_adapt *ad) {
+    SX_REQUIRE(ad != nullptr, "sx_sample (adapt): null adaptation args");
+    SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_sample (adapt): the draws are made in the kernels (SX_RNG_PHILOX)");
+    SX_REQUIRE(ad->warmup >= 0 && ad->warmup <= a->maxiter - 1, "sx_sample (adapt): warmup outside [0, maxiter - 1]");
+    SX_REQUIRE(ad->rec_start >= 0 && ad->rec_start <= a->maxiter - 1, "sx_sample (adapt): rec_start outside [0, maxiter - 1]");
+    SX_REQUIRE(ad->rec_every >= 1 && ad->rec_every < (int64_t)1 << 31, "sx_sample (adapt): rec_every outside [1, 2^31)");
+    SX_REQUIRE(ad->rec_rows == (a->maxiter - ad->rec_start + ad->rec_every - 1) / ad->rec_every,
+               "sx_sample (adapt): rec_rows is not ceil((maxiter - rec_start) / rec_every)");
+    if (ad->warmup > 0) {
+        SX_REQUIRE(ad->scale && ad->hbar && ad->logsbar && ad->nacc_warm, "sx_sample (adapt): null adaptation state pointer");
+        SX_REQUIRE(ad->target > 0.0 && ad->target < 1.0, "sx_sample (adapt): target outside (0, 1)");
+    }
+    return 0;
+}
+
+// the resident kernels walk the recorded samples instead: the first one at or after it0 and its row, then + rec_every / + 1
+__device__ __forceinline__ void adapt_first_record(const sx_sample_adapt &ad, int64_t it0, int64_t &next, int64_t &row) {
+    next = ad.rec_start, row = 0;
+    if (it0 > ad.rec_start) {
+        row = (it0 - ad.rec_start + ad.rec_every - 1) / ad.rec_every;
+        next = ad.rec_start + row * ad.rec_every;
+    }
+}
 
 // parallel tempering, the exchange of rungs (kl, kl + 1) of a ladder after sample `it`: both replicas exchange their states when
 // this holds.  fl / fu their current values, bl / bu their inverse temperatures, ql the LOWER rung's replica index.

@@ -39,14 +39,23 @@ inline Geometry chain_geometry(int64_t C, int n) {
 }
 
 // sample `it`: the proposal (it = 0: the initial point) -> prop (C, n); hmc: momentum -> pmom (C, n), its kinetic energy -> k0 (C)
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kernel(const sx_sample_args a, int64_t it,
-                                                                                  double *__restrict__ prop,
-                                                                                  double *__restrict__ pmom,
-                                                                                  double *__restrict__ k0) {
+// (ADAPT, here and below: sx_sample_adapt -- the chain's multiplier of a.step, read from ad.scale; see sx_sample.hpp)
+template <int LPR, bool ADAPT>
+__device__ __forceinline__ void sample_propose(const sx_sample_args &a, const sx_sample_adapt &ad, int64_t it,
+                                               double *__restrict__ prop, double *__restrict__ pmom,
+                                               double *__restrict__ k0) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l, k = a.k;
     const int64_t c = id.rowc;
+    double scale = 1.0;
+    if constexpr (ADAPT)
+        if (it > 0 && ad.warmup > 0) scale = ad.scale[c];
+    const auto step = [&](int e) {
+        if constexpr (ADAPT)
+            return scale * a.step[e];
+        else
+            return a.step[e];
+    };
     const double *X = a.cur + c * n;
     double *U = prop + c * n;
     if (it == 0) {
@@ -65,11 +74,11 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kerne
             if (in0 || in1)
                 philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
             const double v0 = X[e0];
-            const double u0 = in0 ? v0 + z0 * a.step[e0] : v0;
+            const double u0 = in0 ? v0 + z0 * step(e0) : v0;
             if (id.active) U[e0] = u0;
             if (e1 < n) {
                 const double v1 = X[e1];
-                const double u1 = in1 ? v1 + z1 * a.step[e1] : v1;
+                const double u1 = in1 ? v1 + z1 * step(e1) : v1;
                 if (id.active) U[e1] = u1;
             }
         }
@@ -93,27 +102,60 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kerne
         if (id.active && l == 0) k0[c] = K0;
     }
 }
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kernel(const sx_sample_args a, int64_t it,
+                                                                                  double *__restrict__ prop,
+                                                                                  double *__restrict__ pmom,
+                                                                                  double *__restrict__ k0) {
+    sample_propose<LPR, false>(a, sx_sample_adapt{}, it, prop, pmom, k0);
+}
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_adapt_kernel(const sx_sample_args a,
+                                                                                        const sx_sample_adapt ad, int64_t it,
+                                                                                        double *__restrict__ prop,
+                                                                                        double *__restrict__ pmom,
+                                                                                        double *__restrict__ k0) {
+    sample_propose<LPR, true>(a, ad, it, prop, pmom, k0);
+}
 
 // one momentum step with the gradient G, and the position step behind it when `move`
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_kernel(const sx_sample_args a, double coef, int move,
-                                                                               double *__restrict__ q,
-                                                                               double *__restrict__ pmom,
-                                                                               const double *__restrict__ G) {
+template <int LPR, bool ADAPT>
+__device__ __forceinline__ void sample_leap(const sx_sample_args &a, const sx_sample_adapt &ad, double coef, int move,
+                                            double *__restrict__ q, double *__restrict__ pmom, const double *__restrict__ G) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
     double *Q = q + c * n, *Pm = pmom + c * n;
     const double *g = G + c * n;
+    double scale = 1.0;
+    if constexpr (ADAPT)
+        if (ad.warmup > 0) scale = ad.scale[c];
     for (int e = l; e < n; e += LPR) {
         const double gv = g[e];
-        const double p = Pm[e] - (coef * a.step[e]) * gv;
-        const double qn = Q[e] + a.step[e] * p;
+        double st = a.step[e];
+        if constexpr (ADAPT) st = scale * st;
+        const double p = Pm[e] - (coef * st) * gv;
+        const double qn = Q[e] + st * p;
         if (id.active) {
             Pm[e] = p;
             if (move) Q[e] = qn;
         }
     }
+}
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_kernel(const sx_sample_args a, double coef, int move,
+                                                                               double *__restrict__ q,
+                                                                               double *__restrict__ pmom,
+                                                                               const double *__restrict__ G) {
+    sample_leap<LPR, false>(a, sx_sample_adapt{}, coef, move, q, pmom, G);
+}
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_adapt_kernel(const sx_sample_args a,
+                                                                                     const sx_sample_adapt ad, double coef,
+                                                                                     int move, double *__restrict__ q,
+                                                                                     double *__restrict__ pmom,
+                                                                                     const double *__restrict__ G) {
+    sample_leap<LPR, true>(a, ad, coef, move, q, pmom, G);
 }
 
 // The rows numerical_gradient evaluates for axes [axis0, axis0 + naxes): the reference moves component i of its two copies by
@@ -159,12 +201,10 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_fd_gradient_k
 }
 
 // the decision on sample `it` with the proposal's value fprop (C), and the chain's bookkeeping
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel(const sx_sample_args a, int64_t it,
-                                                                                 const double *__restrict__ prop,
-                                                                                 const double *__restrict__ fprop,
-                                                                                 const double *__restrict__ pmom,
-                                                                                 const double *__restrict__ k0) {
+template <int LPR, bool ADAPT>
+__device__ __forceinline__ void sample_decide(const sx_sample_args &a, const sx_sample_adapt &ad, int64_t it,
+                                              const double *__restrict__ prop, const double *__restrict__ fprop,
+                                              const double *__restrict__ pmom, const double *__restrict__ k0) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
@@ -173,13 +213,16 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
     const bool mcmc = a.method == SX_SAMPLE_MCMC;
     const double fU = fprop[c];
     ChainState st;
+    AdaptState as;
     bool accept = false, xbest_changed = false;
     if (it == 0) {
         st.start(fU);
+        if constexpr (ADAPT) as.start();
         accept = true;  // (cur = the initial point)
         xbest_changed = true;
     } else {
         st.load(a, c);
+        if constexpr (ADAPT) as.load(ad, c);
         double K0 = 0.0, K = 0.0;
         if (!mcmc) {
             K0 = k0[c];
@@ -189,20 +232,30 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
             K = 0.5 * row_sum<LPR>(s);
         }
         const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
+        double dstat = 0.0;
         if (feasible) {
             st.nfeas += 1;
             const double logu = philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
             const double d = mcmc ? st.fcur - fU : ((st.fcur - fU) + K0) - K;
             accept = (d < 0.0 ? d : 0.0) > logu;  // Python's min(0.0, d): a NaN d gives 0.0
+            dstat = d;
         }
         if (accept) {
             bool acc_best, arg_best;
             st.accept(fU, it, acc_best, arg_best);
             xbest_changed = mcmc ? acc_best : arg_best;
         }
+        if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, dstat, st.nacc);
     }
     if (!id.active) return;
-    double *all = a.xall != nullptr ? a.xall + (c * a.maxiter + it) * n : nullptr;
+    bool record = a.xall != nullptr;
+    int64_t row = c * a.maxiter + it;
+    if constexpr (ADAPT) {
+        int64_t r = 0;
+        record = record && adapt_record(ad, it, r);
+        row = c * ad.rec_rows + r;
+    }
+    double *all = record ? a.xall + row * n : nullptr;
     for (int e = l; e < n; e += LPR) {
         const double v = accept ? U[e] : X[e];
         if (accept) X[e] = v;
@@ -210,9 +263,27 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
         if (xbest_changed) a.xbest[c * n + e] = v;
     }
     if (l == 0) {
-        if (all != nullptr) st_stream(a.funall + c * a.maxiter + it, st.fcur);
+        if (all != nullptr) st_stream(a.funall + row, st.fcur);
         st.store(a, c);
+        if constexpr (ADAPT) as.store(ad, c);
     }
+}
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel(const sx_sample_args a, int64_t it,
+                                                                                 const double *__restrict__ prop,
+                                                                                 const double *__restrict__ fprop,
+                                                                                 const double *__restrict__ pmom,
+                                                                                 const double *__restrict__ k0) {
+    sample_decide<LPR, false>(a, sx_sample_adapt{}, it, prop, fprop, pmom, k0);
+}
+template <int LPR>
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_adapt_kernel(const sx_sample_args a,
+                                                                                       const sx_sample_adapt ad, int64_t it,
+                                                                                       const double *__restrict__ prop,
+                                                                                       const double *__restrict__ fprop,
+                                                                                       const double *__restrict__ pmom,
+                                                                                       const double *__restrict__ k0) {
+    sample_decide<LPR, true>(a, ad, it, prop, fprop, pmom, k0);
 }
 
 // Parallel tempering (sx_sample_temper.hip) around a caller's objective: the decision of replica c = ladder * K + rung with
@@ -385,6 +456,42 @@ extern "C" int sx_sample_decide(const sx_sample_args *a, int64_t it, const doubl
     const Geometry g = chain_geometry(a->C, a->n);
     SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_decide_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
                                              (hipStream_t)stream, *a, it, prop, fprop, pmom, k0))
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+// The adapting / thinning forms (sx_sample_adapt): the checks of the plain entry points, then check_adapt
+extern "C" int sx_sample_propose_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop,
+                                       double *pmom, double *k0, void *stream) {
+    if (check_args(a, it) || check_adapt(a, ad)) return -1;
+    SX_REQUIRE(prop != nullptr, "sx_sample_propose_adapt: null proposal array");
+    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_propose_adapt: hmc needs pmom and k0");
+    const Geometry g = chain_geometry(a->C, a->n);
+    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_propose_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
+                                             (hipStream_t)stream, *a, *ad, it, prop, pmom, k0))
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sx_sample_leap_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q,
+                                    double *pmom, const double *G, void *stream) {
+    if (check_args(a, 0) || check_adapt(a, ad)) return -1;
+    SX_REQUIRE(a->method == SX_SAMPLE_HMC && q && pmom && G, "sx_sample_leap_adapt: hmc with q, pmom and G");
+    const Geometry g = chain_geometry(a->C, a->n);
+    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_leap_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
+                                             (hipStream_t)stream, *a, *ad, coef, move, q, pmom, G))
+    SX_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
+                                      const double *fprop, const double *pmom, const double *k0, void *stream) {
+    if (check_args(a, it) || check_adapt(a, ad)) return -1;
+    SX_REQUIRE(prop && fprop, "sx_sample_decide_adapt: null proposal / value array");
+    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_decide_adapt: hmc needs pmom and k0");
+    const Geometry g = chain_geometry(a->C, a->n);
+    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_decide_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
+                                             (hipStream_t)stream, *a, *ad, it, prop, fprop, pmom, k0))
     SX_LAUNCH_CHECK();
     return 0;
 }

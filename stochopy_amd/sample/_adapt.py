@@ -1,0 +1,70 @@
+"""Per-chain step-size adaptation in a warm-up, burn-in and thinning (options ``warmup``, ``target_accept``, ``burn``,
+``thin`` of ``sample.mcmc`` / ``sample.hmc``; csrc/sx_sample.hpp ``adapt_update``).  The checks need no device."""
+import numpy as np
+
+OPTIONS = ("warmup", "target_accept", "burn", "thin")
+
+
+class Adapt:
+    """The checked options of one run: ``warmup`` W, ``target`` (the acceptance the rule steers to), ``burn`` B, ``thin`` T
+    and ``rows`` M = ceil((maxiter - B) / T), the rows of xall / funall per chain."""
+
+    def __init__(self, warmup, target, burn, thin, maxiter):
+        self.warmup, self.target, self.burn, self.thin = warmup, target, burn, thin
+        self.rows = -(-(maxiter - burn) // thin)
+        self.recorded = np.arange(burn, maxiter, thin)  # the samples xall / funall hold
+
+
+def _integer(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{name} is an integer, not {type(value).__name__}")
+    return int(value)
+
+
+def _is(value, default):
+    return not isinstance(value, bool) and isinstance(value, (int, np.integer)) and value == default
+
+
+def given(warmup, target_accept, burn, thin):
+    """The names of the options that are not at their defaults (``warmup=0, target_accept=None, burn=None, thin=1``)."""
+    at_default = {"warmup": _is(warmup, 0), "target_accept": target_accept is None, "burn": burn is None, "thin": _is(thin, 1)}
+    return [name for name in OPTIONS if not at_default[name]]
+
+
+def refuse_with_temperatures(warmup, target_accept, burn, thin):
+    names = given(warmup, target_accept, burn, thin)
+    if names:
+        raise ValueError(f"{' / '.join(names)}: not served together with temperatures (the tempered kernels neither adapt "
+                         "their step nor thin what they record)")
+
+
+def check(warmup, target_accept, burn, thin, rng, maxiter, default_target):
+    """None when every option is at its default (the run then takes the plain path), else the checked ``Adapt``.  Every
+    message names its option; nothing here touches the device."""
+    names = given(warmup, target_accept, burn, thin)
+    if not names:
+        return None
+    warmup = _integer("warmup", warmup)
+    thin = _integer("thin", thin)
+    if burn is not None:
+        burn = _integer("burn", burn)
+    if target_accept is not None:
+        if isinstance(target_accept, bool) or not isinstance(target_accept, (int, float, np.integer, np.floating)):
+            raise TypeError(f"target_accept is a float in (0, 1), not {type(target_accept).__name__}")
+        target_accept = float(target_accept)
+    if not 0 <= warmup <= maxiter - 1:
+        raise ValueError(f"warmup is an integer in [0, maxiter - 1] = [0, {maxiter - 1}], not {warmup}")
+    if target_accept is not None:
+        if warmup == 0:
+            raise ValueError("target_accept is what the warm-up steers the acceptance to: it goes with warmup > 0")
+        if not 0.0 < target_accept < 1.0:  # (a NaN fails both)
+            raise ValueError(f"target_accept is a float in (0, 1), not {target_accept}")
+    if burn is None:
+        burn = warmup
+    if not 0 <= burn <= maxiter - 1:
+        raise ValueError(f"burn is an integer in [0, maxiter - 1] = [0, {maxiter - 1}], not {burn}")
+    if thin < 1:
+        raise ValueError(f"thin is an integer >= 1, not {thin}")
+    if rng != "philox":
+        raise ValueError(f'{" / ".join(names)} need rng="philox": the adapting and thinning kernels make their draws themselves')
+    return Adapt(warmup, default_target if target_accept is None else target_accept, burn, thin, maxiter)

@@ -69,6 +69,8 @@ class Setup:
     temperatures = None  # parallel tempering (mcmc, _temper.py): the ladder as float64 (K,), and
     swap_every = None    # the samples between two exchange events
 
+    adapt = None  # warmup / target_accept / burn / thin (_adapt.py): the checked _adapt.Adapt, or None for the plain path
+
     def __init__(self, fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                  backend, nleap=None):
         if not hasattr(fun, "__call__"):
@@ -169,8 +171,9 @@ class _Unfused:
     propose -> fun -> decide; hmc puts nleap + 2 rounds of (gradient, leap) in front of fun.  The chains' state stays in the
     arrays of ``a``, as between the launches of a fused run with a callback."""
 
-    def __init__(self, s, ctx, a):
+    def __init__(self, s, ctx, a, ad=None):
         self.s, self.ctx, self.a, self.L = s, ctx, a, ctx.L
+        self.ad = ad  # SxSampleAdapt: propose / leap / decide then go through their *_adapt forms
         Cn, n = s.chains, s.ndim
         self.hmc = s.method == _lib.SX_SAMPLE_HMC
         self.prop = ctx.empty((Cn, n))
@@ -186,6 +189,11 @@ class _Unfused:
     def call(self, name, *args):
         _lib.check(getattr(self.L, name)(C.byref(self.a), *args, self.ctx.stream_ptr), name)
 
+    def adapting(self, name, *args):
+        if self.ad is None:
+            return self.call(name, *args)
+        self.call(name + "_adapt", C.byref(self.ad), *args)
+
     def gradient(self):
         s, ptr = self.s, _device.ptr
         if s.gradient is not None:
@@ -199,14 +207,14 @@ class _Unfused:
 
     def sample(self, i):
         s, ptr = self.s, _device.ptr
-        self.call("sx_sample_propose", i, ptr(self.prop), ptr(self.pmom), ptr(self.k0))
+        self.adapting("sx_sample_propose", i, ptr(self.prop), ptr(self.pmom), ptr(self.k0))
         if self.hmc and i > 0:
             for g in range(s.nleap + 2):
                 G = self.gradient()
-                self.call("sx_sample_leap", 0.5 if g in (0, s.nleap + 1) else 1.0, int(g <= s.nleap), ptr(self.prop),
-                          ptr(self.pmom), ptr(G))
+                self.adapting("sx_sample_leap", 0.5 if g in (0, s.nleap + 1) else 1.0, int(g <= s.nleap), ptr(self.prop),
+                              ptr(self.pmom), ptr(G))
         f = s.external(self.ctx, self.prop)
-        self.call("sx_sample_decide", i, ptr(self.prop), ptr(f), ptr(self.pmom), ptr(self.k0))
+        self.adapting("sx_sample_decide", i, ptr(self.prop), ptr(f), ptr(self.pmom), ptr(self.k0))
 
 
 def run(s):
@@ -224,9 +232,10 @@ def run(s):
         dev.update({name: ctx.empty((Cn,)) for name in ("fcur", "facc", "fmin")})
         dev.update({name: ctx.empty((Cn,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
         on_device_all = s.return_all and s.callback is None
+        rows = m if s.adapt is None else s.adapt.rows  # (burn / thin: the rows of xall / funall per chain)
         if on_device_all:
-            dev["xall"] = ctx.empty((Cn, m, n))
-            dev["funall"] = ctx.empty((Cn, m))
+            dev["xall"] = ctx.empty((Cn, rows, n))
+            dev["funall"] = ctx.empty((Cn, rows))
         for name in ("lower", "upper", "step"):
             dev[name] = ctx.upload(getattr(s, name))
         if x0 is not None:
@@ -244,22 +253,38 @@ def run(s):
         a.rng = _lib.SX_RNG_HOST if legacy else _lib.SX_RNG_PHILOX
         a.reject, a.k, a.nleap, a.jac, a.fd_step = int(s.reject), s.k, s.nleap, s.jac, s.fd_step
         a.key0, a.key1 = s.key
+        ad = None
+        if s.adapt is not None:
+            ad = _lib.SxSampleAdapt()
+            if s.adapt.warmup > 0:
+                dev.update({name: ctx.empty((Cn,)) for name in ("scale", "hbar", "logsbar")})
+                dev["nacc_warm"] = ctx.empty((Cn,), dtype=t.int64)
+            for name in ("scale", "hbar", "logsbar", "nacc_warm"):
+                setattr(ad, name, _device.ptr(dev.get(name)))
+            ad.warmup, ad.rec_start, ad.rec_rows, ad.target = s.adapt.warmup, s.adapt.burn, rows, s.adapt.target
+            ad.rec_every = min(s.adapt.thin, m)  # (the same rows; the library takes rec_every < 2^31)
 
         def host(name):
             return dev[name].cpu().numpy()
 
+        def launch(i, steps):
+            if ad is None:
+                _lib.check(L.sx_sample_run(C.byref(a), i, steps, ctx.stream_ptr), "sx_sample_run")
+            else:
+                _lib.check(L.sx_sample_run_adapt(C.byref(a), C.byref(ad), i, steps, ctx.stream_ptr), "sx_sample_run_adapt")
+
         if s.external is not None:
-            advance = _Unfused(s, ctx, a).sample
+            advance = _Unfused(s, ctx, a, ad).sample
         else:
             def advance(i):
-                _lib.check(L.sx_sample_run(C.byref(a), i, 1, ctx.stream_ptr), "sx_sample_run")
+                launch(i, 1)
 
         if s.callback is None:
             if s.external is not None:
                 for i in range(m):
                     advance(i)
             else:  # the whole run is one launch
-                _lib.check(L.sx_sample_run(C.byref(a), 0, m, ctx.stream_ptr), "sx_sample_run")
+                launch(0, m)
             xall = host("xall") if on_device_all else None
             funall = host("funall") if on_device_all else None
         else:
@@ -279,14 +304,23 @@ def run(s):
                                      accept_ratio=1.0 if i == 0 else int(host("nacc").sum()) / (Cn * (i + 1)))
                 if s.return_all:
                     upto = max(i, 1)
-                    state.update({"xall": xall[0, :upto] if Cn == 1 else xall[:, :upto],
-                                  "funall": funall[0, :upto] if Cn == 1 else funall[:, :upto]})
+                    if s.adapt is not None:  # the recorded rows among the samples before the newest
+                        upto = s.adapt.recorded[s.adapt.recorded < upto]
+                    else:
+                        upto = slice(0, upto)
+                    state.update({"xall": xall[0, upto] if Cn == 1 else xall[:, upto],
+                                  "funall": funall[0, upto] if Cn == 1 else funall[:, upto]})
                 s.callback(xall[0, i] if Cn == 1 else xall[:, i], state)
+            if s.adapt is not None:
+                xall, funall = xall[:, s.adapt.recorded], funall[:, s.adapt.recorded]
         ctx.sync()
         nacc, nfeas = host("nacc"), host("nfeas")
         mcmc = s.method == _lib.SX_SAMPLE_MCMC
         fbest = host("facc" if mcmc else "fmin")
         xbest = host("xbest")
+        warm = s.adapt is not None and s.adapt.warmup > 0
+        if warm:
+            scale, nacc_warm = host("scale"), host("nacc_warm")
     if stream is not None:
         stream.sync_back()  # numpy's global stream is where the reference would leave it
     b = int(np.argmin(fbest))  # (numpy's rule: the first NaN, else the first minimum; all inf: chain 0)
@@ -298,6 +332,12 @@ def run(s):
         res["nreject"] = Cn * (m - 1) - int(nfeas.sum())  # proposals that left the box
     if Cn > 1:
         res["accept_ratios"] = nacc / m
+    if warm:
+        after = m - 1 - s.adapt.warmup  # samples generated with the frozen step
+        sampling = (nacc - nacc_warm) / after if after > 0 else np.zeros(Cn)
+        res["stepsizes"] = scale[0] if Cn == 1 else scale
+        res["accept_ratios_sampling"] = sampling[0] if Cn == 1 else sampling
+        res["warmup"] = s.adapt.warmup
     if s.return_all:
         res["xall"] = xall[0] if Cn == 1 else xall
         res["funall"] = funall[0] if Cn == 1 else funall

@@ -13,7 +13,7 @@ _sampler_map = {}
 class SampleResult(OptimizeResult):
     """Sampling result: keys x, fun, nit, accept_ratio (+ nfev for hmc, xall / funall with ``return_all``, and
     accept_ratios with more than one chain; with ``temperatures``: accept_ratios per ladder and rung, temperatures and
-    swap_ratios)."""
+    swap_ratios; with ``warmup``: stepsizes, accept_ratios_sampling and warmup)."""
 
 
 def register(name, sample):
@@ -45,6 +45,11 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
       exchange their states every ``swap_every`` samples (default 1).  The result holds the cold rungs (``xall``,
       ``funall``, ``x``, ``fun``, ``accept_ratio``), ``accept_ratios (C, K)``, ``temperatures (K,)`` and
       ``swap_ratios (C, K-1)``; the callback's ``xk`` is the ``(C, ndim)`` cold states.  See ``sample.mcmc``.
+
+    - ``warmup`` / ``target_accept`` / ``burn`` / ``thin`` (``rng="philox"``; not with ``temperatures``): ``warmup=W``
+      adapts a per-chain multiplier of ``stepsize`` over samples 1 ... W (dual averaging towards ``target_accept``) and
+      freezes it; ``xall`` / ``funall`` hold samples ``burn, burn + thin, ...`` only (``burn`` defaults to ``warmup``).
+      The result gains ``stepsizes``, ``accept_ratios_sampling`` and ``warmup``.  See ``sample.mcmc``.
 
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """

@@ -1,7 +1,7 @@
 """Hamiltonian (hybrid) Monte-Carlo (reference: stochopy/sample/hmc/_hmc.py)."""
 from .. import _lib
 from ..factory.benchmark import batched
-from . import _chains
+from . import _adapt, _chains
 from ._helpers import register
 
 __all__ = ["sample"]
@@ -26,6 +26,10 @@ def sample(
     backend="hip",
     temperatures=None,
     swap_every=None,
+    warmup=0,
+    target_accept=None,
+    burn=None,
+    thin=1,
 ):
     """Sample the variable space with Hamiltonian Monte-Carlo (``hmc/_hmc.py:13-200``), ``chains`` independent
     chains in one kernel.
@@ -52,8 +56,14 @@ def sample(
       draw sequence then depends on the data, so it needs ``rng="philox"``.
     - ``temperatures`` / ``swap_every`` (parallel tempering, see ``sample.mcmc``) are refused: tempering the potential
       and its gradient is not built.
+
+    ``warmup`` / ``target_accept`` / ``burn`` / ``thin`` (``rng="philox"``): per-chain step-size adaptation in a warm-up,
+    burn-in and thinning, as ``sample.mcmc`` describes them; the multiplier scales the momentum and the position steps
+    alike, the default ``target_accept`` is 0.65, and a trajectory whose ``d`` is NaN counts as rejected in the
+    adaptation (it shrinks the step) while the decision itself stays what it is.  They work with every ``jac``.
     """
     if temperatures is not None or swap_every is not None:
+        _adapt.refuse_with_temperatures(warmup, target_accept, burn, thin)
         raise ValueError('temperatures / swap_every (parallel tempering) are served by method="mcmc" only')
     run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                         backend, nleap=nleap)
@@ -76,6 +86,7 @@ def sample(
     elif own_gradient:
         run.gradient = _chains.AutogradGradient(run.external)
     run.fd_step = float(finite_diff_abs_step)
+    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.65)
     return _chains.run(run)
 
 

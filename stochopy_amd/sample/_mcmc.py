@@ -1,6 +1,6 @@
 """Metropolis-Hastings (reference: stochopy/sample/mcmc/_mcmc.py)."""
 from .. import _lib
-from . import _chains
+from . import _adapt, _chains
 from ._helpers import register
 
 __all__ = ["sample"]
@@ -23,6 +23,10 @@ def sample(
     backend="hip",
     temperatures=None,
     swap_every=None,
+    warmup=0,
+    target_accept=None,
+    burn=None,
+    thin=1,
 ):
     """Sample the variable space with the Metropolis-Hastings algorithm (``mcmc/_mcmc.py:13-161``), ``chains``
     independent chains in one kernel.
@@ -56,10 +60,25 @@ def sample(
     ``(ndim,)`` (shared) or ``(C, ndim)`` (one point per ladder, shared by its rungs); the callback's ``xk`` is the
     ``(C, ndim)`` cold states.  K is at most ``sx_sample_tempered_max_rungs(ndim)`` (16 up to ndim 128).  Not served:
     ``method="hmc"``, exchanging temperatures instead of states, adaptive ladders, the hot rungs' trajectories.
+
+    Step-size adaptation in a warm-up, burn-in and thinning (no counterpart in the reference; ``rng="philox"``; not with
+    ``temperatures``).  ``warmup=W`` (integer, ``0 <= W <= maxiter - 1``, default 0): chain c carries a multiplier
+    ``s_c`` of ``stepsize`` (1.0 at the start) that samples 1 ... W adapt by dual averaging (Hoffman & Gelman 2014)
+    towards the acceptance ``target_accept`` (a float in (0, 1); default 0.234, 0.44 when one variable is perturbed per
+    sample; only with ``warmup > 0``); from sample W + 1 on it is frozen at its average.  The decision rule is not
+    changed.  ``burn=B`` (integer, ``0 <= B <= maxiter - 1``, default ``warmup``) and ``thin=T`` (integer >= 1, default
+    1): ``xall`` / ``funall`` hold samples B, B + T, B + 2T, ... ``< maxiter`` -- ``ceil((maxiter - B) / T)`` rows in
+    the place of ``maxiter``.  ``x``, ``fun``, ``nit``, ``accept_ratio`` and ``accept_ratios`` stay defined over ALL
+    generated samples, so ``x`` may be a sample ``xall`` does not hold.  With ``warmup > 0`` the result also has
+    ``stepsizes`` (the frozen multipliers, ``(C,)``; the step in use is ``stepsizes * stepsize``),
+    ``accept_ratios_sampling`` (``(C,)``: accepted samples after the warm-up over ``maxiter - 1 - W``; 0.0 when there is
+    none) -- both scalars for one chain -- and ``warmup``.  The callback is called once per generated sample as before;
+    its state's ``xall`` / ``funall`` hold the recorded rows among the samples before the newest.
     """
     if temperatures is not None or swap_every is not None:
         from . import _temper
 
+        _adapt.refuse_with_temperatures(warmup, target_accept, burn, thin)
         ladder, every = _temper.check_ladder(temperatures, swap_every, rng)
         run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                             backend)
@@ -76,6 +95,7 @@ def sample(
         raise ValueError()
     run.method = _lib.SX_SAMPLE_MCMC
     run.k = max(1, int(perc * run.ndim))
+    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.44 if run.k == 1 else 0.234)
     return _chains.run(run)
 
 

@@ -3,8 +3,8 @@
 
 Configurations (chains = 16 384, rosenbrock, Philox draws; xall stays on the device while timed):
     mcmc           ndim 128, maxiter 1000, return_all off
-    mcmc+xall      ndim 128, maxiter 200,  return_all on  (xall is 3.4 GB: the run is bound by writing it -- the bytes stored
-                   per second are given as a share of the HBM peak DESIGN.md uses, 8 TB/s)
+    mcmc+xall      ndim 128, maxiter 200,  return_all on  (xall is 3.4 GB; the bytes stored per second are given as a share
+                   of the HBM peak DESIGN.md uses, 8 TB/s -- 14 %: not bound by writing it, see --adapt and DESIGN.md §19)
     hmc analytic   ndim 64,  maxiter 100,  nleap 10, jac="analytic"
     hmc fd         ndim 64,  maxiter 10,   nleap 10, finite differences (1 536 objective calls per sample and chain)
 Every configuration is warmed up once, then the configurations take turns for --rounds rounds; the line of a configuration
@@ -21,6 +21,13 @@ rungs (temperatures geomspace(1, 64, 16)), exchanging after every sample (swap_e
 counts every replica's samples, `vs_plain` is the ratio of the medians.  No CPU side.
 
     python tools/bench_sample.py --tempered [--rounds 5] [--out profiles/sample_temper_bench.jsonl]
+
+--adapt: what the warm-up and thinning cost (sx_sample_run_adapt).  The four configurations above take turns, by the same
+protocol, with `mcmc` and `hmc analytic` adapting their step for warmup = maxiter // 2 samples (`vs_plain`: samples / s over the
+plain configuration's, ratio of the medians) and with `mcmc+xall` keeping every 10th sample (thin=10: a tenth of the bytes;
+its line carries the bytes stored per second and `vs_plain` too).
+
+    python tools/bench_sample.py --adapt --no-cpu [--rounds 5] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -110,6 +117,36 @@ class TemperedRun(DeviceRun):
                    "sx_sample_tempered_run")
 
 
+class AdaptRun(DeviceRun):
+    """The same configuration through sx_sample_run_adapt, as stochopy_amd.sample launches it with warmup / burn / thin."""
+
+    def __init__(self, ctx, method, ndim, chains, o, warmup=0, burn=0, thin=1):
+        from stochopy_amd import _device, _lib
+
+        t = _device.torch()
+        rows = -(-(o["maxiter"] - burn) // thin)
+        self.rows = rows
+        super().__init__(ctx, method, ndim, chains, o)
+        if o["return_all"]:  # (the parent's (chains, maxiter, ndim) arrays are dropped for the thinned ones)
+            self.dev["xall"], self.dev["funall"] = ctx.empty((chains, rows, ndim)), ctx.empty((chains, rows))
+            self.a.xall, self.a.funall = _device.ptr(self.dev["xall"]), _device.ptr(self.dev["funall"])
+            self.stored = chains * rows * (ndim + 1) * 8
+        self.ad = ad = _lib.SxSampleAdapt()
+        if warmup > 0:
+            self.state = {name: ctx.empty((chains,)) for name in ("scale", "hbar", "logsbar")}
+            self.state["nacc_warm"] = ctx.empty((chains,), dtype=t.int64)
+            for name, buf in self.state.items():
+                setattr(ad, name, _device.ptr(buf))
+        ad.warmup, ad.rec_start, ad.rec_every, ad.rec_rows = warmup, burn, thin, rows
+        ad.target = 0.234 if method == "mcmc" else 0.65
+
+    def launch(self):
+        from stochopy_amd import _lib
+
+        _lib.check(self.L.sx_sample_run_adapt(C.byref(self.a), C.byref(self.ad), 0, self.m, self.ctx.stream_ptr),
+                   "sx_sample_run_adapt")
+
+
 def cpu_rate(method, ndim, o):
     """Samples per second of one chain on one core, and what ran."""
     o = dict(o, seed=3)
@@ -143,6 +180,7 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--out")
     ap.add_argument("--tempered", action="store_true", help="the plain mcmc kernel next to ladders of 16 replicas")
+    ap.add_argument("--adapt", action="store_true", help="the plain configurations next to a warm-up and to thin=10")
     args = ap.parse_args()
     from stochopy_amd import _device
 
@@ -156,6 +194,18 @@ def main():
                          TemperedRun(ctx, ndim, args.chains // 16 * 16, 16, every, o)))
     else:
         runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o)) for tag, method, ndim, o in CONFIGS]
+    plain_of = {}
+    if args.adapt:
+        by_tag = {tag: (method, ndim, o) for tag, method, ndim, o in CONFIGS}
+        for tag in ("mcmc", "hmc analytic"):
+            method, ndim, o = by_tag[tag]
+            W = o["maxiter"] // 2
+            new = f"{tag} warmup={W}"
+            runs.append((new, method, ndim, dict(o, warmup=W), AdaptRun(ctx, method, ndim, args.chains, o, warmup=W, burn=W)))
+            plain_of[new] = tag
+        method, ndim, o = by_tag["mcmc+xall"]
+        runs.append(("mcmc+xall thin=10", method, ndim, dict(o, thin=10), AdaptRun(ctx, method, ndim, args.chains, o, thin=10)))
+        plain_of["mcmc+xall thin=10"] = "mcmc+xall"
     launches = {}
     for tag, *_, r in runs:
         r.timed()  # warm-up: code object load, first touch of xall
@@ -174,6 +224,9 @@ def main():
         if args.tempered:
             line.update({k: o[k] for k in ("ladders", "K", "swap_every") if k in o})
             line["vs_plain"] = float(np.median(times[runs[0][0]])) / float(np.median(ts)) * r.samples / runs[0][4].samples
+        if tag in plain_of:
+            line.update({k: o[k] for k in ("warmup", "thin") if k in o})
+            line["vs_plain"] = float(np.median(times[plain_of[tag]])) / float(np.median(ts))
         if r.stored:
             line["stored_bytes_per_s"] = r.stored / float(np.median(ts))
             line["share_of_hbm_peak"] = line["stored_bytes_per_s"] / HBM_PEAK
