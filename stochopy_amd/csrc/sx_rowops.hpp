@@ -557,4 +557,16 @@ __device__ __forceinline__ double philox_lhs_element(uint64_t gi, int e, int64_t
         default: { constexpr int LPR = 64; CALL; } break; \
     }
 
+// run CALL with `constexpr int FUN` bound to the objective `fun_id` names (checked by the caller: 0 <= fun_id < SX_FUN_COUNT)
+#define SX_DISPATCH_FUN(fun_id, CALL)                                                           \
+    switch (fun_id) {                                                                           \
+        case SX_FUN_ACKLEY: { constexpr int FUN = SX_FUN_ACKLEY; CALL; } break;                 \
+        case SX_FUN_GRIEWANK: { constexpr int FUN = SX_FUN_GRIEWANK; CALL; } break;             \
+        case SX_FUN_QUARTIC: { constexpr int FUN = SX_FUN_QUARTIC; CALL; } break;               \
+        case SX_FUN_RASTRIGIN: { constexpr int FUN = SX_FUN_RASTRIGIN; CALL; } break;           \
+        case SX_FUN_ROSENBROCK: { constexpr int FUN = SX_FUN_ROSENBROCK; CALL; } break;         \
+        case SX_FUN_SPHERE: { constexpr int FUN = SX_FUN_SPHERE; CALL; } break;                 \
+        default: { constexpr int FUN = SX_FUN_STYBLINSKI_TANG; CALL; } break;                   \
+    }
+
 }  // namespace sx

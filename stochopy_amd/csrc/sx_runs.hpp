@@ -5,22 +5,11 @@
 
 #include "sx_device.hpp"
 #include "sx_enqueue.hpp"
+#include "sx_rowops.hpp"  // SX_DISPATCH_FUN
 
 namespace sx {
 
 constexpr int64_t kLdsLimit = 160 * 1024;  // what one workgroup may declare on gfx950
-
-// run CALL with `constexpr int FUN` bound to the objective `fun_id` names (checked by the caller: 0 <= fun_id < SX_FUN_COUNT)
-#define SX_DISPATCH_FUN(fun_id, CALL)                                                           \
-    switch (fun_id) {                                                                           \
-        case SX_FUN_ACKLEY: { constexpr int FUN = SX_FUN_ACKLEY; CALL; } break;                 \
-        case SX_FUN_GRIEWANK: { constexpr int FUN = SX_FUN_GRIEWANK; CALL; } break;             \
-        case SX_FUN_QUARTIC: { constexpr int FUN = SX_FUN_QUARTIC; CALL; } break;               \
-        case SX_FUN_RASTRIGIN: { constexpr int FUN = SX_FUN_RASTRIGIN; CALL; } break;           \
-        case SX_FUN_ROSENBROCK: { constexpr int FUN = SX_FUN_ROSENBROCK; CALL; } break;         \
-        case SX_FUN_SPHERE: { constexpr int FUN = SX_FUN_SPHERE; CALL; } break;                 \
-        default: { constexpr int FUN = SX_FUN_STYBLINSKI_TANG; CALL; } break;                   \
-    }
 
 // Per-run settings of a sweep (sx_*_runs_sweep_launch): DEVICE (R) arrays, element r for run r; a null pointer leaves the
 // argument struct's scalar to every run.  A kernel takes its struct by value and picks once, at entry.

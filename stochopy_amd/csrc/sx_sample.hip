@@ -11,6 +11,12 @@
 // Draws: SX_RNG_HOST reads the reference's own stream from memory (normals, log of the acceptance uniform: the order
 // does not depend on the data as long as nothing is rejected for feasibility); SX_RNG_PHILOX keys every draw by
 // (slot, chain, sample, purpose) -- sx_device.hpp kPurposeSample* -- so a chain depends on its index and the key only.
+//
+// The two resident kernels below keep their OWN spelling of the chain step (proposal, decision, load / record / store), the
+// one sx_sample.hpp states for the unfused and tempered kernels: folded into those shared functions the same arithmetic came out
+// 1 - 3 % slower here (register allocation and scheduling of the sample loop moved), so the copies stay and the
+// GPU tests hold the two spellings together bit for bit (tests/test_gpu_sample_batched.py, test_gpu_sample_temper.py).
+#include "sx_enqueue.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
 #include "sx_sample.hpp"
@@ -318,7 +324,6 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void gradient_kernel(cons
 
 template <bool ADAPT>
 using sample_kernel_t = void (*)(const sx_sample_args, const PlanArg, int64_t, int64_t, const AdaptArg<ADAPT>);
-using gradient_kernel_t = void (*)(const double *, int64_t, int, double *);
 
 template <int FUN, int LPR, bool ADAPT>
 sample_kernel_t<ADAPT> pick_variant(int variant) {
@@ -326,32 +331,28 @@ sample_kernel_t<ADAPT> pick_variant(int variant) {
            : variant == kHmcFd ? hmc_kernel<FUN, LPR, false, ADAPT>
                                : hmc_kernel<FUN, LPR, true, ADAPT>;
 }
-template <int LPR, bool ADAPT>
-sample_kernel_t<ADAPT> pick_sample(int fun_id, int variant) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return pick_variant<SX_FUN_ACKLEY, LPR, ADAPT>(variant);
-        case SX_FUN_GRIEWANK: return pick_variant<SX_FUN_GRIEWANK, LPR, ADAPT>(variant);
-        case SX_FUN_QUARTIC: return pick_variant<SX_FUN_QUARTIC, LPR, ADAPT>(variant);
-        case SX_FUN_RASTRIGIN: return pick_variant<SX_FUN_RASTRIGIN, LPR, ADAPT>(variant);
-        case SX_FUN_ROSENBROCK: return pick_variant<SX_FUN_ROSENBROCK, LPR, ADAPT>(variant);
-        case SX_FUN_SPHERE: return pick_variant<SX_FUN_SPHERE, LPR, ADAPT>(variant);
-        default: return pick_variant<SX_FUN_STYBLINSKI_TANG, LPR, ADAPT>(variant);
-    }
-}
-template <int LPR>
-gradient_kernel_t pick_gradient(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return gradient_kernel<SX_FUN_ACKLEY, LPR>;
-        case SX_FUN_GRIEWANK: return gradient_kernel<SX_FUN_GRIEWANK, LPR>;
-        case SX_FUN_QUARTIC: return gradient_kernel<SX_FUN_QUARTIC, LPR>;
-        case SX_FUN_RASTRIGIN: return gradient_kernel<SX_FUN_RASTRIGIN, LPR>;
-        case SX_FUN_ROSENBROCK: return gradient_kernel<SX_FUN_ROSENBROCK, LPR>;
-        case SX_FUN_SPHERE: return gradient_kernel<SX_FUN_SPHERE, LPR>;
-        default: return gradient_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
-    }
-}
 
 int variant_of(int method, int jac) { return method == SX_SAMPLE_MCMC ? kMcmc : jac == SX_JAC_ANALYTIC ? kHmcAnalytic : kHmcFd; }
+
+// sx_sample_run and its adapting / thinning form: the same geometry and LDS
+template <bool ADAPT>
+int run_chains(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it0, int64_t steps, void *stream) {
+    if (check_sample_args(who, a, it0, steps, true, true) || (ADAPT && check_adapt(a, ad))) return -1;
+    if (steps == 0) return 0;
+    PlanArg plan;
+    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
+    const int variant = variant_of(a->method, a->jac);
+    sample_kernel_t<ADAPT> kern = nullptr;
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, (kern = pick_variant<FUN, LPR, ADAPT>(variant))))
+    const int waves = sample_waves(variant, a->n);
+    const int chains = waves * (kWave / lanes_per_row(a->n));
+    const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
+    if (lds > 64 * 1024)  // one wave's chains need more than the default limit (gfx950: 160 KiB per workgroup)
+        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return Enqueue((hipStream_t)stream)
+        .kernel(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, *a, plan, it0, it0 + steps,
+                adapt_arg<ADAPT>(ad));
+}
 
 }  // namespace
 }  // namespace sx
@@ -363,84 +364,24 @@ extern "C" int sx_sample_chains_per_workgroup(int method, int jac, int n) {
     return sample_waves(variant_of(method, jac), n) * (kWave / lanes_per_row(n));
 }
 
-namespace {
-int check_run_args(const sx_sample_args *a, int64_t it0, int64_t steps) {
-    SX_REQUIRE(a != nullptr, "sx_sample_run: null args");
-    SX_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
-               "sx_sample_run: null state pointer");
-    SX_REQUIRE(a->lower && a->upper && a->step, "sx_sample_run: bounds / step missing");
-    SX_REQUIRE(a->C >= 1 && a->C < (int64_t)1 << 31 && a->n >= 1 && a->n <= kWideFrom, "sx_sample_run: bad shape");
-    SX_REQUIRE(a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT, "sx_sample_run: unknown objective");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || a->method == SX_SAMPLE_HMC, "sx_sample_run: unknown method");
-    SX_REQUIRE(a->jac == SX_JAC_FINITE_DIFF || a->jac == SX_JAC_ANALYTIC, "sx_sample_run: unknown gradient mode");
-    SX_REQUIRE(a->rng == SX_RNG_HOST || a->rng == SX_RNG_PHILOX, "sx_sample_run: unknown rng mode");
-    SX_REQUIRE(a->maxiter >= 1 && a->maxiter < (int64_t)1 << 31 && it0 >= 0 && steps >= 0 && it0 + steps <= a->maxiter,
-               "sx_sample_run: samples outside [0, maxiter)");
-    SX_REQUIRE(a->rng != SX_RNG_HOST || (a->C == 1 && a->x0 && !a->reject && (a->maxiter == 1 || (a->normals && a->logu))),
-               "sx_sample_run: host draws serve one chain without feasibility rejection, and need x0, normals and logu");
-    SX_REQUIRE((a->xall == nullptr) == (a->funall == nullptr), "sx_sample_run: xall and funall go together");
-    SX_REQUIRE(a->x0 == nullptr || a->x0_stride == 0 || a->x0_stride >= a->n, "sx_sample_run: bad x0 stride");
-    if (a->method == SX_SAMPLE_MCMC)
-        SX_REQUIRE(a->k >= 1 && a->k <= a->n, "sx_sample_run: block length outside [1, n]");
-    else
-        SX_REQUIRE(a->nleap >= 1 && (a->jac == SX_JAC_ANALYTIC || a->fd_step != 0.0), "sx_sample_run: bad nleap / step");
-    return 0;
-}
-}  // namespace
-
 extern "C" int sx_sample_run(const sx_sample_args *a, int64_t it0, int64_t steps, void *stream) {
-    if (check_run_args(a, it0, steps)) return -1;
-    if (steps == 0) return 0;
-    PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const int variant = variant_of(a->method, a->jac);
-    sample_kernel_t<false> kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = (pick_sample<LPR, false>(a->fun_id, variant)))
-    const int waves = sample_waves(variant, a->n);
-    const int chains = waves * (kWave / lanes_per_row(a->n));
-    const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
-    if (lds > 64 * 1024)  // one wave's chains need more than the default limit (gfx950: 160 KiB per workgroup)
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, (hipStream_t)stream,
-                       *a, plan, it0, it0 + steps, NoAdapt{});
-    SX_LAUNCH_CHECK();
-    return 0;
+    return run_chains<false>("sx_sample_run", a, nullptr, it0, steps, stream);
 }
 
 extern "C" int sx_sample_adapt_bytes(void) { return (int)sizeof(sx_sample_adapt); }
 
-// sx_sample_run with the adapting / thinning kernels (the same geometry and LDS)
 extern "C" int sx_sample_run_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it0, int64_t steps,
                                    void *stream) {
-    if (check_run_args(a, it0, steps) || check_adapt(a, ad)) return -1;
-    if (steps == 0) return 0;
-    PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    const int variant = variant_of(a->method, a->jac);
-    sample_kernel_t<true> kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = (pick_sample<LPR, true>(a->fun_id, variant)))
-    const int waves = sample_waves(variant, a->n);
-    const int chains = waves * (kWave / lanes_per_row(a->n));
-    const size_t lds = (size_t)chains * sample_row_doubles(variant, a->n) * sizeof(double);
-    if (lds > 64 * 1024)
-        SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a->C + chains - 1) / chains)), dim3(waves * kWave), lds, (hipStream_t)stream,
-                       *a, plan, it0, it0 + steps, *ad);
-    SX_LAUNCH_CHECK();
-    return 0;
+    return run_chains<true>("sx_sample_run_adapt", a, ad, it0, steps, stream);
 }
 
 extern "C" int sx_sample_gradient(int fun_id, const double *X, int64_t P, int n, double *G, void *stream) {
     SX_REQUIRE(X && G && P >= 1 && n >= 1 && n <= kWideFrom, "sx_sample_gradient: bad arguments");
     SX_REQUIRE(fun_id >= 0 && fun_id < SX_FUN_COUNT, "sx_sample_gradient: unknown objective");
-    gradient_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(n, kern = pick_gradient<LPR>(fun_id))
-    const int rpw = kWave / lanes_per_row(n);
-    int waves = 1;
-    while (2 * waves <= kMaxWavesPerBlock && 2 * waves * rpw <= kMaxRowsPerBlock && 2 * waves * rpw * n * 8 <= 64 * 1024) waves *= 2;
-    const int rows = waves * rpw;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((P + rows - 1) / rows)), dim3(waves * kWave), (size_t)rows * n * sizeof(double),
-                       (hipStream_t)stream, X, P, n, G);
-    SX_LAUNCH_CHECK();
-    return 0;
+    const int waves = waves_per_workgroup(n, (size_t)n * sizeof(double));
+    const int rows = waves * (kWave / lanes_per_row(n));
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(n, SX_DISPATCH_FUN(fun_id, return q.kernel(gradient_kernel<FUN, LPR>, dim3((unsigned)((P + rows - 1) / rows)),
+                                                               dim3(waves * kWave), (size_t)rows * n * sizeof(double), X, P, n, G)))
+    return -1;
 }

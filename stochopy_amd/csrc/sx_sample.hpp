@@ -1,8 +1,12 @@
-// Device helpers the sampler kernels share: the resident chain kernels (sx_sample.hip) and the kernels around a
-// caller-supplied objective (sx_sample_unfused.hip) compile the SAME expressions from here -- with bit-identical objective
-// (and gradient) values the two paths give the same run, bit for bit.  The tempered ladders (sx_sample_temper.hip, and their
-// decide / swap kernels in sx_sample_unfused.hip) share them too, with the exchange rule at the end of this file.
+// What the sampler kernels share, written once: the draws, a chain's scalars and its step-size adaptation, the STEP of a chain
+// (the mcmc block perturbation and the Metropolis decision, for the kernels around a caller-supplied objective,
+// sx_sample_unfused.hip, and the tempered ladders, sx_sample_temper.hip), the unfused tail, the exchange rule of the ladders,
+// and the host's argument check and workgroup size.  The two resident kernels of sx_sample.hip share the draws, the scalars and
+// the adaptation, but spell the step themselves (folded into the functions below it ran 1 - 3 % slower there: DESIGN.md 19);
+// the same expressions under -ffp-contract=off -- with bit-identical objective (and gradient) values the resident and the
+// unfused path give the same run, bit for bit, which tests/test_gpu_sample_batched.py holds them to.
 #pragma once
+#include <string>
 #include <type_traits>
 
 #include "sx_host.hpp"
@@ -18,15 +22,16 @@ __host__ __device__ inline int sample_row_doubles(int variant, int n) {
     const int S = gen_row_stride(n);
     return variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S;
 }
-// waves per workgroup: the largest power of two with <= 16 chains and <= 64 KiB of LDS; one wave may need more than that
-// (hmc with finite differences on rows of ~2 048 elements: the launch then raises the kernel's dynamic-LDS limit)
-inline int sample_waves(int variant, int n) {
+// Waves per workgroup of a kernel with one row group per chain (or row): the largest power of two within the row kernels' caps
+// (kMaxWavesPerBlock waves, kMaxRowsPerBlock rows) whose rows, at `row_bytes` of LDS each, fit 64 KiB.  One wave may need more
+// than that (hmc with finite differences on rows of ~2 048 elements: the launch then raises the kernel's dynamic-LDS limit).
+inline int waves_per_workgroup(int n, size_t row_bytes) {
     const int rpw = kWave / lanes_per_row(n);
-    const int fit = (64 * 1024) / (8 * sample_row_doubles(variant, n) * rpw);
     int w = 1;
-    while (2 * w <= fit && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w <= kMaxWavesPerBlock) w *= 2;
+    while (2 * w <= kMaxWavesPerBlock && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w * rpw * row_bytes <= 64 * 1024) w *= 2;
     return w;
 }
+inline int sample_waves(int variant, int n) { return waves_per_workgroup(n, sizeof(double) * sample_row_doubles(variant, n)); }
 
 template <int LPR>
 __device__ __forceinline__ double row_prod(double v) {
@@ -122,6 +127,13 @@ struct AdaptState {
 struct NoAdapt {};
 template <bool ADAPT>
 using AdaptArg = std::conditional_t<ADAPT, sx_sample_adapt, NoAdapt>;
+template <bool ADAPT>
+AdaptArg<ADAPT> adapt_arg(const sx_sample_adapt *ad) {  // (the plain entry points pass no `ad`)
+    if constexpr (ADAPT)
+        return *ad;
+    else
+        return {};
+}
 
 // After the decision of sample `it` >= 1 (d its own log acceptance ratio; feasible: it passed the box test; nacc the count
 // with this sample): one step of the rule for it <= warmup, the averaged multiplier frozen at it == warmup.  The decision
@@ -146,6 +158,37 @@ __device__ __forceinline__ bool adapt_record(const sx_sample_adapt &ad, int64_t 
     const uint32_t off = (uint32_t)(it - ad.rec_start), every = (uint32_t)ad.rec_every;
     row = (int64_t)(off / every);
     return off % every == 0u;
+}
+
+// SX_REQUIRE with the message "<who>: <what>", `who` the entry point's name in scope (here and in the three .hip files)
+#define SX_SAMPLE_REQUIRE(cond, what) SX_REQUIRE(cond, std::string(who) + ": " what)
+
+// What every sampler entry point `who` requires of sx_sample_args before it launches samples [it0, it0 + steps).  `resident`:
+// the objective is compiled into the kernel (fun_id names one, finite differences need their step here); `host_draws`: the
+// kernel can read the reference's stream (the resident chain kernels alone).
+inline int check_sample_args(const char *who, const sx_sample_args *a, int64_t it0, int64_t steps, bool resident, bool host_draws) {
+    SX_SAMPLE_REQUIRE(a != nullptr, "null args");
+    SX_SAMPLE_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
+                      "null state pointer");
+    SX_SAMPLE_REQUIRE(a->lower && a->upper && a->step, "bounds / step missing");
+    SX_SAMPLE_REQUIRE(a->C >= 1 && a->C < (int64_t)1 << 31 && a->n >= 1 && a->n <= kWideFrom, "bad shape");
+    SX_SAMPLE_REQUIRE(!resident || (a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT), "unknown objective");
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC || a->method == SX_SAMPLE_HMC, "unknown method");
+    SX_SAMPLE_REQUIRE(a->jac == SX_JAC_FINITE_DIFF || a->jac == SX_JAC_ANALYTIC, "unknown gradient mode");
+    SX_SAMPLE_REQUIRE(a->rng == SX_RNG_PHILOX || (host_draws && a->rng == SX_RNG_HOST),
+                      "unknown rng mode (around a caller's objective and on a ladder the draws are made in the kernels: "
+                      "SX_RNG_PHILOX)");
+    SX_SAMPLE_REQUIRE(a->maxiter >= 1 && a->maxiter < (int64_t)1 << 31 && it0 >= 0 && steps >= 0 && it0 + steps <= a->maxiter,
+                      "samples outside [0, maxiter)");
+    SX_SAMPLE_REQUIRE(a->rng != SX_RNG_HOST || (a->C == 1 && a->x0 && !a->reject && (a->maxiter == 1 || (a->normals && a->logu))),
+                      "host draws serve one chain without feasibility rejection, and need x0, normals and logu");
+    SX_SAMPLE_REQUIRE((a->xall == nullptr) == (a->funall == nullptr), "xall and funall go together");
+    SX_SAMPLE_REQUIRE(a->x0 == nullptr || a->x0_stride == 0 || a->x0_stride >= a->n, "bad x0 stride");
+    if (a->method == SX_SAMPLE_MCMC)
+        SX_SAMPLE_REQUIRE(a->k >= 1 && a->k <= a->n, "block length outside [1, n]");
+    else
+        SX_SAMPLE_REQUIRE(a->nleap >= 1 && (!resident || a->jac == SX_JAC_ANALYTIC || a->fd_step != 0.0), "bad nleap / step");
+    return 0;
 }
 
 // what every *_adapt entry point requires of `ad` next to its own checks of `a` (which come first: a is not null here)
@@ -204,6 +247,93 @@ __device__ __forceinline__ bool row_in_box(const sx_sample_args &a, const double
         in = in && v >= a.lower[e] && v <= a.upper[e];
     }
     return row_all<LPR>(in);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The step of a chain.  The kernels differ in where a chain's rows live (LDS, device memory) and whether a padding row group
+// may store: they pass that as functors (`put`, `step`) and keep their own loops over the rows.
+// ---------------------------------------------------------------------------------------------------------------------
+// element e of the chain's step: a.step[e] times the adapted multiplier s (the plain kernels do not multiply at all)
+template <bool ADAPT>
+__device__ __forceinline__ double chain_step(const sx_sample_args &a, double s, int e) {
+    if constexpr (ADAPT)
+        return s * a.step[e];
+    else
+        return a.step[e];
+}
+
+// Metropolis-Hastings, the proposal (mcmc/_mcmc.py:104-118): sample it >= 1 perturbs block (it - 1) mod nblocks of k
+// consecutive variables, [j0, j1) (the last block is the shorter one when k does not divide n), by randn(j1 - j0) * step
+__device__ __forceinline__ void mcmc_block(int64_t it, int n, int k, int nblocks, int &j0, int &j1) {
+    j0 = (int)((it - 1) % nblocks) * k;
+    j1 = j0 + k < n ? j0 + k : n;
+}
+// put(e, .) takes every element of the proposal: X[e] + z * step(e) inside the block, X[e] outside
+template <int LPR, class Step, class Put>
+__device__ __forceinline__ void mcmc_propose(const sx_sample_args &a, uint32_t chain, int64_t it, const double *X, int l,
+                                             int j0, int j1, Step &&step, Put &&put) {
+    const int n = a.n;
+    for (int e0 = l; e0 < n; e0 += 2 * LPR) {  // element pairs (e0, e0 + LPR): one Box-Muller call
+        const int e1 = e0 + LPR;
+        const bool in0 = e0 >= j0 && e0 < j1, in1 = e1 >= j0 && e1 < j1;
+        double z0 = 0.0, z1 = 0.0;
+        if (in0 || in1) {  // (Philox draws: the reference's stream is read by the resident kernels alone)
+            philox_normal_pair<LPR>(e0, chain, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
+        }
+        const double v0 = X[e0];
+        put(e0, in0 ? v0 + z0 * step(e0) : v0);
+        if (e1 < n) {
+            const double v1 = X[e1];
+            put(e1, in1 ? v1 + z1 * step(e1) : v1);
+        }
+    }
+}
+
+// The Metropolis decision on sample it >= 1 (mcmc/_mcmc.py:120-134, hmc/_hmc.py:159-172): a proposal of value fprop that
+// passed the box test (`feasible`; any proposal without constraints) is accepted when min(0, d) > log(rand()), d its log
+// acceptance ratio -- mcmc: fcur - fprop, on a tempered rung times beta; hmc: (fcur - fprop) + K0 - K.  Python's
+// min(0.0, d): a NaN d gives 0.0 and accepts.  `mcmc` picks what the run returns as x, whose change xbest_changed reports:
+// the best ACCEPTED sample (mcmc/_mcmc.py:155), or numpy's argmin over funall (hmc/_hmc.py:187).
+struct Decision {
+    bool accept = false, xbest_changed = false;
+    double dstat = 0.0;  // d of a feasible proposal, 0.0 else: what adapt_update takes
+};
+__device__ __forceinline__ Decision chain_decide(ChainState &st, const sx_sample_args &a, uint32_t chain, int64_t it,
+                                                 bool mcmc, bool feasible, double d, double fprop) {
+    Decision r;
+    if (feasible) {
+        st.nfeas += 1;
+        const double logu = philox_log_accept(chain, (uint32_t)it, a.key0, a.key1);
+        r.accept = (d < 0.0 ? d : 0.0) > logu;
+        r.dstat = d;
+    }
+    if (r.accept) {
+        bool acc_best, arg_best;
+        st.accept(fprop, it, acc_best, arg_best);
+        r.xbest_changed = mcmc ? acc_best : arg_best;
+    }
+    return r;
+}
+
+// The tail of a sample AROUND a caller's objective (sx_sample_unfused.hip), the chain's rows in device memory: cur <- the
+// proposal U when accepted; row `row` of xall / funall (when `record`) and xbest (when it changed) take the sample; the
+// scalars go back to their arrays
+template <int LPR>
+__device__ __forceinline__ void commit_sample(const sx_sample_args &a, const ChainState &st, int64_t c, int l, const double *U,
+                                              bool accept, bool xbest_changed, bool record, int64_t row) {
+    const int n = a.n;
+    double *X = a.cur + c * n;
+    double *all = record ? a.xall + row * n : nullptr;
+    for (int e = l; e < n; e += LPR) {
+        const double v = accept ? U[e] : X[e];
+        if (accept) X[e] = v;
+        if (all != nullptr) st_stream(all + e, v);
+        if (xbest_changed) a.xbest[c * n + e] = v;
+    }
+    if (l == 0) {
+        if (all != nullptr) st_stream(a.funall + row, st.fcur);
+        st.store(a, c);
+    }
 }
 
 }  // namespace

@@ -1,12 +1,12 @@
 // Parallel tempering (replica exchange) for the Metropolis-Hastings chains: LADDERS of K device-resident replicas.
 //
 // Replica q = c K + k is rung k of ladder c and samples p^(beta[k]), beta[k] = 1 / T_k, 1 = T_0 < T_1 < ... < T_{K-1}: its
-// acceptance test is mcmc_kernel's (sx_sample.hip) with d = (fcur - fprop) * beta[k], its draws are keyed by q in the place of
-// the chain index.  After sample `it` (it >= 1, it % swap_every == 0) the exchange event j = it / swap_every pairs neighbouring
-// rungs -- odd j (0,1), (2,3), ..., even j (1,2), (3,4), ...; a rung without a partner sits out -- and a pair exchanges its
-// STATES (X and fcur; the rungs stay where they are) when sx_sample.hpp tempered_swap says so.  Sample `it` of a replica is its
-// state after the event; an arriving state is compared with the replica's best values as an accepted proposal is, and moves
-// neither nacc nor nfeas.
+// proposal and acceptance test are mcmc_kernel's (sx_sample.hpp mcmc_propose / chain_decide, as the unfused kernels') with
+// d = (fcur - fprop) * beta[k], its draws are keyed by q in the place of the chain index.  After sample `it` (it >= 1,
+// it % swap_every == 0) the exchange event j = it / swap_every pairs neighbouring rungs -- odd j (0,1), (2,3), ..., even j
+// (1,2), (3,4), ...; a rung without a partner sits out -- and a pair exchanges its STATES (X and fcur; the rungs stay where
+// they are) when sx_sample.hpp tempered_swap says so.  Sample `it` of a replica is its state after the event; an arriving
+// state is compared with the replica's best values as an accepted proposal is, and moves neither nacc nor nfeas.
 //
 // Layout: a workgroup of `rows` row groups carries floor(rows / K) WHOLE ladders in consecutive row slots, so a ladder never
 // spans two workgroups and an exchange is two workgroup barriers and a row copy in LDS: no grid barrier, no atomics, no
@@ -76,42 +76,23 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (tempered_min_waves<FUN, 
             if (it == 0) {
                 for (int e = l; e < n; e += LPR) U[e] = initial_value<LPR>(a, q, e);
             } else {
-                j0 = (int)((it - 1) % nblocks) * k;
-                j1 = j0 + k < n ? j0 + k : n;
-                for (int e0 = l; e0 < n; e0 += 2 * LPR) {  // element pairs (e0, e0 + LPR): one Box-Muller call
-                    const int e1 = e0 + LPR;
-                    const bool in0 = e0 >= j0 && e0 < j1, in1 = e1 >= j0 && e1 < j1;
-                    double z0 = 0.0, z1 = 0.0;
-                    if (in0 || in1)
-                        philox_normal_pair<LPR>(e0, (uint32_t)q, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
-                    const double v0 = X[e0];
-                    U[e0] = in0 ? v0 + z0 * a.step[e0] : v0;
-                    if (e1 < n) {
-                        const double v1 = X[e1];
-                        U[e1] = in1 ? v1 + z1 * a.step[e1] : v1;
-                    }
-                }
+                mcmc_block(it, n, k, nblocks, j0, j1);
+                mcmc_propose<LPR>(
+                    a, (uint32_t)q, it, X, l, j0, j1, [&](int e) { return chain_step<false>(a, 1.0, e); },
+                    [&](int e, double v) { U[e] = v; });
             }
             const double fU = row_objective<FUN, LPR, 0, 0>(U, n, plan, l);
-            bool xbest_changed = false;
+            bool xbest_changed = true;  // (sample 0)
             if (it == 0) {
                 st.start(fU);
                 for (int e = l; e < n; e += LPR) X[e] = U[e];
-                xbest_changed = true;
             } else {
                 const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
-                bool accept = false;
-                if (feasible) {
-                    st.nfeas += 1;
-                    const double logu = philox_log_accept((uint32_t)q, (uint32_t)it, a.key0, a.key1);
-                    const double d = (st.fcur - fU) * beta[rung];  // (1.0 on the cold rung: mcmc_kernel's d, bit for bit)
-                    accept = (d < 0.0 ? d : 0.0) > logu;
-                }
-                if (accept) {
-                    bool arg_best;
-                    st.accept(fU, it, xbest_changed, arg_best);
+                // (beta = 1.0 on the cold rung: mcmc_kernel's d, bit for bit)
+                const Decision r = chain_decide(st, a, (uint32_t)q, it, true, feasible, (st.fcur - fU) * beta[rung], fU);
+                if (r.accept)
                     for (int e = l + ((j0 - l + LPR - 1) / LPR) * LPR; e < j1; e += LPR) X[e] = U[e];
-                }
+                xbest_changed = r.xbest_changed;
             }
             if (xbest_changed)  // (before the exchange: the state may leave this replica)
                 for (int e = l; e < n; e += LPR) a.xbest[(int64_t)q * n + e] = X[e];
@@ -160,19 +141,6 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (tempered_min_waves<FUN, 
 
 using tempered_kernel_t = void (*)(const sx_sample_args, const PlanArg, const double *, int, int64_t, int64_t *, int64_t, int64_t);
 
-template <int LPR>
-tempered_kernel_t pick_tempered(int fun_id) {
-    switch (fun_id) {
-        case SX_FUN_ACKLEY: return mcmc_tempered_kernel<SX_FUN_ACKLEY, LPR>;
-        case SX_FUN_GRIEWANK: return mcmc_tempered_kernel<SX_FUN_GRIEWANK, LPR>;
-        case SX_FUN_QUARTIC: return mcmc_tempered_kernel<SX_FUN_QUARTIC, LPR>;
-        case SX_FUN_RASTRIGIN: return mcmc_tempered_kernel<SX_FUN_RASTRIGIN, LPR>;
-        case SX_FUN_ROSENBROCK: return mcmc_tempered_kernel<SX_FUN_ROSENBROCK, LPR>;
-        case SX_FUN_SPHERE: return mcmc_tempered_kernel<SX_FUN_SPHERE, LPR>;
-        default: return mcmc_tempered_kernel<SX_FUN_STYBLINSKI_TANG, LPR>;
-    }
-}
-
 // rows a workgroup can hold at all: the row kernels' caps
 inline int max_rows(int n) {
     const int cap = kMaxWavesPerBlock * (kWave / lanes_per_row(n));
@@ -192,34 +160,25 @@ extern "C" int sx_sample_tempered_max_rungs(int n) {
 
 extern "C" int sx_sample_tempered_run(const sx_sample_args *a, const double *beta, int K, int64_t swap_every, int64_t *nswap,
                                       int64_t it0, int64_t steps, void *stream) {
-    SX_REQUIRE(a != nullptr && beta != nullptr && nswap != nullptr, "sx_sample_tempered_run: null args / beta / nswap");
-    SX_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
-               "sx_sample_tempered_run: null state pointer");
-    SX_REQUIRE(a->lower && a->upper && a->step, "sx_sample_tempered_run: bounds / step missing");
-    SX_REQUIRE(a->n >= 1 && a->n <= kWideFrom, "sx_sample_tempered_run: bad row length");
-    SX_REQUIRE(K >= 2 && K <= sx_sample_tempered_max_rungs(a->n),
-               "sx_sample_tempered_run: K outside [2, sx_sample_tempered_max_rungs(n)]");
-    SX_REQUIRE(a->C >= K && a->C < (int64_t)1 << 31 && a->C % K == 0, "sx_sample_tempered_run: C is ladders x K replicas");
-    SX_REQUIRE(swap_every >= 1, "sx_sample_tempered_run: swap_every < 1");
-    SX_REQUIRE(a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT, "sx_sample_tempered_run: unknown objective");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC && a->rng == SX_RNG_PHILOX, "sx_sample_tempered_run: mcmc with Philox draws");
-    SX_REQUIRE(a->maxiter >= 1 && a->maxiter < (int64_t)1 << 31 && it0 >= 0 && steps >= 0 && it0 + steps <= a->maxiter,
-               "sx_sample_tempered_run: samples outside [0, maxiter)");
-    SX_REQUIRE((a->xall == nullptr) == (a->funall == nullptr), "sx_sample_tempered_run: xall and funall go together");
-    SX_REQUIRE(a->x0 == nullptr || a->x0_stride == 0 || a->x0_stride >= a->n, "sx_sample_tempered_run: bad x0 stride");
-    SX_REQUIRE(a->k >= 1 && a->k <= a->n, "sx_sample_tempered_run: block length outside [1, n]");
+    const char *who = "sx_sample_tempered_run";
+    SX_SAMPLE_REQUIRE(a != nullptr && beta != nullptr && nswap != nullptr, "null args / beta / nswap");
+    if (check_sample_args(who, a, it0, steps, true, false)) return -1;
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC, "mcmc only");
+    SX_SAMPLE_REQUIRE(K >= 2 && K <= sx_sample_tempered_max_rungs(a->n), "K outside [2, sx_sample_tempered_max_rungs(n)]");
+    SX_SAMPLE_REQUIRE(a->C % K == 0, "C is ladders x K replicas");
+    SX_SAMPLE_REQUIRE(swap_every >= 1, "swap_every < 1");
     if (steps == 0) return 0;
     PlanArg plan;
     if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
     tempered_kernel_t kern = nullptr;
-    SX_DISPATCH_LPR(a->n, kern = pick_tempered<LPR>(a->fun_id))
+    SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, (kern = mcmc_tempered_kernel<FUN, LPR>)))
     const int rpw = kWave / lanes_per_row(a->n);
     int waves = sample_waves(kMcmc, a->n);
     while (waves * rpw < K) waves *= 2;  // (K <= max_rows(n): ends at kMaxWavesPerBlock or before)
     const int per_wg = waves * rpw / K;
     const int64_t ladders = a->C / K;
     const size_t lds = (size_t)per_wg * K * sample_row_doubles(kMcmc, a->n) * sizeof(double);
-    SX_REQUIRE(lds <= kLdsPerWorkgroup, "sx_sample_tempered_run: the ladders of a workgroup do not fit its LDS");
+    SX_SAMPLE_REQUIRE(lds <= kLdsPerWorkgroup, "the ladders of a workgroup do not fit its LDS");
     if (lds > 64 * 1024)  // more than the default limit (gfx950: 160 KiB per workgroup)
         SX_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     Enqueue q((hipStream_t)stream);

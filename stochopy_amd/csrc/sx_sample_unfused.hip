@@ -3,9 +3,12 @@
 //   mcmc: propose kernel -> caller's objective -> decide kernel
 //   hmc:  propose kernel -> (nleap + 2) x (gradient -> leap kernel) -> caller's objective -> decide kernel
 // where a gradient is the caller's own, or 2-point finite differences: fd_rows kernel -> caller's objective on the stacked
-// rows -> fd_gradient kernel.  Draws, arithmetic and bookkeeping are the resident kernels' (sx_sample.hpp, the same
-// expressions under -ffp-contract=off): given bit-identical objective / gradient values the run is the resident run, bit for
-// bit.  State lives in sx_sample_args' per-chain arrays, which the resident kernels round-trip from launch to launch too.
+// rows -> fd_gradient kernel.  The mcmc proposal, the decision and the tail of a sample are sx_sample.hpp's functions, shared with
+// the tempered ladders; they state the resident kernels' expressions (sx_sample.hip spells its own, for speed), under
+// -ffp-contract=off: given bit-identical objective / gradient values the run is the resident run, bit for bit.  What is
+// written HERE is where a chain's rows live (device memory, `if (active)` stores), the hmc momentum draw, the leap-frog step cut
+// at the gradient, the finite-difference rows and the exchange of a ladder's states in memory.  State lives in sx_sample_args'
+// per-chain arrays, which the resident kernels round-trip from launch to launch too.
 //
 // Parallel tempering (sx_sample_temper.hip) around such an objective: propose kernel -> caller's objective -> decide_tempered
 // kernel -> on an exchange event the swap kernel (one row group per pair of neighbouring rungs, the states in device memory).
@@ -13,13 +16,14 @@
 // One geometry for all these kernels: one row group of lanes_per_row(n) lanes per chain, lane l owns elements l, l + LPR, ...;
 // padding row groups shadow the last chain for loads and store nothing; no LDS, no barrier, no atomics.  Philox draws only.
 //
-// Reference code replaced (paths relative to the reference checkout):
+// Reference code replaced (paths relative to the reference checkout; the block's perturbation and the decisions are cited
+// again at the function of sx_sample.hpp that states them):
 //   stochopy/sample/mcmc/_mcmc.py:93, :106-118   initial point, the block's perturbation
 //   stochopy/sample/mcmc/_mcmc.py:120-140        decision and bookkeeping after `fun(xnew)`
 //   stochopy/sample/hmc/_hmc.py:124, :137-141    initial point, momentum and its kinetic energy
-//   stochopy/sample/hmc/_hmc.py:143-155          leap-frog steps
+//   stochopy/sample/hmc/_hmc.py:143-155          leap-frog steps (sample_leap_kernel)
 //   stochopy/sample/hmc/_hmc.py:157-172          decision and bookkeeping
-//   stochopy/sample/hmc/_hmc.py:217-233          numerical_gradient (in-place perturb / restore)
+//   stochopy/sample/hmc/_hmc.py:217-233          numerical_gradient (in-place perturb / restore: sample_fd_rows_kernel)
 #include "sx_enqueue.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
@@ -31,109 +35,85 @@ namespace {
 
 // rows of one workgroup: the row kernels' 16-row cap, no LDS to fit
 inline Geometry chain_geometry(int64_t C, int n) {
-    const int rpw = kWave / lanes_per_row(n);
-    int waves = 1;
-    while (2 * waves <= kMaxWavesPerBlock && 2 * waves * rpw <= kMaxRowsPerBlock) waves *= 2;
-    const int rows = waves * rpw;
+    const int waves = waves_per_workgroup(n, 0);
+    const int rows = waves * (kWave / lanes_per_row(n));
     return Geometry{(unsigned)((C + rows - 1) / rows), (unsigned)(waves * kWave), 0};
 }
 
+// ADAPT, here and below: sx_sample_adapt as the kernel's last argument (sx_sample.hpp; without it an empty struct that is never
+// read).  The propose and leap kernels need chain c's multiplier of a.step alone: ad.scale, 1.0 while nothing adapts.
+template <bool ADAPT>
+__device__ __forceinline__ double chain_scale(const AdaptArg<ADAPT> &ad, int64_t c) {
+    if constexpr (ADAPT)
+        if (ad.warmup > 0) return ad.scale[c];
+    return 1.0;
+}
+
 // sample `it`: the proposal (it = 0: the initial point) -> prop (C, n); hmc: momentum -> pmom (C, n), its kinetic energy -> k0 (C)
-// (ADAPT, here and below: sx_sample_adapt -- the chain's multiplier of a.step, read from ad.scale; see sx_sample.hpp)
 template <int LPR, bool ADAPT>
-__device__ __forceinline__ void sample_propose(const sx_sample_args &a, const sx_sample_adapt &ad, int64_t it,
-                                               double *__restrict__ prop, double *__restrict__ pmom,
-                                               double *__restrict__ k0) {
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kernel(const sx_sample_args a, int64_t it,
+                                                                                  double *__restrict__ prop,
+                                                                                  double *__restrict__ pmom,
+                                                                                  double *__restrict__ k0,
+                                                                                  const AdaptArg<ADAPT> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l, k = a.k;
     const int64_t c = id.rowc;
-    double scale = 1.0;
-    if constexpr (ADAPT)
-        if (it > 0 && ad.warmup > 0) scale = ad.scale[c];
-    const auto step = [&](int e) {
-        if constexpr (ADAPT)
-            return scale * a.step[e];
-        else
-            return a.step[e];
-    };
+    const bool active = id.active;
+    // (sample 0 takes no step; its decide kernel writes the first multiplier)
+    const double scale = it > 0 ? chain_scale<ADAPT>(ad, c) : 1.0;
     const double *X = a.cur + c * n;
     double *U = prop + c * n;
     if (it == 0) {
         for (int e = l; e < n; e += LPR) {
             const double v = initial_value<LPR>(a, c, e);
-            if (id.active) U[e] = v;
+            if (active) U[e] = v;
         }
     } else if (a.method == SX_SAMPLE_MCMC) {
-        const int nblocks = (n + k - 1) / k;
-        const int j0 = (int)((it - 1) % nblocks) * k;
-        const int j1 = j0 + k < n ? j0 + k : n;
-        for (int e0 = l; e0 < n; e0 += 2 * LPR) {  // element pairs (e0, e0 + LPR): one Box-Muller call
-            const int e1 = e0 + LPR;
-            const bool in0 = e0 >= j0 && e0 < j1, in1 = e1 >= j0 && e1 < j1;
-            double z0 = 0.0, z1 = 0.0;
-            if (in0 || in1)
-                philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleProposal, a.key0, a.key1, z0, z1);
-            const double v0 = X[e0];
-            const double u0 = in0 ? v0 + z0 * step(e0) : v0;
-            if (id.active) U[e0] = u0;
-            if (e1 < n) {
-                const double v1 = X[e1];
-                const double u1 = in1 ? v1 + z1 * step(e1) : v1;
-                if (id.active) U[e1] = u1;
-            }
-        }
+        int j0, j1;
+        mcmc_block(it, n, k, (n + k - 1) / k, j0, j1);
+        mcmc_propose<LPR>(
+            a, (uint32_t)c, it, X, l, j0, j1, [&](int e) { return chain_step<ADAPT>(a, scale, e); },
+            [&](int e, double v) {
+                if (active) U[e] = v;
+            });
     } else {
         double *Pm = pmom + c * n;
-        double s = 0.0;
+        double s = 0.0;  // (hmc_kernel's momentum draw, hmc/_hmc.py:137-141)
         for (int e0 = l; e0 < n; e0 += 2 * LPR) {
             const int e1 = e0 + LPR;
             double z0 = 0.0, z1 = 0.0;
             philox_normal_pair<LPR>(e0, (uint32_t)c, (uint32_t)it, kPurposeSampleMomentum, a.key0, a.key1, z0, z1);
             const double v0 = X[e0];
-            if (id.active) U[e0] = v0, Pm[e0] = z0;
+            if (active) U[e0] = v0, Pm[e0] = z0;
             s += z0 * z0;
             if (e1 < n) {
                 const double v1 = X[e1];
-                if (id.active) U[e1] = v1, Pm[e1] = z1;
+                if (active) U[e1] = v1, Pm[e1] = z1;
                 s += z1 * z1;
             }
         }
         const double K0 = 0.5 * row_sum<LPR>(s);
-        if (id.active && l == 0) k0[c] = K0;
+        if (active && l == 0) k0[c] = K0;
     }
 }
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kernel(const sx_sample_args a, int64_t it,
-                                                                                  double *__restrict__ prop,
-                                                                                  double *__restrict__ pmom,
-                                                                                  double *__restrict__ k0) {
-    sample_propose<LPR, false>(a, sx_sample_adapt{}, it, prop, pmom, k0);
-}
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_adapt_kernel(const sx_sample_args a,
-                                                                                        const sx_sample_adapt ad, int64_t it,
-                                                                                        double *__restrict__ prop,
-                                                                                        double *__restrict__ pmom,
-                                                                                        double *__restrict__ k0) {
-    sample_propose<LPR, true>(a, ad, it, prop, pmom, k0);
-}
 
-// one momentum step with the gradient G, and the position step behind it when `move`
+// one momentum step with the gradient G, and the position step behind it when `move` (hmc/_hmc.py:143-155)
 template <int LPR, bool ADAPT>
-__device__ __forceinline__ void sample_leap(const sx_sample_args &a, const sx_sample_adapt &ad, double coef, int move,
-                                            double *__restrict__ q, double *__restrict__ pmom, const double *__restrict__ G) {
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_kernel(const sx_sample_args a, double coef, int move,
+                                                                               double *__restrict__ q,
+                                                                               double *__restrict__ pmom,
+                                                                               const double *__restrict__ G,
+                                                                               const AdaptArg<ADAPT> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
     double *Q = q + c * n, *Pm = pmom + c * n;
     const double *g = G + c * n;
-    double scale = 1.0;
-    if constexpr (ADAPT)
-        if (ad.warmup > 0) scale = ad.scale[c];
+    const double scale = chain_scale<ADAPT>(ad, c);
     for (int e = l; e < n; e += LPR) {
         const double gv = g[e];
-        double st = a.step[e];
-        if constexpr (ADAPT) st = scale * st;
+        const double st = chain_step<ADAPT>(a, scale, e);
         const double p = Pm[e] - (coef * st) * gv;
         const double qn = Q[e] + st * p;
         if (id.active) {
@@ -141,21 +121,6 @@ __device__ __forceinline__ void sample_leap(const sx_sample_args &a, const sx_sa
             if (move) Q[e] = qn;
         }
     }
-}
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_kernel(const sx_sample_args a, double coef, int move,
-                                                                               double *__restrict__ q,
-                                                                               double *__restrict__ pmom,
-                                                                               const double *__restrict__ G) {
-    sample_leap<LPR, false>(a, sx_sample_adapt{}, coef, move, q, pmom, G);
-}
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_adapt_kernel(const sx_sample_args a,
-                                                                                     const sx_sample_adapt ad, double coef,
-                                                                                     int move, double *__restrict__ q,
-                                                                                     double *__restrict__ pmom,
-                                                                                     const double *__restrict__ G) {
-    sample_leap<LPR, true>(a, ad, coef, move, q, pmom, G);
 }
 
 // The rows numerical_gradient evaluates for axes [axis0, axis0 + naxes): the reference moves component i of its two copies by
@@ -202,24 +167,24 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_fd_gradient_k
 
 // the decision on sample `it` with the proposal's value fprop (C), and the chain's bookkeeping
 template <int LPR, bool ADAPT>
-__device__ __forceinline__ void sample_decide(const sx_sample_args &a, const sx_sample_adapt &ad, int64_t it,
-                                              const double *__restrict__ prop, const double *__restrict__ fprop,
-                                              const double *__restrict__ pmom, const double *__restrict__ k0) {
+__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel(const sx_sample_args a, int64_t it,
+                                                                                 const double *__restrict__ prop,
+                                                                                 const double *__restrict__ fprop,
+                                                                                 const double *__restrict__ pmom,
+                                                                                 const double *__restrict__ k0,
+                                                                                 const AdaptArg<ADAPT> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
     const double *U = prop + c * n;
-    double *X = a.cur + c * n;
     const bool mcmc = a.method == SX_SAMPLE_MCMC;
     const double fU = fprop[c];
     ChainState st;
     AdaptState as;
-    bool accept = false, xbest_changed = false;
+    Decision r{true, true, 0.0};  // (sample 0: cur = the initial point)
     if (it == 0) {
         st.start(fU);
         if constexpr (ADAPT) as.start();
-        accept = true;  // (cur = the initial point)
-        xbest_changed = true;
     } else {
         st.load(a, c);
         if constexpr (ADAPT) as.load(ad, c);
@@ -232,58 +197,20 @@ __device__ __forceinline__ void sample_decide(const sx_sample_args &a, const sx_
             K = 0.5 * row_sum<LPR>(s);
         }
         const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
-        double dstat = 0.0;
-        if (feasible) {
-            st.nfeas += 1;
-            const double logu = philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
-            const double d = mcmc ? st.fcur - fU : ((st.fcur - fU) + K0) - K;
-            accept = (d < 0.0 ? d : 0.0) > logu;  // Python's min(0.0, d): a NaN d gives 0.0
-            dstat = d;
-        }
-        if (accept) {
-            bool acc_best, arg_best;
-            st.accept(fU, it, acc_best, arg_best);
-            xbest_changed = mcmc ? acc_best : arg_best;
-        }
-        if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, dstat, st.nacc);
+        r = chain_decide(st, a, (uint32_t)c, it, mcmc, feasible, mcmc ? st.fcur - fU : ((st.fcur - fU) + K0) - K, fU);
+        if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, r.dstat, st.nacc);
     }
     if (!id.active) return;
     bool record = a.xall != nullptr;
     int64_t row = c * a.maxiter + it;
     if constexpr (ADAPT) {
-        int64_t r = 0;
-        record = record && adapt_record(ad, it, r);
-        row = c * ad.rec_rows + r;
+        int64_t rec = 0;
+        record = record && adapt_record(ad, it, rec);
+        row = c * ad.rec_rows + rec;
     }
-    double *all = record ? a.xall + row * n : nullptr;
-    for (int e = l; e < n; e += LPR) {
-        const double v = accept ? U[e] : X[e];
-        if (accept) X[e] = v;
-        if (all != nullptr) st_stream(all + e, v);
-        if (xbest_changed) a.xbest[c * n + e] = v;
-    }
-    if (l == 0) {
-        if (all != nullptr) st_stream(a.funall + row, st.fcur);
-        st.store(a, c);
-        if constexpr (ADAPT) as.store(ad, c);
-    }
-}
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel(const sx_sample_args a, int64_t it,
-                                                                                 const double *__restrict__ prop,
-                                                                                 const double *__restrict__ fprop,
-                                                                                 const double *__restrict__ pmom,
-                                                                                 const double *__restrict__ k0) {
-    sample_decide<LPR, false>(a, sx_sample_adapt{}, it, prop, fprop, pmom, k0);
-}
-template <int LPR>
-__global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_adapt_kernel(const sx_sample_args a,
-                                                                                       const sx_sample_adapt ad, int64_t it,
-                                                                                       const double *__restrict__ prop,
-                                                                                       const double *__restrict__ fprop,
-                                                                                       const double *__restrict__ pmom,
-                                                                                       const double *__restrict__ k0) {
-    sample_decide<LPR, true>(a, ad, it, prop, fprop, pmom, k0);
+    commit_sample<LPR>(a, st, c, l, U, r.accept, r.xbest_changed, record, row);
+    if constexpr (ADAPT)
+        if (l == 0) as.store(ad, c);
 }
 
 // Parallel tempering (sx_sample_temper.hip) around a caller's objective: the decision of replica c = ladder * K + rung with
@@ -300,41 +227,19 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_temper
     const int64_t c = id.rowc;
     const int rung = (int)(c % K);
     const double *U = prop + c * n;
-    double *X = a.cur + c * n;
     const double fU = fprop[c];
     ChainState st;
-    bool accept = false, xbest_changed = false;
+    Decision r{true, true, 0.0};  // (sample 0: cur = the initial point)
     if (it == 0) {
         st.start(fU);
-        accept = true;  // (cur = the initial point)
-        xbest_changed = true;
     } else {
         st.load(a, c);
         const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
-        if (feasible) {
-            st.nfeas += 1;
-            const double logu = philox_log_accept((uint32_t)c, (uint32_t)it, a.key0, a.key1);
-            const double d = (st.fcur - fU) * beta[rung];
-            accept = (d < 0.0 ? d : 0.0) > logu;
-        }
-        if (accept) {
-            bool arg_best;
-            st.accept(fU, it, xbest_changed, arg_best);
-        }
+        r = chain_decide(st, a, (uint32_t)c, it, true, feasible, (st.fcur - fU) * beta[rung], fU);
     }
     if (!id.active) return;
-    const int64_t ladder = c / K;
-    double *all = (a.xall != nullptr && record && rung == 0) ? a.xall + (ladder * a.maxiter + it) * n : nullptr;
-    for (int e = l; e < n; e += LPR) {
-        const double v = accept ? U[e] : X[e];
-        if (accept) X[e] = v;
-        if (all != nullptr) st_stream(all + e, v);
-        if (xbest_changed) a.xbest[c * n + e] = v;
-    }
-    if (l == 0) {
-        if (all != nullptr) st_stream(a.funall + ladder * a.maxiter + it, st.fcur);
-        st.store(a, c);
-    }
+    commit_sample<LPR>(a, st, c, l, U, r.accept, r.xbest_changed, a.xall != nullptr && record && rung == 0,
+                       (c / K) * a.maxiter + it);
 }
 
 // Exchange event j after sample `it`: one row group per PAIR (pairs = ladders * pairs_per_ladder; the lower rungs are
@@ -380,128 +285,111 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_swap_kernel(c
     if (all != nullptr && l == 0) st_stream(a.funall + ladder * a.maxiter + it, swap ? fu : fl);
 }
 
-// sx_sample_run's conditions on the arguments these kernels read
-int check_args(const sx_sample_args *a, int64_t it) {
-    SX_REQUIRE(a != nullptr, "sx_sample (unfused): null args");
-    SX_REQUIRE(a->cur && a->fcur && a->facc && a->fmin && a->xbest && a->iacc && a->imin && a->nacc && a->nfeas,
-               "sx_sample (unfused): null state pointer");
-    SX_REQUIRE(a->lower && a->upper && a->step, "sx_sample (unfused): bounds / step missing");
-    SX_REQUIRE(a->C >= 1 && a->C < (int64_t)1 << 31 && a->n >= 1 && a->n <= kWideFrom, "sx_sample (unfused): bad shape");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || a->method == SX_SAMPLE_HMC, "sx_sample (unfused): unknown method");
-    SX_REQUIRE(a->jac == SX_JAC_FINITE_DIFF || a->jac == SX_JAC_ANALYTIC, "sx_sample (unfused): unknown gradient mode");
-    SX_REQUIRE(a->rng == SX_RNG_PHILOX, "sx_sample (unfused): the draws are made in the kernels (SX_RNG_PHILOX)");
-    SX_REQUIRE(a->maxiter >= 1 && a->maxiter < (int64_t)1 << 31 && it >= 0 && it < a->maxiter,
-               "sx_sample (unfused): sample outside [0, maxiter)");
-    SX_REQUIRE((a->xall == nullptr) == (a->funall == nullptr), "sx_sample (unfused): xall and funall go together");
-    SX_REQUIRE(a->x0 == nullptr || a->x0_stride == 0 || a->x0_stride >= a->n, "sx_sample (unfused): bad x0 stride");
-    if (a->method == SX_SAMPLE_MCMC)
-        SX_REQUIRE(a->k >= 1 && a->k <= a->n, "sx_sample (unfused): block length outside [1, n]");
-    else
-        SX_REQUIRE(a->nleap >= 1, "sx_sample (unfused): bad nleap");
-    return 0;
+// What every entry point `who` does first, for its sample `it` (the entry points without one pass 0): sx_sample_run's
+// conditions on the arguments these kernels read, and those on `ad` for the adapting / thinning forms
+template <bool ADAPT = false>
+int check_entry(const char *who, const sx_sample_args *a, int64_t it, const sx_sample_adapt *ad = nullptr) {
+    return (check_sample_args(who, a, it, 1, false, false) || (ADAPT && check_adapt(a, ad))) ? -1 : 0;
+}
+
+// each plain entry point and its *_adapt form: one body
+template <bool ADAPT>
+int propose(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop, double *pmom,
+            double *k0, void *stream) {
+    if (check_entry<ADAPT>(who, a, it, ad)) return -1;
+    SX_SAMPLE_REQUIRE(prop != nullptr, "null proposal array");
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "hmc needs pmom and k0");
+    const Geometry g = chain_geometry(a->C, a->n);
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_propose_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
+                                          pmom, k0, adapt_arg<ADAPT>(ad)))
+    return -1;
+}
+
+template <bool ADAPT>
+int leap(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q, double *pmom,
+         const double *G, void *stream) {
+    if (check_entry<ADAPT>(who, a, 0, ad)) return -1;
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_HMC && q && pmom && G, "hmc with q, pmom and G");
+    const Geometry g = chain_geometry(a->C, a->n);
+    Enqueue sink((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return sink.kernel(sample_leap_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, coef, move, q,
+                                             pmom, G, adapt_arg<ADAPT>(ad)))
+    return -1;
+}
+
+template <bool ADAPT>
+int decide(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
+           const double *fprop, const double *pmom, const double *k0, void *stream) {
+    if (check_entry<ADAPT>(who, a, it, ad)) return -1;
+    SX_SAMPLE_REQUIRE(prop && fprop, "null proposal / value array");
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "hmc needs pmom and k0");
+    const Geometry g = chain_geometry(a->C, a->n);
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_decide_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
+                                          fprop, pmom, k0, adapt_arg<ADAPT>(ad)))
+    return -1;
 }
 
 }  // namespace
 
 extern "C" int sx_sample_propose(const sx_sample_args *a, int64_t it, double *prop, double *pmom, double *k0, void *stream) {
-    if (check_args(a, it)) return -1;
-    SX_REQUIRE(prop != nullptr, "sx_sample_propose: null proposal array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_propose: hmc needs pmom and k0");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_propose_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, it, prop, pmom, k0))
-    SX_LAUNCH_CHECK();
-    return 0;
+    return propose<false>("sx_sample_propose", a, nullptr, it, prop, pmom, k0, stream);
 }
-
 extern "C" int sx_sample_leap(const sx_sample_args *a, double coef, int move, double *q, double *pmom, const double *G,
                               void *stream) {
-    if (check_args(a, 0)) return -1;
-    SX_REQUIRE(a->method == SX_SAMPLE_HMC && q && pmom && G, "sx_sample_leap: hmc with q, pmom and G");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_leap_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, coef, move, q, pmom, G))
-    SX_LAUNCH_CHECK();
-    return 0;
+    return leap<false>("sx_sample_leap", a, nullptr, coef, move, q, pmom, G, stream);
+}
+extern "C" int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
+                                const double *pmom, const double *k0, void *stream) {
+    return decide<false>("sx_sample_decide", a, nullptr, it, prop, fprop, pmom, k0, stream);
+}
+
+// The adapting / thinning forms (sx_sample_adapt)
+extern "C" int sx_sample_propose_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop,
+                                       double *pmom, double *k0, void *stream) {
+    return propose<true>("sx_sample_propose_adapt", a, ad, it, prop, pmom, k0, stream);
+}
+extern "C" int sx_sample_leap_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q,
+                                    double *pmom, const double *G, void *stream) {
+    return leap<true>("sx_sample_leap_adapt", a, ad, coef, move, q, pmom, G, stream);
+}
+extern "C" int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
+                                      const double *fprop, const double *pmom, const double *k0, void *stream) {
+    return decide<true>("sx_sample_decide_adapt", a, ad, it, prop, fprop, pmom, k0, stream);
 }
 
 extern "C" int sx_sample_fd_rows(const sx_sample_args *a, const double *q, int axis0, int naxes, double *W, void *stream) {
-    if (check_args(a, 0)) return -1;
-    SX_REQUIRE(a->method == SX_SAMPLE_HMC && q && W && a->fd_step != 0.0, "sx_sample_fd_rows: hmc with q, W and a step");
-    SX_REQUIRE(axis0 >= 0 && naxes >= 1 && axis0 <= a->n - naxes, "sx_sample_fd_rows: axes outside [0, n)");
+    const char *who = "sx_sample_fd_rows";
+    if (check_entry(who, a, 0)) return -1;
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_HMC && q && W && a->fd_step != 0.0, "hmc with q, W and a step");
+    SX_SAMPLE_REQUIRE(axis0 >= 0 && naxes >= 1 && axis0 <= a->n - naxes, "axes outside [0, n)");
     const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_fd_rows_kernel<LPR>), dim3(g.blocks, (unsigned)naxes), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, q, axis0, W))
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue sink((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return sink.kernel(sample_fd_rows_kernel<LPR>, dim3(g.blocks, (unsigned)naxes), dim3(g.threads), 0, *a, q,
+                                             axis0, W))
+    return -1;
 }
 
 extern "C" int sx_sample_fd_gradient(const sx_sample_args *a, const double *fW, int axis0, int naxes, double *G,
                                      void *stream) {
-    if (check_args(a, 0)) return -1;
-    SX_REQUIRE(a->method == SX_SAMPLE_HMC && fW && G && a->fd_step != 0.0, "sx_sample_fd_gradient: hmc with fW, G and a step");
-    SX_REQUIRE(axis0 >= 0 && naxes >= 1 && axis0 <= a->n - naxes, "sx_sample_fd_gradient: axes outside [0, n)");
+    const char *who = "sx_sample_fd_gradient";
+    if (check_entry(who, a, 0)) return -1;
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_HMC && fW && G && a->fd_step != 0.0, "hmc with fW, G and a step");
+    SX_SAMPLE_REQUIRE(axis0 >= 0 && naxes >= 1 && axis0 <= a->n - naxes, "axes outside [0, n)");
     const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_fd_gradient_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, fW, axis0, naxes, G))
-    SX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
-                                const double *pmom, const double *k0, void *stream) {
-    if (check_args(a, it)) return -1;
-    SX_REQUIRE(prop && fprop, "sx_sample_decide: null proposal / value array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_decide: hmc needs pmom and k0");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_decide_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, it, prop, fprop, pmom, k0))
-    SX_LAUNCH_CHECK();
-    return 0;
-}
-
-// The adapting / thinning forms (sx_sample_adapt): the checks of the plain entry points, then check_adapt
-extern "C" int sx_sample_propose_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop,
-                                       double *pmom, double *k0, void *stream) {
-    if (check_args(a, it) || check_adapt(a, ad)) return -1;
-    SX_REQUIRE(prop != nullptr, "sx_sample_propose_adapt: null proposal array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_propose_adapt: hmc needs pmom and k0");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_propose_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, *ad, it, prop, pmom, k0))
-    SX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sx_sample_leap_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q,
-                                    double *pmom, const double *G, void *stream) {
-    if (check_args(a, 0) || check_adapt(a, ad)) return -1;
-    SX_REQUIRE(a->method == SX_SAMPLE_HMC && q && pmom && G, "sx_sample_leap_adapt: hmc with q, pmom and G");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_leap_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, *ad, coef, move, q, pmom, G))
-    SX_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
-                                      const double *fprop, const double *pmom, const double *k0, void *stream) {
-    if (check_args(a, it) || check_adapt(a, ad)) return -1;
-    SX_REQUIRE(prop && fprop, "sx_sample_decide_adapt: null proposal / value array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "sx_sample_decide_adapt: hmc needs pmom and k0");
-    const Geometry g = chain_geometry(a->C, a->n);
-    SX_DISPATCH_LPR(a->n, hipLaunchKernelGGL((sample_decide_adapt_kernel<LPR>), dim3(g.blocks), dim3(g.threads), 0,
-                                             (hipStream_t)stream, *a, *ad, it, prop, fprop, pmom, k0))
-    SX_LAUNCH_CHECK();
-    return 0;
+    Enqueue q((hipStream_t)stream);
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_fd_gradient_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0, *a, fW, axis0, naxes, G))
+    return -1;
 }
 
 extern "C" int sx_sample_decide_tempered(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
                                          const double *beta, int K, int record, void *stream) {
-    if (check_args(a, it)) return -1;
-    SX_REQUIRE(prop && fprop && beta, "sx_sample_decide_tempered: null proposal / value / beta array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC, "sx_sample_decide_tempered: mcmc only");
-    SX_REQUIRE(K >= 2 && a->C % K == 0, "sx_sample_decide_tempered: C is ladders x K replicas, K >= 2");
+    const char *who = "sx_sample_decide_tempered";
+    if (check_entry(who, a, it)) return -1;
+    SX_SAMPLE_REQUIRE(prop && fprop && beta, "null proposal / value / beta array");
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC, "mcmc only");
+    SX_SAMPLE_REQUIRE(K >= 2 && a->C % K == 0, "C is ladders x K replicas, K >= 2");
     const Geometry g = chain_geometry(a->C, a->n);
     Enqueue q((hipStream_t)stream);
     SX_DISPATCH_LPR(a->n, return q.kernel(sample_decide_tempered_kernel<LPR>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
@@ -511,10 +399,11 @@ extern "C" int sx_sample_decide_tempered(const sx_sample_args *a, int64_t it, co
 
 extern "C" int sx_sample_swap(const sx_sample_args *a, int64_t it, int64_t j, const double *beta, int K, int64_t *nswap,
                               void *stream) {
-    if (check_args(a, it)) return -1;
-    SX_REQUIRE(beta && nswap, "sx_sample_swap: null beta / nswap array");
-    SX_REQUIRE(a->method == SX_SAMPLE_MCMC, "sx_sample_swap: mcmc only");
-    SX_REQUIRE(K >= 2 && a->C % K == 0 && it >= 1 && j >= 1, "sx_sample_swap: C is ladders x K replicas, K >= 2; it, j >= 1");
+    const char *who = "sx_sample_swap";
+    if (check_entry(who, a, it)) return -1;
+    SX_SAMPLE_REQUIRE(beta && nswap, "null beta / nswap array");
+    SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC, "mcmc only");
+    SX_SAMPLE_REQUIRE(K >= 2 && a->C % K == 0 && it >= 1 && j >= 1, "C is ladders x K replicas, K >= 2; it, j >= 1");
     const int first = (int)((j + 1) & 1);
     const int pairs_per_ladder = (K - first) / 2;
     if (pairs_per_ladder == 0) return 0;  // (K = 2 at an even event: nobody has a partner)

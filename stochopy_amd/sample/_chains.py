@@ -217,42 +217,54 @@ class _Unfused:
         self.adapting("sx_sample_decide", i, ptr(self.prop), ptr(f), ptr(self.pmom), ptr(self.k0))
 
 
+def chain_args(ctx, s, rows, chains=None, x0=None, draws=None):
+    """``(dev, a)``: the per-chain device arrays of a run of ``s`` (a Setup, or anything with its fields) and the
+    SxSampleArgs that points at them, on the current stream.  ``rows``: the rows of xall / funall to keep per chain on the
+    device, None for neither.  ``chains``: the length of the per-chain arrays when it is not ``s.chains`` -- the replicas of a
+    tempered run, whose xall / funall stay one per ladder.  ``x0``: the initial point(s) as the kernels read them, (ndim,)
+    for all or one row per chain.  ``draws``: (normals, logu) of the numpy-legacy stream, which the kernels then read
+    (SX_RNG_HOST) instead of making their own."""
+    t = _device.torch()
+    Cn, n = s.chains if chains is None else chains, s.ndim
+    dev = {name: ctx.empty((Cn, n)) for name in ("cur", "xbest")}
+    dev.update({name: ctx.empty((Cn,)) for name in ("fcur", "facc", "fmin")})
+    dev.update({name: ctx.empty((Cn,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
+    if rows is not None:
+        dev["xall"] = ctx.empty((s.chains, rows, n))
+        dev["funall"] = ctx.empty((s.chains, rows))
+    for name in ("lower", "upper", "step"):
+        dev[name] = ctx.upload(getattr(s, name))
+    if x0 is not None:
+        dev["x0"] = ctx.upload(x0)
+    if draws is not None:
+        dev["normals"], dev["logu"] = (ctx.upload(d) for d in draws)
+    a = _lib.SxSampleArgs()
+    for name in ("cur", "fcur", "facc", "fmin", "xbest", "iacc", "imin", "nacc", "nfeas", "x0", "xall", "funall",
+                 "lower", "upper", "step", "normals", "logu"):
+        setattr(a, name, _device.ptr(dev.get(name)))
+    a.C, a.maxiter = Cn, s.maxiter
+    a.x0_stride = n if (x0 is not None and x0.ndim == 2) else 0
+    a.n, a.fun_id, a.method = n, s.fun_id, s.method
+    a.rng = _lib.SX_RNG_HOST if draws is not None else _lib.SX_RNG_PHILOX
+    a.reject, a.k, a.nleap, a.jac, a.fd_step = int(s.reject), s.k, s.nleap, s.jac, s.fd_step
+    a.key0, a.key1 = s.key
+    return dev, a
+
+
 def run(s):
     L = _lib.lib()
     legacy = s.rng == "numpy-legacy"
     Cn, n, m = s.chains, s.ndim, s.maxiter
-    stream = None
+    stream = draws = None
     x0 = s.x0
     if legacy:
-        stream, x0, normals, logu = _legacy_draws(s)
+        stream, x0, *draws = _legacy_draws(s)
     ctx = _device.Context()
     t = _device.torch()
     with t.cuda.stream(ctx.stream):
-        dev = {name: ctx.empty((Cn, n)) for name in ("cur", "xbest")}
-        dev.update({name: ctx.empty((Cn,)) for name in ("fcur", "facc", "fmin")})
-        dev.update({name: ctx.empty((Cn,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
         on_device_all = s.return_all and s.callback is None
         rows = m if s.adapt is None else s.adapt.rows  # (burn / thin: the rows of xall / funall per chain)
-        if on_device_all:
-            dev["xall"] = ctx.empty((Cn, rows, n))
-            dev["funall"] = ctx.empty((Cn, rows))
-        for name in ("lower", "upper", "step"):
-            dev[name] = ctx.upload(getattr(s, name))
-        if x0 is not None:
-            dev["x0"] = ctx.upload(x0)
-        if legacy:
-            dev["normals"] = ctx.upload(normals)
-            dev["logu"] = ctx.upload(logu)
-        a = _lib.SxSampleArgs()
-        for name in ("cur", "fcur", "facc", "fmin", "xbest", "iacc", "imin", "nacc", "nfeas", "x0", "xall", "funall",
-                     "lower", "upper", "step", "normals", "logu"):
-            setattr(a, name, _device.ptr(dev.get(name)))
-        a.C, a.maxiter = Cn, m
-        a.x0_stride = n if (x0 is not None and x0.ndim == 2) else 0
-        a.n, a.fun_id, a.method = n, s.fun_id, s.method
-        a.rng = _lib.SX_RNG_HOST if legacy else _lib.SX_RNG_PHILOX
-        a.reject, a.k, a.nleap, a.jac, a.fd_step = int(s.reject), s.k, s.nleap, s.jac, s.fd_step
-        a.key0, a.key1 = s.key
+        dev, a = chain_args(ctx, s, rows if on_device_all else None, x0=x0, draws=draws)
         ad = None
         if s.adapt is not None:
             ad = _lib.SxSampleAdapt()

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _device, _lib
+from ._chains import chain_args
 from ._helpers import SampleResult
 
 
@@ -64,28 +65,11 @@ def run(s):
     ctx = _device.Context()
     t = _device.torch()
     with t.cuda.stream(ctx.stream):
-        dev = {name: ctx.empty((R, n)) for name in ("cur", "xbest")}
-        dev.update({name: ctx.empty((R,)) for name in ("fcur", "facc", "fmin")})
-        dev.update({name: ctx.empty((R,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
-        nswap = ctx.zeros((R,), dtype=t.int64)
         on_device_all = s.return_all and s.callback is None
-        if on_device_all:
-            dev["xall"] = ctx.empty((Cn, m, n))
-            dev["funall"] = ctx.empty((Cn, m))
-        for name in ("lower", "upper", "step"):
-            dev[name] = ctx.upload(getattr(s, name))
+        # (s is an mcmc Setup: method mcmc; nleap, jac and fd_step, which the kernels do not read, at their defaults)
+        dev, a = chain_args(ctx, s, m if on_device_all else None, chains=R, x0=x0)
+        nswap = ctx.zeros((R,), dtype=t.int64)
         dbeta = ctx.upload(beta)
-        if x0 is not None:
-            dev["x0"] = ctx.upload(x0)
-        a = _lib.SxSampleArgs()
-        for name in ("cur", "fcur", "facc", "fmin", "xbest", "iacc", "imin", "nacc", "nfeas", "x0", "xall", "funall",
-                     "lower", "upper", "step"):
-            setattr(a, name, _device.ptr(dev.get(name)))
-        a.C, a.maxiter = R, m
-        a.x0_stride = n if (x0 is not None and x0.ndim == 2) else 0
-        a.n, a.fun_id, a.method, a.rng = n, s.fun_id, _lib.SX_SAMPLE_MCMC, _lib.SX_RNG_PHILOX
-        a.reject, a.k, a.nleap, a.jac, a.fd_step = int(s.reject), s.k, 1, _lib.SX_JAC_FINITE_DIFF, s.fd_step
-        a.key0, a.key1 = s.key
         ptr = _device.ptr
 
         def cold(name):

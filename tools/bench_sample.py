@@ -35,6 +35,7 @@ import json
 import os
 import sys
 import time
+import types
 
 import numpy as np
 
@@ -56,26 +57,18 @@ class DeviceRun:
     """The buffers and arguments of one configuration, launched as stochopy_amd.sample does without a callback."""
 
     def __init__(self, ctx, method, ndim, chains, o, seed=3):
-        from stochopy_amd import _device, _lib
+        from stochopy_amd import _lib
+        from stochopy_amd.sample._chains import chain_args
 
-        t = _device.torch()
         self.ctx, self.L, self.m = ctx, ctx.L, o["maxiter"]
         lower, upper = np.full(ndim, -5.12), np.full(ndim, 5.12)
-        self.dev = dev = {name: ctx.empty((chains, ndim)) for name in ("cur", "xbest")}
-        dev.update({name: ctx.empty((chains,)) for name in ("fcur", "facc", "fmin")})
-        dev.update({name: ctx.empty((chains,), dtype=t.int64) for name in ("iacc", "imin", "nacc", "nfeas")})
-        if o["return_all"]:
-            dev["xall"], dev["funall"] = ctx.empty((chains, self.m, ndim)), ctx.empty((chains, self.m))
-        dev["lower"], dev["upper"] = ctx.upload(lower), ctx.upload(upper)
-        dev["step"] = ctx.upload(np.full(ndim, o["stepsize"]) * (0.5 * (upper - lower)))
-        self.a = a = _lib.SxSampleArgs()
-        for name in dev:
-            setattr(a, name, _device.ptr(dev[name]))
-        a.C, a.maxiter, a.x0_stride, a.n = chains, self.m, 0, ndim
-        a.fun_id, a.method = _lib.FUN_IDS["rosenbrock"], (_lib.SX_SAMPLE_MCMC if method == "mcmc" else _lib.SX_SAMPLE_HMC)
-        a.rng, a.reject, a.k, a.nleap = _lib.SX_RNG_PHILOX, 0, max(1, int(o.get("perc", 1.0) * ndim)), o.get("nleap", 1)
-        a.jac = _lib.SX_JAC_ANALYTIC if o.get("jac") == "analytic" else _lib.SX_JAC_FINITE_DIFF
-        a.fd_step, a.key0, a.key1 = 1.0e-4, seed, 0
+        s = types.SimpleNamespace(  # the fields of sample._chains.Setup that chain_args reads
+            chains=chains, ndim=ndim, maxiter=self.m, lower=lower, upper=upper,
+            step=np.full(ndim, o["stepsize"]) * (0.5 * (upper - lower)), fun_id=_lib.FUN_IDS["rosenbrock"],
+            method=_lib.SX_SAMPLE_MCMC if method == "mcmc" else _lib.SX_SAMPLE_HMC, reject=False,
+            k=max(1, int(o.get("perc", 1.0) * ndim)), nleap=o.get("nleap", 1),
+            jac=_lib.SX_JAC_ANALYTIC if o.get("jac") == "analytic" else _lib.SX_JAC_FINITE_DIFF, fd_step=1.0e-4, key=(seed, 0))
+        self.dev, self.a = chain_args(ctx, s, self.m if o["return_all"] else None)
         self.samples = chains * self.m
         self.stored = chains * self.m * (ndim + 1) * 8 if o["return_all"] else 0
 
