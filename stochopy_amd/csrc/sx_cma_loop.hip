@@ -17,6 +17,7 @@
 // do nothing.
 #include <algorithm>
 
+#include "sx_cma_rules.hpp"
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 
@@ -350,8 +351,9 @@ __global__ __launch_bounds__(kPathThreads) void cma_paths_kernel(const sx_cma_ar
     }
 }
 
-// D = sqrt(eigenvalues) when a decomposition was made, then the ten ordered stopping rules (:360-434), the
-// result copy when one fires, and the publication of the new step size / generation counter.  One workgroup.
+// D = sqrt(eigenvalues) when a decomposition was made, then the ten ordered stopping rules (:360-434; cma_stop_status of
+// sx_cma_rules.hpp from the facts gathered here), the result copy when one fires, and the publication of the new step size /
+// generation counter.  One workgroup.
 __global__ __launch_bounds__(kPathThreads) void cma_stop_kernel(const sx_cma_args a, int64_t gen, int did_eigh) {
     __shared__ double red14[kPathThreads / 64][14];
     __shared__ double fin14[14];
@@ -373,43 +375,17 @@ __global__ __launch_bounds__(kPathThreads) void cma_stop_kernel(const sx_cma_arg
         dx2 += d * d;
         if (!(fabs(0.1 * sigma * a.B[(int64_t)e * n + axis] * dax) < 1.0e-10)) fail4 += 1.0;
         const double sd = sqrt(a.C[(int64_t)e * n + e]);
-        if (0.2 * sigma * sd < 1.0e-10) any5 += 1.0;
+        rule_facts_add(sd, sigma, a.insigma, a.pc[e], any5, any8, nan_sd, sdmax, fail10);
         const double de = a.D[e];
         dmax = fmax(dmax, de), dmin = fmin(dmin, de);  // (numpy's max/min propagate NaN; rule 6 then compares False either way)
         if (de != de) nan_d += 1.0;
-        if (sigma * sd > 1.0e3 * a.insigma) any8 += 1.0;
-        if (sd != sd) nan_sd += 1.0;
-        sdmax = fmax(sdmax, sd);
-        if (!(sigma * fabs(a.pc[e]) < 1.0e-11 * a.insigma)) fail10 += 1.0;
     }
-    // histories: window [gen-ilim, gen] of the zero-initialised best-fitness array (entry `gen` is not written yet),
-    // and the whole array joined with this generation's fitness values
-    double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
-    if (gen >= a.ilim) {
-        const int64_t hi = gen + 1 < a.maxiter ? gen + 1 : a.maxiter;
-        for (int64_t k = gen - a.ilim + tid; k < hi; k += kPathThreads) {
-            const double v = a.besthist[k];
-            wmax = fmax(wmax, v), wmin = fmin(wmin, v);
-        }
-    }
-    for (int64_t k = tid; k < a.maxiter; k += kPathThreads) {
-        const double v = a.besthist[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
-    for (int64_t k = tid; k < a.P; k += kPathThreads) {
-        const double v = a.fit[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
+    double wmax, wmin, jmax, jmin;
+    history_extremes<int64_t>(a.besthist, a.fit, gen, a.ilim, a.maxiter, a.P, tid, kPathThreads, wmax, wmin, jmax, jmin);
     // one combined reduction: 7 sums, 4 maxima, 3 minima
     double vs[14] = {dx2, fail4, any5, any8, fail10, nan_sd, nan_d, dmax, sdmax, wmax, jmax, dmin, wmin, jmin};
-#pragma unroll
-    for (int q = 0; q < 14; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(vs[q], off, kWave);
-            vs[q] = q < 7 ? vs[q] + o : (q < 11 ? fmax(vs[q], o) : fmin(vs[q], o));
-        }
-    }
+    const int kind[14] = {0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2};
+    wave_reduce_many(vs, kind);
     if ((tid & 63) == 0) {
 #pragma unroll
         for (int q = 0; q < 14; ++q) red14[tid >> 6][q] = vs[q];
@@ -433,27 +409,8 @@ __global__ __launch_bounds__(kPathThreads) void cma_stop_kernel(const sx_cma_arg
     for (int q = 0; q < 14; ++q) vs[q] = fin14[q];
     dx2 = vs[0], fail4 = vs[1], any5 = vs[2], any8 = vs[3], fail10 = vs[4], nan_sd = vs[5], nan_d = vs[6];
     dmax = vs[7], sdmax = vs[8], wmax = vs[9], jmax = vs[10], dmin = vs[11], wmin = vs[12], jmin = vs[13];
-    int status = SX_STATUS_NONE;
-    if (gen >= a.maxiter)
-        status = -1;
-    else if (sqrt(dx2) <= a.xtol && fbest < a.ftol)
-        status = 0;
-    else if (fbest <= a.ftol)
-        status = 1;
-    else if (fail4 == 0.0)
-        status = -2;
-    else if (any5 > 0.0)
-        status = -3;
-    else if (nan_d == 0.0 && dmax > 1.0e7 * dmin)
-        status = -4;
-    else if (gen >= a.ilim && wmax - wmin < 1.0e-10)
-        status = -5;
-    else if (any8 > 0.0)
-        status = -6;
-    else if (gen > 2 && jmax - jmin < 1.0e-12)
-        status = -7;
-    else if (fail10 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * a.insigma)
-        status = -8;
+    const int status = cma_stop_status<int64_t>(gen, a.maxiter, a.ilim, a.xtol, a.ftol, sigma, a.insigma, dx2, fbest, fail4, any5, nan_d,
+                                               dmax, dmin, wmax, wmin, any8, jmax, jmin, fail10, nan_sd, sdmax);
     if (status != SX_STATUS_NONE) {  // the caller's result: best candidate of THIS generation, un-standardised (:345-353)
         const double *row = a.arx + state->best_row * (int64_t)n;
         for (int e = tid; e < n; e += kPathThreads) {

@@ -26,13 +26,22 @@
 // A generation mirrors sx_cmaes_generation (sx_cma_loop.hip) with barriers where it has launches: the same normals (the
 // device function behind sx_cmaes_normals, counter (slot, row, gen, kPurposeCmaNormal), row = the row within the run), the
 // same objective (row_objective<FUN, 16> on the un-standardised row), key_less for the ranking, the expressions of
-// cma_paths_kernel / cma_cov_finish_kernel / cma_stop_kernel, the sweeps of eigh_small_kernel (sx_eigh_small.hpp: rotation,
+// cma_paths_kernel / cma_cov_finish_kernel, the stopping rules as sx_cma_rules.hpp states them for cma_stop_kernel (spelled
+// out here: see LEFT APART below), the sweeps of eigh_small_kernel (sx_eigh_small.hpp: rotation,
 // jacobi_sweep, block_sum; cold start, tol = max(1e-14, n 2^-53), kRunsSweeps sweeps at the most) and the finish of
 // eigh_colstats / eigh_rank / eigh_write_kernel.  Sums whose order the single run leaves to its launch geometry (dot
 // products with B, the recombination, the covariance contraction) are summed here in index order, which depends on n and mu
 // only: run r agrees with the single run of its key to rounding, not bit for bit, and with the oracle as the single run does.
 // The loop that drives the sweeps (measure, compare, sweep) is the one statement sequence that exists twice
 // (eigh_small_kernel keeps its own: as a shared function it compiled to other instructions there).
+// LEFT APART from sx_cma_rules.hpp, on measurement (profiles/cma_rules_refactor_resources.txt and
+// cma_rules_refactor_ab.txt): this kernel keeps its own spelling of history_extremes, rule_facts_add and cma_stop_status,
+// and the ranking by wave votes stands here and in vd_runs_kernel (sx_vd_runs.hip); it compiles to the instructions it had
+// before that header existed.  It sits at 128 VGPRs with 568 ... 812 bytes of scratch per lane: history_extremes,
+// cma_stop_status or the votes as a shared function -- each alone, together, as values, by reference, with early returns --
+// made 1 ... 5 of the 14 instantiations GAIN 4 ... 36 bytes of scratch; rule_facts_add alone cost no register, gave the
+// same bytes, and ran 0.11 ... 0.16 % below the parent's own spread at n = 32 with 4096 and 16 384 runs, twice.
+// A correction to a rule in the header is owed here as well.
 // What return_all would need (the argmin row of cma_rank_kernel) has no reader here and is not computed: the result is the
 // first row of the ranking, as in cma_stop_kernel.
 //
@@ -44,9 +53,6 @@
 #include "sx_rowops.hpp"
 #include "sx_runs.hpp"
 
-namespace sx {
-int make_plan_arg(int fun_id, int n, PlanArg *out);
-}
 using namespace sx;
 
 namespace {
@@ -176,7 +182,7 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
         __syncthreads();
 
         // ---- order = argsort(fit) (:272; NaN last, lower index first on ties): cma_rank_kernel's votes, a wavefront
-        //      ranks four rows against 64-key chunks
+        //      ranks four rows against 64-key chunks (the same loop as in vd_runs_kernel: see the header comment)
         for (int g = wave; 4 * g < P; g += NW) {
             const int i0 = 4 * g;
             double fi[4];
@@ -315,10 +321,10 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
             __syncthreads();
         }
 
-        // ---- the ten ordered stopping rules (:360-434), cma_stop_kernel's expressions.  "all(x < t)" is carried as the
-        //      count of elements that FAIL (NaN fails, as in numpy).  Histories: window [gen-ilim, gen] of the
-        //      zero-initialised best-fitness array (entry `gen` is not written yet), and the whole array joined with this
-        //      generation's fitness values: every wavefront folds its share, the totals are folded by everybody
+        // ---- the ten ordered stopping rules (:360-434): history_extremes and, below, rule_facts_add and cma_stop_status of
+        //      sx_cma_rules.hpp, spelled out (see the header comment).  "all(x < t)" is carried as the count of elements that
+        //      FAIL (NaN fails, as in numpy); entry `gen` of the zero-initialised history is read before it is written.
+        //      Every wavefront folds its share of the histories, the totals are folded by everybody
         sigma = sigma_next;
         {
             double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
@@ -384,7 +390,7 @@ __global__ __launch_bounds__(runs_threads<M2>(), SX_CMA_RUNS_WAVES) void cma_run
             dmax = fmax(dmax, __shfl_xor(dmax, off, kWave)), sdmax = fmax(sdmax, __shfl_xor(sdmax, off, kWave));
             dmin = fmin(dmin, __shfl_xor(dmin, off, kWave));
         }
-        int status = SX_STATUS_NONE;
+        int status = SX_STATUS_NONE;  // cma_stop_status, statement for statement
         if (gen >= maxiter)
             status = -1;
         else if (sqrt(dx2) <= a.xtol && fbest < a.ftol)
@@ -432,26 +438,15 @@ extern "C" int64_t sx_cma_runs_lds_bytes(int64_t P, int n) {
     return bytes <= kLdsLimit ? bytes : -1;
 }
 
-extern "C" int64_t sx_cma_runs_workspace_bytes(int64_t R, int64_t maxiter) {
-    if (R < 1 || maxiter < 1 || maxiter >= (int64_t)1 << 31 || R >= (int64_t)1 << 31) return -1;
-    return R * maxiter * (int64_t)sizeof(double);
-}
+extern "C" int64_t sx_cma_runs_workspace_bytes(int64_t R, int64_t maxiter) { return sigma_runs_workspace_bytes(R, maxiter); }
 
 extern "C" int sx_cma_runs_sweep_launch(const sx_cma_runs_args *a, const double *sigma, void *stream) {
     SX_REQUIRE(a != nullptr, "sx_cma_runs_launch: null args");
-    SX_REQUIRE(a->keys && a->xmean0 && a->xm && a->xstd && a->w && a->work && a->xs && a->funs && a->nits && a->statuses,
-               "sx_cma_runs_launch: null device pointer");
-    SX_REQUIRE(a->R >= 1 && a->R < (int64_t)1 << 31 && a->P >= 2 && a->n >= 1 && a->n <= kRunsMaxDim && a->mu >= 1 &&
-                   a->mu <= a->P && a->maxiter >= 1 && a->ilim >= 0,
-               "sx_cma_runs_launch: bad shape");
-    SX_REQUIRE(a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT, "sx_cma_runs_launch: unknown objective");
-    SX_REQUIRE(a->sigma > 0.0, "sx_cma_runs_launch: sigma must be positive");
     const int64_t lds = sx_cma_runs_lds_bytes(a->P, a->n);
-    SX_REQUIRE(lds > 0, "sx_cma_runs_launch: the run's model and candidates do not fit one workgroup's LDS");
     PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
-    SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_cma_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
+    if (int rc = prepare_sigma_runs("sx_cma_runs_launch", a, 1, kRunsMaxDim, lds,
+                                    "sx_cma_runs_launch: the run's model and candidates do not fit one workgroup's LDS", &plan, stream))
+        return rc;
     const SigmaSweep sweep = {sigma};
     if (runs_m2(a->n) == 16) {
         SX_DISPATCH_FUN(a->fun_id,

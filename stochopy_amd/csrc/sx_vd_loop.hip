@@ -9,9 +9,11 @@
 //   stochopy/optimize/vdcma/_vdcma.py:331-378  moments of the path, natural gradient (:447-460), update of v and d
 //   stochopy/optimize/cmaes/_cmaes.py:360-434  converge as vdcma calls it (no B, D: rules -2 and -4 drop out)
 // The model update is O(n): one workgroup of 512 threads holds the vectors in registers (n <= 4096), with a workgroup
-// reduction wherever the reference takes a dot product, a norm, a max or a min; the scalars in between are computed by
-// every thread from the reduced values.  Expressions keep the reference's association order (no FMA contraction in
+// reduction (reduce_many of sx_cma_rules.hpp) wherever the reference takes a dot product, a norm, a max or a min; the scalars
+// in between are computed by every thread from the reduced values.  The stopping rules, their facts and the histories are
+// that header's too (cma_stop_status with rules -2 and -4 off, rule_facts_add, history_extremes), here and in the wide chain.  Expressions keep the reference's association order (no FMA contraction in
 // this build).
+#include "sx_cma_rules.hpp"
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 #include "sx_wide.hpp"
@@ -36,44 +38,9 @@ constexpr int kVdThreads = 512;
 constexpr int kVdWaves = kVdThreads / 64;
 constexpr int kVdPer = 8;  // elements per thread: n <= 4096, everything in registers (227 VGPRs; 1024 threads x 4 spill 154)
 
-// K values at once (kind[q]: 0 sum, 1 max, 2 min): one pair of barriers for all of them; every thread gets the results
-template <int K, int NW = kVdWaves>
-__device__ void reduce_many(double (&v)[K], const int (&kind)[K], double (*red)[K]) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(v[q], off, kWave);
-            v[q] = kind[q] == 0 ? v[q] + o : (kind[q] == 1 ? fmax(v[q], o) : fmin(v[q], o));
-        }
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) red[threadIdx.x >> 6][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        double r = red[0][q];
-        for (int wv = 1; wv < NW; ++wv) {
-            const double o = red[wv][q];
-            r = kind[q] == 0 ? r + o : (kind[q] == 1 ? fmax(r, o) : fmin(r, o));
-        }
-        v[q] = r;
-    }
-}
-
-__device__ double reduce_sum(double x, double (*red)[1]) {
-    double v[1] = {x};
-    const int k[1] = {0};
-    reduce_many<1>(v, k, red);
-    return v[0];
-}
-
 // the mean-shift injection (:241-247): dy = |z| / sqrt(mnorm) * dx with mnorm = |dx/d|^2 - (dx/d . v)^2 / (1 + |v|^2)
 __global__ __launch_bounds__(kVdThreads) void vd_inject_kernel(const sx_vd_args a) {
-    __shared__ double red3[kVdWaves][3];
+    __shared__ double red3[kVdWaves * 3];
     const sx_cma_state *state = (const sx_cma_state *)a.state;
     if (state->done || state->reserved[3] == 0.0) return;
     const int n = a.n, tid = threadIdx.x;
@@ -94,7 +61,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_inject_kernel(const sx_vd_args 
     }
     double v3[3] = {s1, s2, s3};
     const int k3[3] = {0, 0, 0};
-    reduce_many<3>(v3, k3, red3);
+    reduce_many<3, kVdWaves>(v3, k3, red3);
     const double mnorm = v3[0] - v3[1] * v3[1] / (1.0 + nv2);
     const double fac = sqrt(v3[2]) / sqrt(mnorm);
 #pragma unroll
@@ -105,10 +72,10 @@ __global__ __launch_bounds__(kVdThreads) void vd_inject_kernel(const sx_vd_args 
 }
 
 __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args a, int64_t gen) {
-    __shared__ double red1[kVdWaves][1];
-    __shared__ double red2[kVdWaves][2];
-    __shared__ double red4[kVdWaves][4];
-    __shared__ double red10[kVdWaves][10];
+    __shared__ double red1[kVdWaves * 1];
+    __shared__ double red2[kVdWaves * 2];
+    __shared__ double red4[kVdWaves * 4];
+    __shared__ double red10[kVdWaves * 10];
     sx_cma_state *state = (sx_cma_state *)a.state;
     if (state->done) return;
     const int n = a.n, tid = threadIdx.x;
@@ -165,7 +132,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
     {
         double v4[4] = {pos0, pos1, dx2, vmax};
         const int k4[4] = {0, 0, 0, 1};
-        reduce_many<4>(v4, k4, red4);
+        reduce_many<4, kVdWaves>(v4, k4, red4);
         pos0 = v4[0], pos1 = v4[1], dx2 = v4[2], vmax = v4[3];
     }
     // ---- step size from the rank gap (:298-306) ----
@@ -218,7 +185,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
     {
         double v2[2] = {t, svi};
         const int k2[2] = {0, 0};
-        reduce_many<2>(v2, k2, red2);
+        reduce_many<2, kVdWaves>(v2, k2, red2);
         t = v2[0], svi = v2[1];
     }
     // ---- moments of the path (:340-345, :428-444), p and q (:348-352), vn . q ----
@@ -237,7 +204,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
             vq += v1[u] * q[u];
         }
     }
-    vq = reduce_sum(vq, red1);
+    vq = reduce_one<kVdWaves>(vq, 0, red1);
     const bool learn = a.cmu + a.c1 > 0.0;
     // ---- natural gradient (:447-460) ----
     double ri = 0.0;
@@ -252,7 +219,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
             p[u] = 0.0;
         }
     }
-    ri = reduce_sum(ri, red1);
+    ri = reduce_one<kVdWaves>(ri, 0, red1);
     double svn = 0.0;
 #pragma unroll
     for (int u = 0; u < kVdPer; ++u) {  // s overwrites r
@@ -263,7 +230,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
             svn += p[u] * vnn;
         }
     }
-    svn = reduce_sum(svn, red1);
+    svn = reduce_one<kVdWaves>(svn, 0, red1);
     double g2 = 0.0, mind = __builtin_inf();
 #pragma unroll
     for (int u = 0; u < kVdPer; ++u) {  // ngv overwrites q, ngd overwrites s
@@ -280,7 +247,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
     {
         double v2[2] = {g2, mind};
         const int k2[2] = {0, 2};
-        reduce_many<2>(v2, k2, red2);
+        reduce_many<2, kVdWaves>(v2, k2, red2);
         g2 = v2[0], mind = v2[1];
     }
     double up = 1.0;
@@ -301,33 +268,15 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
             a.vvec[e] = vv[u];
             a.dvec[e] = dv[u] + up * p[u];
             nv2n += vv[u] * vv[u];
-            if (0.2 * sigma * sd < 1.0e-10) any3 += 1.0;
-            if (sigma * sd > 1.0e3 * a.insigma) any6 += 1.0;
-            if (sd != sd) nan_sd += 1.0;
-            sdmax = fmax(sdmax, sd);
-            if (!(sigma * fabs(pc0[u]) < 1.0e-11 * a.insigma)) fail8 += 1.0;
+            rule_facts_add(sd, sigma, a.insigma, pc0[u], any3, any6, nan_sd, sdmax, fail8);
         }
     }
-    double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
-    if (gen >= a.ilim) {
-        const int64_t hi = gen + 1 < a.maxiter ? gen + 1 : a.maxiter;
-        for (int64_t k = gen - a.ilim + tid; k < hi; k += kVdThreads) {
-            const double v = a.besthist[k];
-            wmax = fmax(wmax, v), wmin = fmin(wmin, v);
-        }
-    }
-    for (int64_t k = tid; k < a.maxiter; k += kVdThreads) {
-        const double v = a.besthist[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
-    for (int64_t k = tid; k < a.P; k += kVdThreads) {
-        const double v = a.fit[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
+    double wmax, wmin, jmax, jmin;
+    history_extremes<int64_t>(a.besthist, a.fit, gen, a.ilim, a.maxiter, a.P, tid, kVdThreads, wmax, wmin, jmax, jmin);
     {
         double v10[10] = {nv2n, any3, any6, fail8, nan_sd, sdmax, wmax, jmax, wmin, jmin};
         const int k10[10] = {0, 0, 0, 0, 0, 1, 1, 1, 2, 2};
-        reduce_many<10>(v10, k10, red10);
+        reduce_many<10, kVdWaves>(v10, k10, red10);
         nv2n = v10[0], any3 = v10[1], any6 = v10[2], fail8 = v10[3], nan_sd = v10[4], sdmax = v10[5], wmax = v10[6];
         jmax = v10[7], wmin = v10[8], jmin = v10[9];
     }
@@ -337,23 +286,8 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
         const int e = tid + u * kVdThreads;
         if (e < n) a.vn[e] = vv[u] / nvn;
     }
-    int status = SX_STATUS_NONE;
-    if (gen >= a.maxiter)
-        status = -1;
-    else if (sqrt(dx2) <= a.xtol && fbest < a.ftol)
-        status = 0;
-    else if (fbest <= a.ftol)
-        status = 1;
-    else if (any3 > 0.0)
-        status = -3;
-    else if (gen >= a.ilim && wmax - wmin < 1.0e-10)
-        status = -5;
-    else if (any6 > 0.0)
-        status = -6;
-    else if (gen > 2 && jmax - jmin < 1.0e-12)
-        status = -7;
-    else if (fail8 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * a.insigma)
-        status = -8;
+    const int status = cma_stop_status<int64_t>(gen, a.maxiter, a.ilim, a.xtol, a.ftol, sigma, a.insigma, dx2, fbest, kRuleOff, any3,
+                                               kRuleOff, 0.0, 0.0, wmax, wmin, any6, jmax, jmin, fail8, nan_sd, sdmax);
     if (status != SX_STATUS_NONE) {  // the caller's result: best candidate of THIS generation, un-standardised
         const double *row = a.arx + state->best_row * (int64_t)n;
         for (int e = tid; e < n; e += kVdThreads) {
@@ -433,7 +367,7 @@ __device__ __forceinline__ void vw_st(double *p, double v) {
 }
 // the K partial sums of phase `ph` over all workgroups (kind: 0 sum, 1 max, 2 min), in every thread
 template <int K>
-__device__ __forceinline__ void vw_collect(const VwScratch &w, int ph, const int (&kind)[K], double (&v)[K], double (*red)[K]) {
+__device__ __forceinline__ void vw_collect(const VwScratch &w, int ph, const int (&kind)[K], double (&v)[K], double *red) {
     const double *p = w.part + ((int64_t)ph * kVwMaxBlocks + threadIdx.x) * kVwSlots;
 #pragma unroll
     for (int q = 0; q < K; ++q)
@@ -441,7 +375,7 @@ __device__ __forceinline__ void vw_collect(const VwScratch &w, int ph, const int
     reduce_many<K, kVwWaves>(v, kind, red);
 }
 template <int K>
-__device__ __forceinline__ void vw_leave(const VwScratch &w, int ph, const int (&kind)[K], double (&v)[K], double (*red)[K]) {
+__device__ __forceinline__ void vw_leave(const VwScratch &w, int ph, const int (&kind)[K], double (&v)[K], double *red) {
     reduce_many<K, kVwWaves>(v, kind, red);
     if (threadIdx.x == 0) {
         double *p = w.part + ((int64_t)ph * kVwMaxBlocks + blockIdx.x) * kVwSlots;
@@ -485,7 +419,7 @@ __device__ __forceinline__ double vw_avec(const VwModel &m, double vnn) { return
 
 // the mean-shift injection (:241-247) with the injection's normals ("row P" of the generation) drawn in place
 __global__ __launch_bounds__(kVwThreads) void vw_inject_norms_kernel(const sx_vd_args a, int64_t gen, double *base) {
-    __shared__ double red3[kVwWaves][3];
+    __shared__ double red3[kVwWaves * 3];
     const sx_cma_state *state = (const sx_cma_state *)a.state;
     if (blockIdx.x == 0 && threadIdx.x < kVwSyncWords) vw_sync(a)[threadIdx.x] = 0u;  // (vw_chain_kernel's barrier words)
     if (state->done || state->reserved[3] == 0.0) return;
@@ -516,7 +450,7 @@ __global__ __launch_bounds__(kVwThreads) void vw_inject_norms_kernel(const sx_vd
     vw_leave<3>(w, 7, k3, v3, red3);
 }
 __global__ __launch_bounds__(kVwThreads) void vw_inject_apply_kernel(const sx_vd_args a, double *base) {
-    __shared__ double red3[kVwWaves][3];
+    __shared__ double red3[kVwWaves * 3];
     const sx_cma_state *state = (const sx_cma_state *)a.state;
     if (state->done || state->reserved[3] == 0.0) return;
     const int n = a.n;
@@ -531,7 +465,7 @@ __global__ __launch_bounds__(kVwThreads) void vw_inject_apply_kernel(const sx_vd
 
 // phase A: the injected pair in the ranking (:299-300), mean shift (:292-294)
 __device__ __forceinline__ void vw_a_phase(const sx_vd_args &a, double *base) {
-    __shared__ double red4[kVwWaves][4];
+    __shared__ double red4[kVwWaves * 4];
     const sx_cma_state *state = (const sx_cma_state *)a.state;
     const int n = a.n;
     const VwScratch w = vw_scratch(base, n);
@@ -567,8 +501,8 @@ __device__ __forceinline__ void vw_a_phase(const sx_vd_args &a, double *base) {
 
 // phase B: evolution path (:309-314), t = y . vn, sum of vn^2 invavnn
 __device__ __forceinline__ void vw_b_phase(const sx_vd_args &a, double *base) {
-    __shared__ double red4[kVwWaves][4];
-    __shared__ double red2[kVwWaves][2];
+    __shared__ double red4[kVwWaves * 4];
+    __shared__ double red2[kVwWaves * 2];
     const int n = a.n;
     const VwScratch w = vw_scratch(base, n);
     double v4[4];
@@ -600,7 +534,7 @@ __device__ __forceinline__ void vw_b_phase(const sx_vd_args &a, double *base) {
 
 // phases C .. F (:331-378, :428-460): which = 0 p, q and vn . q;  1 r and r . invavnn;  2 s and s . vn^2;  3 the steps ngv, ngd
 __device__ __forceinline__ void vw_cdef_phase(const sx_vd_args &a, double *base, const int which) {
-    __shared__ double red2[kVwWaves][2];
+    __shared__ double red2[kVwWaves * 2];
     __shared__ double s_scal[32];
     const int n = a.n;
     const VwScratch w = vw_scratch(base, n);
@@ -676,8 +610,8 @@ __device__ __forceinline__ void vw_cdef_phase(const sx_vd_args &a, double *base,
 
 // phase G: update of v and d (:371-378), the stopping rules' per-dimension counts, the best-fitness histories
 __device__ __forceinline__ void vw_g_phase(const sx_vd_args &a, int64_t gen, double *base) {
-    __shared__ double red2[kVwWaves][2];
-    __shared__ double red10[kVwWaves][10];
+    __shared__ double red2[kVwWaves * 2];
+    __shared__ double red10[kVwWaves * 10];
     __shared__ double s_scal[32];
     const int n = a.n;
     const VwScratch w = vw_scratch(base, n);
@@ -704,29 +638,11 @@ __device__ __forceinline__ void vw_g_phase(const sx_vd_args &a, int64_t gen, dou
         a.vvec[e] = vv;
         a.dvec[e] = dv + up * w.sp[e];
         nv2n += vv * vv;
-        if (0.2 * sigma * sd < 1.0e-10) any3 += 1.0;
-        if (sigma * sd > 1.0e3 * a.insigma) any6 += 1.0;
-        if (sd != sd) nan_sd += 1.0;
-        sdmax = fmax(sdmax, sd);
-        if (!(sigma * fabs(a.pc[e]) < 1.0e-11 * a.insigma)) fail8 += 1.0;
+        rule_facts_add(sd, sigma, a.insigma, a.pc[e], any3, any6, nan_sd, sdmax, fail8);
     }
-    double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
-    const int64_t g0 = blockIdx.x * kVwThreads + threadIdx.x, gs = (int64_t)gridDim.x * kVwThreads;
-    if (gen >= a.ilim) {
-        const int64_t hi = gen + 1 < a.maxiter ? gen + 1 : a.maxiter;
-        for (int64_t k = gen - a.ilim + g0; k < hi; k += gs) {
-            const double v = a.besthist[k];
-            wmax = fmax(wmax, v), wmin = fmin(wmin, v);
-        }
-    }
-    for (int64_t k = g0; k < a.maxiter; k += gs) {
-        const double v = a.besthist[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
-    for (int64_t k = g0; k < a.P; k += gs) {
-        const double v = a.fit[k];
-        jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-    }
+    double wmax, wmin, jmax, jmin;  // (the grid shares the histories as it shares the elements)
+    history_extremes<int64_t>(a.besthist, a.fit, gen, a.ilim, a.maxiter, a.P, blockIdx.x * kVwThreads + threadIdx.x,
+                              (int64_t)gridDim.x * kVwThreads, wmax, wmin, jmax, jmin);
     double v10[10] = {nv2n, any3, any6, fail8, nan_sd, sdmax, wmax, jmax, wmin, jmin};
     const int k10[10] = {0, 0, 0, 0, 0, 1, 1, 1, 2, 2};
     vw_leave<10>(w, 6, k10, v10, red10);
@@ -736,7 +652,7 @@ __device__ __forceinline__ void vw_g_phase(const sx_vd_args &a, int64_t gen, dou
 // (only workgroup 0 writes the state, at its very end, and nobody reads anything of it after phase A but `done` -- at the
 //  launch's start; raise_done: one launch for the whole chain, where every workgroup has read `done` long before)
 __device__ __forceinline__ void vw_h_phase(const sx_vd_args &a, int64_t gen, double *base, const bool raise_done) {
-    __shared__ double red10[kVwWaves][10];
+    __shared__ double red10[kVwWaves * 10];
     __shared__ double s_scal[32];
     sx_cma_state *state = (sx_cma_state *)a.state;
     const int n = a.n;
@@ -752,23 +668,8 @@ __device__ __forceinline__ void vw_h_phase(const sx_vd_args &a, int64_t gen, dou
     const double jmax = v10[7], wmin = v10[8], jmin = v10[9];
     const double nvn = sqrt(nv2n), sigma = m.sigma, fbest = m.fbest, dx2 = s_scal[kSDx2];
     VW_FOR_E a.vn[e] = a.vvec[e] / nvn;
-    int status = SX_STATUS_NONE;
-    if (gen >= a.maxiter)
-        status = -1;
-    else if (sqrt(dx2) <= a.xtol && fbest < a.ftol)
-        status = 0;
-    else if (fbest <= a.ftol)
-        status = 1;
-    else if (any3 > 0.0)
-        status = -3;
-    else if (gen >= a.ilim && wmax - wmin < 1.0e-10)
-        status = -5;
-    else if (any6 > 0.0)
-        status = -6;
-    else if (gen > 2 && jmax - jmin < 1.0e-12)
-        status = -7;
-    else if (fail8 == 0.0 && nan_sd == 0.0 && sigma * sdmax < 1.0e-11 * a.insigma)
-        status = -8;
+    const int status = cma_stop_status<int64_t>(gen, a.maxiter, a.ilim, a.xtol, a.ftol, sigma, a.insigma, dx2, fbest, kRuleOff, any3,
+                                               kRuleOff, 0.0, 0.0, wmax, wmin, any6, jmax, jmin, fail8, nan_sd, sdmax);
     if (status != SX_STATUS_NONE) {  // the caller's result: best candidate of THIS generation, un-standardised
         // (arx NULL: the candidates were not kept; the row is formed again from its step -- old mean, old sigma -- as they were)
         const int64_t br = (int64_t)s_scal[kSState + 6] * (int64_t)n;

@@ -36,32 +36,36 @@
 // the same normals (counter (slot, row within the run, gen, kPurposeCmaNormal), the injection's normals "row P"), the same
 // objective (row_objective<FUN, LPR> on the un-standardised row), key_less for the ranking, the expressions of
 // vd_inject_kernel / vd_sample_kernel / vd_moments_partial_kernel / vd_update_kernel in their association order
-// (-ffp-contract=off), the stopping rules of cma_stop_kernel as vd_update_kernel states them.
+// (-ffp-contract=off).  The reductions (reduce_many) and the stopping rules' facts (rule_facts_add, history_extremes) are
+// those of sx_cma_rules.hpp, shared with the single run.
+// LEFT APART, on measurement (profiles/cma_rules_refactor_resources.txt and
+// cma_rules_refactor_ab.txt): this kernel's own spelling of that header's cma_stop_status, and the ranking by wave votes,
+// which stands here and in cma_runs_kernel (sx_cma_runs.hip).  Every instantiation sits at 256 VGPRs or close.  With the
+// cascade as a call -- as values, by reference, with early returns -- vd_runs_kernel<5, 64> and <6, 64> went from 84 to 88
+// and 92 bytes of scratch per lane.  The votes as a shared function, alone, made three instantiations gain 4 and 8 bytes;
+// next to the other calls they cost no register and gave the same bytes, but n = 64 ran 0.2 ... 0.6 % below the parent's
+// own spread (without: inside).  A correction to a rule in the header, or to the votes there, is owed here as well.
 //
 // ORDERS OF SUMMATION.  They depend on n, P and mu only -- never on R, the grid or the neighbours:
 //   * over the elements of a row (t, t_k): lane l of the row's LPR lanes adds its elements in the order pass 1 visits them
 //     (pairs l, l + LPR, ...: cosine element, then sine element), the LPR sums meet in an xor butterfly (1, 2, ... LPR / 2);
 //   * over n (every dot product, norm, max, min of the update and the injection): thread t adds its elements t, t + NT, ...
 //     in order, a wavefront's 64 sums meet in an xor butterfly (32 ... 1), the wavefronts' totals are added in order
-//     (block_reduce); the injection's |z|^2 goes by pairs (cosine, then sine) the same way;
+//     (reduce_many); the injection's |z|^2 goes by pairs (cosine, then sine) the same way;
 //   * over the mu selected rows (wx, wy, p_mu, q_mu): slice g adds the rows k = g, g + G, ... in order, the G slices are
 //     added in order;
 //   * over P and the history (maxima, minima): order is immaterial.
 // The single run leaves these orders to its launch geometry (64 slices, four of sixteen), so run r agrees with the single
 // run of its key and with the oracle to rounding, not bit for bit; two launches that hold the same run agree bit for bit.
-// block_reduce is reduce_many of sx_vd_loop.hip with the wave count as found: a second copy (moving it to a header was not
-// checked against that file's device assembly).
 //
 // Nothing passes between workgroups: no grid barrier, no spin-wait, no atomics.  Every loop is bounded by maxiter, P, mu
 // or n.
+#include "sx_cma_rules.hpp"
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
 #include "sx_runs.hpp"
 
-namespace sx {
-int make_plan_arg(int fun_id, int n, PlanArg *out);
-}
 using namespace sx;
 
 namespace {
@@ -94,34 +98,6 @@ __host__ __device__ inline VrLayout vr_layout(int64_t P, int n) {
     L.U = L.pos + kVrPos;
     L.total = L.U + (stage > part ? stage : part);
     return L;
-}
-
-// K values at once (kind[q]: 0 sum, 1 max, 2 min): one pair of barriers for all of them; every thread gets the results
-template <int K, int NW>
-__device__ __forceinline__ void block_reduce(double (&v)[K], const int (&kind)[K], double *red) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(v[q], off, kWave);
-            v[q] = kind[q] == 0 ? v[q] + o : (kind[q] == 1 ? fmax(v[q], o) : fmin(v[q], o));
-        }
-    }
-    __syncthreads();  // (the previous reduction's readers are through)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) red[(threadIdx.x >> 6) * K + q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        double r = red[q];
-        for (int wv = 1; wv < NW; ++wv) {
-            const double o = red[wv * K + q];
-            r = kind[q] == 0 ? r + o : (kind[q] == 1 ? fmax(r, o) : fmin(r, o));
-        }
-        v[q] = r;
-    }
 }
 
 // minimum wavefronts per SIMD asked of the compiler: 2, i.e. up to 256 VGPRs.  The floor of 4 of the other runs kernels (128
@@ -164,7 +140,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
     {
         double r1[1] = {nv2};
         const int k1[1] = {0};
-        block_reduce<1, NW>(r1, k1, red);
+        reduce_many<1, NW>(r1, k1, red);
         nv2 = r1[0];
     }
     double nv = sqrt(nv2), vmax = -__builtin_inf();
@@ -176,7 +152,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
     {
         double r1[1] = {vmax};
         const int k1[1] = {1};
-        block_reduce<1, NW>(r1, k1, red);
+        reduce_many<1, NW>(r1, k1, red);
         vmax = r1[0];
     }
     // the run's own initial step size (a sweep's element `run`; rules -6 and -8 then compare with it), else the struct's
@@ -205,7 +181,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
             }
             double v3[3] = {s1, s2, s3};
             const int k3[3] = {0, 0, 0};
-            block_reduce<3, NW>(v3, k3, red);
+            reduce_many<3, NW>(v3, k3, red);
             const double mnorm = v3[0] - v3[1] * v3[1] / (1.0 + nv2);
             const double fac = sqrt(v3[2]) / sqrt(mnorm);
             for (int e = tid; e < n; e += NT) dy[e] = fac * dx[e];
@@ -249,7 +225,8 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         __syncthreads();
 
         // ---- order = argsort(fit) (:289; NaN last, lower index first on ties): cma_rank_kernel's votes, a wavefront ranks
-        //      four rows against 64-key chunks; where rows 0 and 1 (the injected pair) end up
+        //      four rows against 64-key chunks (the same loop as in cma_runs_kernel: see the header comment); where rows 0
+        //      and 1 (the injected pair) end up
         for (int g = wave; 4 * g < P; g += NW) {
             const int i0 = 4 * g;
             double fi[4];
@@ -368,7 +345,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
             }
             double v3[3] = {dx2, t, svi};
             const int k3[3] = {0, 0, 0};
-            block_reduce<3, NW>(v3, k3, red);
+            reduce_many<3, NW>(v3, k3, red);
             dx2 = v3[0], t = v3[1], svi = v3[2];
         }
         // ---- moments of the path (:340-345, :428-444), p and q (:348-352), vn . q
@@ -390,7 +367,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         {
             double r1[1] = {vq};
             const int k1[1] = {0};
-            block_reduce<1, NW>(r1, k1, red);
+            reduce_many<1, NW>(r1, k1, red);
             vq = r1[0];
         }
         // ---- natural gradient (:447-460)
@@ -404,7 +381,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         {
             double r1[1] = {ri};
             const int k1[1] = {0};
-            block_reduce<1, NW>(r1, k1, red);
+            reduce_many<1, NW>(r1, k1, red);
             ri = r1[0];
         }
         double svn = 0.0;
@@ -417,7 +394,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         {
             double r1[1] = {svn};
             const int k1[1] = {0};
-            block_reduce<1, NW>(r1, k1, red);
+            reduce_many<1, NW>(r1, k1, red);
             svn = r1[0];
         }
         double g2 = 0.0, mind = __builtin_inf();
@@ -435,7 +412,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         {
             double v2[2] = {g2, mind};
             const int k2[2] = {0, 2};
-            block_reduce<2, NW>(v2, k2, red);
+            reduce_many<2, NW>(v2, k2, red);
             g2 = v2[0], mind = v2[1];
         }
         double up = 1.0;
@@ -454,36 +431,18 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
             vv[e] = vnew;
             dv[e] = de + up * pp[e];
             nv2n += vnew * vnew;
-            if (0.2 * sigma * sd < 1.0e-10) any3 += 1.0;
-            if (sigma * sd > 1.0e3 * insigma) any6 += 1.0;
-            if (sd != sd) nan_sd += 1.0;
-            sdmax = fmax(sdmax, sd);
-            if (!(sigma * fabs(pc[e]) < 1.0e-11 * insigma)) fail8 += 1.0;
+            rule_facts_add(sd, sigma, insigma, pc[e], any3, any6, nan_sd, sdmax, fail8);
         }
-        double wmax = -__builtin_inf(), wmin = __builtin_inf(), jmax = -__builtin_inf(), jmin = __builtin_inf();
-        if (gen >= a.ilim) {
-            const int hi = gen + 1 < maxiter ? gen + 1 : maxiter;
-            for (int k = gen - a.ilim + tid; k < hi; k += NT) {
-                const double v = hist[k];
-                wmax = fmax(wmax, v), wmin = fmin(wmin, v);
-            }
-        }
-        for (int k = tid; k < maxiter; k += NT) {
-            const double v = hist[k];
-            jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-        }
-        for (int k = tid; k < P; k += NT) {
-            const double v = fit[k];
-            jmax = fmax(jmax, v), jmin = fmin(jmin, v);
-        }
+        double wmax, wmin, jmax, jmin;
+        history_extremes<int>(hist, fit, gen, a.ilim, maxiter, P, tid, NT, wmax, wmin, jmax, jmin);
         {
             double v10[10] = {nv2n, any3, any6, fail8, nan_sd, sdmax, wmax, jmax, wmin, jmin};
             const int k10[10] = {0, 0, 0, 0, 0, 1, 1, 1, 2, 2};
-            block_reduce<10, NW>(v10, k10, red);
+            reduce_many<10, NW>(v10, k10, red);
             nv2n = v10[0], any3 = v10[1], any6 = v10[2], fail8 = v10[3], nan_sd = v10[4], sdmax = v10[5], wmax = v10[6];
             jmax = v10[7], wmin = v10[8], jmin = v10[9];
         }
-        int status = SX_STATUS_NONE;
+        int status = SX_STATUS_NONE;  // cma_stop_status without rules -2 and -4, statement for statement (see the header comment)
         if (gen >= maxiter)
             status = -1;
         else if (sqrt(dx2) <= a.xtol && fbest < a.ftol)
@@ -528,7 +487,7 @@ __global__ __launch_bounds__(LPR == 64 ? 512 : 256, SX_VD_RUNS_WAVES) void vd_ru
         {
             double r1[1] = {vm};
             const int k1[1] = {1};
-            block_reduce<1, NW>(r1, k1, red);
+            reduce_many<1, NW>(r1, k1, red);
             vmax = r1[0];
         }
         __syncthreads();  // the update is complete (and pass 2's partial sums are dead): the next generation may write
@@ -545,27 +504,16 @@ extern "C" int64_t sx_vd_runs_lds_bytes(int64_t P, int n) {
     return bytes <= kLdsLimit ? bytes : -1;
 }
 
-extern "C" int64_t sx_vd_runs_workspace_bytes(int64_t R, int64_t maxiter) {
-    if (R < 1 || maxiter < 1 || maxiter >= (int64_t)1 << 31 || R >= (int64_t)1 << 31) return -1;
-    return R * maxiter * (int64_t)sizeof(double);
-}
+extern "C" int64_t sx_vd_runs_workspace_bytes(int64_t R, int64_t maxiter) { return sigma_runs_workspace_bytes(R, maxiter); }
 
 extern "C" int sx_vd_runs_sweep_launch(const sx_vd_runs_args *a, const double *sigma, void *stream) {
     SX_REQUIRE(a != nullptr, "sx_vd_runs_launch: null args");
-    SX_REQUIRE(a->keys && a->xmean0 && a->vvec0 && a->xm && a->xstd && a->w && a->work && a->xs && a->funs && a->nits &&
-                   a->statuses,
-               "sx_vd_runs_launch: null device pointer");
-    SX_REQUIRE(a->R >= 1 && a->R < (int64_t)1 << 31 && a->P >= 2 && a->n >= kVrMinDim && a->n <= kWideFrom && a->mu >= 1 &&
-                   a->mu <= a->P && a->maxiter >= 1 && a->ilim >= 0,
-               "sx_vd_runs_launch: bad shape");
-    SX_REQUIRE(a->fun_id >= 0 && a->fun_id < SX_FUN_COUNT, "sx_vd_runs_launch: unknown objective");
-    SX_REQUIRE(a->sigma > 0.0, "sx_vd_runs_launch: sigma must be positive");
     const int64_t lds = sx_vd_runs_lds_bytes(a->P, a->n);
-    SX_REQUIRE(lds > 0, "sx_vd_runs_launch: the run's model and staging rows do not fit one workgroup's LDS");
     PlanArg plan;
-    if (make_plan_arg(a->fun_id, a->n, &plan)) return -1;
-    // the zero-initialised histories (stopping rules -5 and -7 read entries that no generation has written yet)
-    SX_HIP(hipMemsetAsync(a->work, 0, (size_t)sx_vd_runs_workspace_bytes(a->R, a->maxiter), (hipStream_t)stream));
+    SX_REQUIRE(a->vvec0 != nullptr, "sx_vd_runs_launch: null device pointer");
+    if (int rc = prepare_sigma_runs("sx_vd_runs_launch", a, kVrMinDim, kWideFrom, lds,
+                                    "sx_vd_runs_launch: the run's model and staging rows do not fit one workgroup's LDS", &plan, stream))
+        return rc;
     const SigmaSweep sweep = {sigma};
     SX_DISPATCH_LPR(a->n, SX_DISPATCH_FUN(a->fun_id, return enqueue_runs(vd_runs_kernel<FUN, LPR>, *a, plan, sweep,
                                                                          vr_threads(a->n), lds, stream)))

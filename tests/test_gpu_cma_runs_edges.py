@@ -75,6 +75,7 @@ import oracle
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _cma_runs_abi as abi  # noqa: E402
+import _stop_rules  # noqa: E402
 from test_gpu_cma_runs import _same_run  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -268,18 +269,8 @@ RULES = {
 
 def admitted(objective, lower, upper, P, x0, opts, seeds, maxiter=3000):
     """[(seed, the oracle's run)] of the seeds the oracle ALONE is insensitive for, and the table of all of them."""
-    keep, table = [], []
-    for seed in seeds:
-        sigma = opts["sigma"]
-        ref, lo, hi = (oracle_run(objective, lower, upper, P, seed, x0=x0, maxiter=maxiter, **dict(opts, sigma=s))
-                       for s in (sigma, np.nextafter(sigma, 0.0), np.nextafter(sigma, np.inf)))
-        moved = max(abs(q.fun - ref.fun) / max(abs(ref.fun), 1e-300) for q in (lo, hi))
-        ok = all((q.nit, q.status) == (ref.nit, ref.status) for q in (lo, hi)) and moved < 1e-6
-        table.append("  seed %d oracle status %d nit %d | sigma - 1 ulp: %d %d | + 1 ulp: %d %d | fun moves %.2e | %s"
-                     % (seed, ref.status, ref.nit, lo.status, lo.nit, hi.status, hi.nit, moved, "admitted" if ok else "no"))
-        if ok:
-            keep.append((seed, ref))
-    return keep, table
+    return _stop_rules.admitted(lambda seed, s: oracle_run(objective, lower, upper, P, seed, x0=x0, maxiter=maxiter, **dict(opts, sigma=s)),
+                                opts["sigma"], seeds)
 
 
 @pytest.mark.parametrize("name", sorted(RULES))

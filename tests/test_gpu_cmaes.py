@@ -492,6 +492,49 @@ def test_cmaes_device_resident_loop_stop_rules(sa):
         assert got.status == ref.status and abs(got.nit - ref.nit) <= max(3, ref.nit // 50)
 
 
+# name: (rule, objective, lower, upper, x0, options, seeds tried): the recipes of tests/test_gpu_cma_runs_edges.py RULES and of
+# tests/test_gpu_cma_runs.py OTHER_RULES (rules -5 and -2 with the seeds chosen there), popsize 10, maxiter 3000
+def _single_run_rules():
+    from test_gpu_cma_runs import OTHER_RULES
+    from test_gpu_cma_runs_edges import RULES, box
+
+    cases = {name: (c[0],) + c[2:] for name, c in RULES.items() if name != "rule-4_sphere_n2_sigma0.3"}
+    for obj, n, P, sigma, seeds, rule, _ in OTHER_RULES:
+        cases["rule%d_%s_n%d" % (rule, obj, n)] = (rule, obj, *box(n), None, dict(sigma=sigma, ftol=-1.0), seeds)
+    return cases
+
+
+SINGLE_RUN_RULES = _single_run_rules()
+
+
+@pytest.mark.parametrize("name", sorted(SINGLE_RUN_RULES))
+def test_cmaes_device_resident_loop_ends_on_every_stop_rule_as_the_oracle_does(sa, name):
+    """The single run's stopping kernel (csrc/sx_cma_loop.hip cma_stop_kernel) on the rules the tests above do not pin: they
+    end on -1 and 1 exactly and on -5 with nit allowed to drift.  Here 0, -2, -4, -5, -6, -7, -8, one run per seed that the
+    oracle ALONE admits (tests/_stop_rules.py): nit, nfev and status exactly, fun within 1e-6, x within rtol 1e-5 / atol 1e-7,
+    as test_cmaes_device_resident_loop_vs_oracle compares.  Rule -3: no recipe with four admitted seeds exists
+    (tests/test_gpu_cma_runs_edges.py (d) has the search)."""
+    from test_gpu_cma_runs_edges import admitted
+
+    rule, objective, lower, upper, x0, opts, tried = SINGLE_RUN_RULES[name]
+    n, P = len(lower), 10
+    x0 = None if x0 is None else np.full(n, x0)
+    keep, table = admitted(objective, lower, upper, P, x0, opts, tried)
+    print(name, opts)
+    print("\n".join(table))
+    assert len(keep) >= 4 and any(ref.status == rule for _, ref in keep)
+    failures = []
+    for seed, ref in keep:
+        got = sa.optimize.minimize(getattr(sa.factory, objective), np.transpose([lower, upper]), x0=x0, method="cmaes",
+                                   options=dict(opts, popsize=P, seed=seed, maxiter=3000, backend="hip", rng="philox"))
+        rel = abs(got.fun - ref.fun) / max(abs(ref.fun), 1e-300)
+        print("  seed %d oracle nit %d status %d | device nit %d status %d rel fun %.3g" % (seed, ref.nit, ref.status, got.nit, got.status, rel))
+        if not ((got.nit, got.nfev, got.status) == (ref.nit, ref.nfev, ref.status) and np.isclose(got.fun, ref.fun, rtol=1e-6, atol=1e-300)
+                and np.allclose(got.x, ref.x, rtol=1e-5, atol=1e-7)):
+            failures.append(seed)
+    assert not failures, failures
+
+
 def test_cmaes_device_eigensolver_converges(sa):
     """eigh="device" in the cases where the eigenbasis is NOT determined (mu + 1 < n: a repeated eigenvalue, any
     basis of its eigenspace is valid) -- the run must still behave like CMA-ES: converge on the sphere with

@@ -16,6 +16,7 @@ import oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import _stop_rules  # noqa: E402
 import _vd_runs_abi as abi  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +124,23 @@ def test_rule_minus_3_against_the_oracle(sa):
     for r, ref in enumerate(refs):
         assert ref.status == -3 and 196 <= ref.nit <= 259
         _same_run(got, r, ref, P, counts=False)
+
+
+@pytest.mark.parametrize("rule", [-3, -6, -7, -8])
+def test_the_other_stop_rules_against_the_oracle(sa, rule):
+    """The rules TABLE does not reach (it has -1, 0, 1 and -5; -3 above without its counts), by the recipes of
+    tests/_stop_rules.py at n = 8, popsize 10: the seeds the oracle alone admits, in one launch, each held to its oracle run --
+    nit, nfev and status exactly, fun and x with this module's tolerances."""
+    n = 8
+    keep, table = _stop_rules.vd_admitted(rule, n)
+    obj, bounds, x0, opts = _stop_rules.vd_case(rule, n)
+    print("rule", rule, obj, opts)
+    print("\n".join(table))
+    got = _runs(sa, obj, n, [s for s, _ in keep], x0=x0, bounds=bounds, runs=len(keep), **opts)
+    print("  device nit", [int(v) for v in got.nits], "status", [int(v) for v in got.statuses])
+    print("  rel fun", ["%.3g" % (abs(got.funs[r] - ref.fun) / max(abs(ref.fun), 1e-300)) for r, (_, ref) in enumerate(keep)])
+    for r, (_, ref) in enumerate(keep):
+        _same_run(got, r, ref, opts["popsize"])
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,12 +1,17 @@
 """GPU parity: VD-CMA (device sampling + objective, host model update) vs the reference's golden vectors and
 the oracle (Philox draws)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 import oracle
 from conftest import GOLDEN, case_bounds, load_golden, unhex
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _stop_rules  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -221,6 +226,25 @@ def test_vdcma_device_loop_matches_oracle(sa, objective, n, P, maxiter, extra, m
     hl = sa.optimize.minimize(getattr(sa.factory, objective), bounds, method="vdcma",
                               options=dict(opts, backend="hip", rng="philox"), callback=lambda X, r: trace.append(r.fun))
     assert (hl.nit, hl.status) == (got.nit, got.status) and np.isclose(hl.fun, got.fun, rtol=1e-6, atol=1e-300)
+
+
+@pytest.mark.parametrize("rule", [0, 1, -3, -5, -6, -7, -8])
+def test_device_loop_ends_on_every_stop_rule_as_the_oracle_does(sa, rule):
+    """The single run's model update (csrc/sx_vd_loop.hip vd_update_kernel) on every rule VD-CMA can reach but -1, which the
+    tests above end on: the recipes of tests/_stop_rules.py at n = 8, popsize 10, one run per seed the oracle alone admits --
+    nit, nfev and status exactly, fun within 1e-6, x within rtol 1e-5 / atol 1e-7 (test_vdcma_device_loop_matches_oracle)."""
+    n = 8
+    keep, table = _stop_rules.vd_admitted(rule, n)
+    obj, bounds, x0, opts = _stop_rules.vd_case(rule, n)
+    print("rule", rule, obj, opts)
+    print("\n".join(table))
+    for seed, ref in keep:
+        got = sa.optimize.minimize(getattr(sa.factory, obj), bounds, x0=x0, method="vdcma",
+                                   options=dict(opts, seed=seed, backend="hip", rng="philox"))
+        print("  seed %d device nit %d status %d rel fun %.3g" % (seed, got.nit, got.status, abs(got.fun - ref.fun) / max(abs(ref.fun), 1e-300)))
+        assert (got.nit, got.nfev, got.status) == (ref.nit, ref.nfev, ref.status), seed
+        assert np.isclose(got.fun, ref.fun, rtol=1e-6, atol=1e-300), (seed, got.fun, ref.fun)
+        assert np.allclose(got.x, ref.x, rtol=1e-5, atol=1e-7), seed
 
 
 def test_vdcma_device_loop_small_shapes_and_short_runs(sa):

@@ -4,6 +4,7 @@ has no dimension limit (de/_de.py:208-218; vdcma/_vdcma.py:144-458 exists for lo
 and the unfused / sharded paths are compared with the oracle BIT FOR BIT (+, -, * objectives), VD-CMA within 1e-6 and
 against a vector captured from the reference at n = 8192 (tests/golden/vdcma_wide.json)."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +12,10 @@ import pytest
 import oracle
 from oracle.objectives import OBJECTIVES
 from conftest import GOLDEN, load_golden, unhex
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import _stop_rules  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -235,6 +240,27 @@ def test_wide_vdcma_device_loop_matches_oracle(sa, n, P, maxiter, monkeypatch):
     host = sa.optimize.minimize(sa.factory.rosenbrock, bounds, method="vdcma", options=dict(opts, backend="hip", rng="philox"),
                                 callback=lambda X, r: t_host.append(r.fun))
     assert np.allclose(t_host, t_ref, rtol=1e-6) and (host.nit, host.status) == (ref.nit, ref.status)
+
+
+@pytest.mark.parametrize("rule", [0, 1, -3, -7])
+def test_wide_vdcma_chain_ends_on_a_stop_rule_as_the_oracle_does(sa, rule):
+    """The wide chain's last phase (csrc/sx_vd_loop.hip vw_h_phase) on the rules a run of the first wide row, n = 4097,
+    popsize 10, reaches within a few generations -- the test above ends on -1 only: the recipes of tests/_stop_rules.py, one
+    run per seed the oracle alone admits; nit, nfev and status exactly, fun within 1e-6, x as above.
+    NOT covered at n = 4097: -6 (the recipe ends after 445 generations there, and its admission alone is 36 s of the oracle),
+    -5 (the window is 10 + 30 n / popsize = 12 301 generations) and -8 (sigma has to fall by eleven decades)."""
+    n = 4097
+    keep, table = _stop_rules.vd_admitted(rule, n)
+    obj, bounds, x0, opts = _stop_rules.vd_case(rule, n)
+    print("rule", rule, obj, opts)
+    print("\n".join(table))
+    for seed, ref in keep:
+        got = sa.optimize.minimize(getattr(sa.factory, obj), bounds, x0=x0, method="vdcma",
+                                   options=dict(opts, seed=seed, backend="hip", rng="philox"))
+        print("  seed %d device nit %d status %d rel fun %.3g" % (seed, got.nit, got.status, abs(got.fun - ref.fun) / max(abs(ref.fun), 1e-300)))
+        assert (got.nit, got.nfev, got.status) == (ref.nit, ref.nfev, ref.status), seed
+        assert np.isclose(got.fun, ref.fun, rtol=1e-6, atol=1e-300), (seed, got.fun, ref.fun)
+        assert np.allclose(got.x, ref.x, rtol=1e-5, atol=1e-6), seed
 
 
 _CHAIN_AB = r"""
