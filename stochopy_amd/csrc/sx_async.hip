@@ -151,6 +151,7 @@ __global__ __launch_bounds__(sweep_waves(FUN) * kWave) void de_async_kernel(cons
             if (t < k && d[t] >= i0 && d[t] < i) dep |= 1ull << (int)(d[t] - i0);
         const double *xi = X + i * ld;
         const int nq = (n + LPR - 1) / LPR;
+        // de_propose_row (sx_unfused.hpp) inside the ordered sweep, left apart: a correction made there is owed here
         for (int q0 = 0; q0 < nq; q0 += 4) {  // four row steps share one Philox call, as in the synchronous kernel
             double rr[4] = {2.0, 2.0, 2.0, 2.0};
             if (RNG == SX_RNG_PHILOX) {
@@ -289,6 +290,7 @@ __global__ __launch_bounds__(sweep_waves(FUN) * kWave) void pso_async_kernel(con
         const double *xr = a.X + i * ld, *vr = a.V + i * ld, *pb = a.pbest + i * ld;
         double beta = __builtin_huge_val();
         const int nq = (n + LPR - 1) / LPR;
+        // pso_move_row (sx_unfused.hpp) inside the ordered sweep, left apart: a correction made there is owed here
         for (int q0 = 0; q0 < nq; q0 += 2) {  // two row steps share one Philox call, as in the synchronous kernel
             U4 pw = {0u, 0u, 0u, 0u}, pv = {0u, 0u, 0u, 0u};  // 53-bit r1 / r2, the synchronous kernel's layout
             if (RNG == SX_RNG_PHILOX) {

@@ -13,6 +13,7 @@
 #include "sx_device.hpp"
 #include "sx_enqueue.hpp"
 #include "sx_rowops.hpp"
+#include "sx_unfused.hpp"
 #include "sx_wide.hpp"
 
 namespace sx {
@@ -802,71 +803,17 @@ __device__ __forceinline__ double final_dist2(const double *__restrict__ a, cons
     return acc;
 }
 
+// one workgroup, rows of up to kMaxDim elements (enqueue_finalize launches it for no others): best_step, sx_unfused.hpp
 __global__ __launch_bounds__(kFinalThreads) void select_finalize_kernel(
     const double *__restrict__ part_f, const int64_t *__restrict__ part_i, int64_t npart,
     const double *__restrict__ rows0, const double *__restrict__ rows1, int64_t ld, int n,
     double *__restrict__ gbest, sx_state *__restrict__ state, int maxiter, double xtol, double ftol) {
-    __shared__ double sf[kFinalThreads / kWave];
-    __shared__ int64_t si[kFinalThreads / kWave];
     double bf = __builtin_huge_val();
     int64_t bi = INT64_MAX;
     scan_records(part_f, part_i, npart, bf, bi);  // the loads do not depend on the state word: issue them first
     if (state->done) return;
-    const int64_t it = state->it + 1;  // the generation being finalised
-    block_argmin(bf, bi, sf, si);
-
-    // generation g lives in rows[g & 1] (double-buffered populations); rows0 == rows1 for in-place state
-    const double *src = ((it & 1) ? rows1 : rows0) + bi * ld;
-    // dx = ||xbest_prev - x[k]||_2 (np.linalg.norm, _common.py:135); all loads of a thread in flight together
-    constexpr int kPer = (kMaxDim + kFinalThreads - 1) / kFinalThreads;
-    double gv[kPer], sv[kPer];
-    double acc = 0.0;
-    if (n <= kMaxDim) {
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            const int e = threadIdx.x + u * kFinalThreads;
-            gv[u] = e < n ? gbest[e] : 0.0;
-            sv[u] = e < n ? src[e] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < kPer; ++u) {
-            if (threadIdx.x + u * kFinalThreads < n) {
-                const double d = gv[u] - sv[u];
-                acc += d * d;
-            }
-        }
-    } else {  // (longer rows take the three-launch form below: enqueue_finalize)
-        acc = final_dist2(gbest, src, n);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
-    if ((threadIdx.x & 63) == 0) sf[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    double ss = 0.0;
-    for (int k = 0; k < kFinalThreads / kWave; ++k) ss += sf[k];
-    const double dx = sqrt(ss);
-    if (n <= kMaxDim) {
-#pragma unroll
-        for (int u = 0; u < kPer; ++u)
-            if (threadIdx.x + u * kFinalThreads < n) gbest[threadIdx.x + u * kFinalThreads] = sv[u];
-    } else {
-        final_copy(gbest, src, n);
-    }
-    if (threadIdx.x == 0) {
-        int status = SX_STATUS_NONE;
-        if (dx <= xtol && bf <= ftol)
-            status = 0;
-        else if (bf <= ftol)
-            status = 1;
-        else if (it >= maxiter)
-            status = -1;
-        state->it = it;
-        state->gbidx = bi;
-        state->gfit = bf;
-        state->dx = dx;
-        state->status = status;
-        state->done = status != SX_STATUS_NONE;
-    }
+    best_step<(kMaxDim + kFinalThreads - 1) / kFinalThreads>(bf, bi, state->it + 1, rows0, rows1, ld, n, gbest, state, maxiter,
+                                                             xtol, ftol);
 }
 
 // The same step for rows of more than kMaxDim elements, in three launches: one workgroup walking a row of 65 536 elements twice
@@ -939,13 +886,7 @@ __global__ __launch_bounds__(kWave) void wide_finalize_state_kernel(const double
     for (int k = 0; k < nshare; ++k) ss += share[k];
     const double dx = sqrt(ss), bf = state->gfit;
     const int64_t it = state->it + 1;
-    int status = SX_STATUS_NONE;
-    if (dx <= xtol && bf <= ftol)
-        status = 0;
-    else if (bf <= ftol)
-        status = 1;
-    else if (it >= maxiter)
-        status = -1;
+    const int status = sync_status(dx, xtol, bf, ftol, it, maxiter);
     state->it = it;
     state->dx = dx;
     state->status = status;
@@ -1033,13 +974,7 @@ __global__ __launch_bounds__(kFinalThreads) void gather_finalize_kernel(const do
     final_copy(gbest, src, n);
     if (threadIdx.x == 0) {
         const int64_t it = state->it + 1;
-        int status = SX_STATUS_NONE;
-        if (dx <= xtol && bf <= ftol)
-            status = 0;
-        else if (bf <= ftol)
-            status = 1;
-        else if (it >= maxiter)
-            status = -1;
+        const int status = sync_status(dx, xtol, bf, ftol, it, maxiter);
         state->it = it;
         state->gbidx = bi;
         state->gfit = bf;

@@ -171,6 +171,7 @@ __device__ __forceinline__ void p2p_service(const sx_de_args &a, const sx_xchg_a
         if (wave != 0) return;
     }
     if (lane == 0) {
+        // sync_status (sx_rowops.hpp) without its dx rule (the host settles status 0), left apart: a correction made there is owed here
         int status = SX_STATUS_NONE;
         if (it >= 2) {
             if (gf <= a.ftol)
@@ -489,6 +490,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
             __syncthreads();
             bf = s_gf, bi = s_gi;
         }
+        // sync_status (sx_rowops.hpp) without its dx rule (the host settles status 0), left apart: a correction made there is owed here
         int status = SX_STATUS_NONE;
         if (it >= 2) {  // the reference does not test the initial population (de/_de.py:212-218)
             if (bf <= a.ftol)
@@ -518,6 +520,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, (NFIX != 0 && XM <= 1) ? 
 
     // ---- D. trial vector: mutation (de/_strategy.py, same association), crossover (de/_de.py:344 forced
     //      index OR r <= CR), Random repair (de/_constraints.py:21-26) -> LDS
+    //      de_propose_row (sx_unfused.hpp) fused with the objective, left apart: a correction made there is owed here
     const int nq = (n + LPR - 1) / LPR;
     // one batch per row -- NFIX, and (round 5) EVERY row of a short-row kernel, whatever its run-time length (lanes_per_row
     // gives rows of up to 64 / 128 elements 16 / 32 lanes: n <= kStep * LPR): trial and own row stay in registers for the

@@ -107,6 +107,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de
                         U[e] = philox_lhs_element((uint64_t)row, e, a.P, n, a.lower[e], a.upper[e], key0, key1);
                 }
             } else {
+                // de_propose_row (sx_unfused.hpp) onto a resident row, left apart: a correction made there is owed here
                 int64_t d[kMaxDonors];
                 int irand;
                 philox_donors(a.P, k, row, grow, gen, key0, key1, n, d, irand);
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_DE_RUNS_WAVES) void de
                     ss += acc;
                 }
                 const double dx = sqrt(ss);
+                // best_step's sum (sx_unfused.hpp) and sync_status (sx_rowops.hpp), left apart: a correction made there is owed here
                 if (dx <= a.xtol && wf <= a.ftol)
                     st = 0;
                 else if (wf <= a.ftol)

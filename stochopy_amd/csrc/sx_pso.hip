@@ -851,6 +851,7 @@ __global__ __launch_bounds__(kSelThreads) void cpso_post_kernel(const sx_pso_arg
     for (int k = 0; k < kPostDxThreads / kWave; ++k) ss += sf[k];
     const double dx = sqrt(ss);
     if (mine) a.gbest[tid] = sv;
+    // best_step's sum (sx_unfused.hpp) and sync_status (sx_rowops.hpp), left apart: a correction made there is owed here
     int status = SX_STATUS_NONE;
     if (dx <= xtol && bf <= a.ftol)
         status = 0;

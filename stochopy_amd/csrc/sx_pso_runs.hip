@@ -113,6 +113,7 @@ __device__ __forceinline__ int runs_best_status(const double *fit, const int P, 
             ss += acc;
         }
         const double dx = sqrt(ss);
+        // best_step's sum (sx_unfused.hpp) and sync_status (sx_rowops.hpp), left apart: a correction made there is owed here
         if (dx <= xtol && wf <= ftol)
             st = 0;
         else if (wf <= ftol)
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave, SX_PSO_RUNS_WAVES) void p
             } else {
                 // V = w*V + c1*r1*(pbest - X) + c2*r2*(gbest - X) (cpso/_cpso.py:326).  Without Shrink the new position
                 // follows at once; with Shrink the raw velocity waits in V for the row-wide beta
+                // pso_move_row (sx_unfused.hpp) on resident rows, left apart: a correction made there is owed here
                 double beta = __builtin_huge_val();
                 for (int q0 = 0; q0 < nq; q0 += kStep) {  // a pair of row steps: one Philox call per purpose
                     // 53-bit r1 and r2: slot (q >> 1) * LPR + l, two per call (pso_generation_kernel's layout)

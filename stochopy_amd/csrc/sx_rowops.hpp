@@ -425,6 +425,15 @@ __device__ __forceinline__ void block_argmin(double &bf, int64_t &bi, double *sf
     __syncthreads();
 }
 
+// the termination ladder of the synchronous loops (_common.py:131-158) after generation `it`: dx = step of the best row,
+// best = its value.  The one-thread / one-workgroup epilogues call this; the kernels that spell it out themselves say so
+__device__ __forceinline__ int sync_status(double dx, double xtol, double best, double ftol, int64_t it, int64_t maxiter) {
+    if (dx <= xtol && best <= ftol) return 0;
+    if (best <= ftol) return 1;
+    if (it >= maxiter) return -1;
+    return SX_STATUS_NONE;
+}
+
 // best of the per-workgroup records, 8 records per thread and trip so their loads overlap
 template <int kScan>
 __device__ __forceinline__ void scan_records_n(const double *__restrict__ part_f, const int64_t *__restrict__ part_i,

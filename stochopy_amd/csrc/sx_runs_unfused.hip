@@ -2,18 +2,16 @@
 // (include/stochopy_hip.h, sx_runs_rowwise_args).  The objective cannot be fused, so the R populations live in device memory
 // -- three (R, P, n) arrays -- and a generation of ALL runs is
 //   propose / move kernel  ->  the caller's objective, ONCE, on the stacked (R*P, n) rows  ->  selection kernel  ->
-//   one best / termination workgroup per run
-// with the same draws, arithmetic and record layout as the single-run kernels: given the same objective values run r is the
-// single run of keys[r], bit for bit.
+//   one best / termination workgroup per run.
+// The four steps of a generation are the single run's own (sx_unfused.hpp, where their reference code is listed): the kernels
+// here find a workgroup's run, form that run's pointers, key and settings, and call them -- so given the same objective values
+// run r is the single run of keys[r], bit for bit.  What only a batch has is written here: the initial populations, the start
+// of every run, a run's results and the count of ended runs.
 //
-// Reference code replaced (paths relative to the reference checkout), R times over:
+// Reference code replaced here (paths relative to the reference checkout), R times over:
 //   stochopy/optimize/_common.py:109-120      the Latin hypercube (in-kernel draws: philox_lhs_element)
 //   stochopy/optimize/de/_de.py:208-218       initial population and best
-//   stochopy/optimize/de/_de.py:314-351       de_sync up to the candidates U (mutation, crossover, Random)
 //   stochopy/optimize/cpso/_cpso.py:219-247   initial swarm (V = 0, pbest = X) and best
-//   stochopy/optimize/cpso/_cpso.py:324-329   mutation (velocity / position) + cpso/_constraints.py:4-53
-//   stochopy/optimize/_common.py:123-130      selection_sync after `candfun = fun(cand)`: strict <, in place
-//   stochopy/optimize/_common.py:131-158      argmin + the termination ladder
 //
 // Geometry: every kernel but the last two uses the row geometry of the single-run kernels (lanes_per_row, rows_per_block,
 // RowIds), and a workgroup never spans two runs: a run takes per_run = ceil(P / rows_per_block(n)) workgroups, workgroup b
@@ -27,12 +25,12 @@
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
 #include "sx_runs.hpp"
+#include "sx_unfused.hpp"
 
 using namespace sx;
 
 namespace {
 
-constexpr int kStep = 4;  // row steps per batch of the DE kernel (de_propose_kernel's layout)
 constexpr int kDe = 0, kPso = 1;
 
 // ---- 1. the initial populations (generation 1).  DE: buffer 1 -- generation g lives in buffer g & 1 -- and cand, the rows
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(kFinalWorkgroup) void runs_start_kernel(const sx_ru
     }
 }
 
-// ---- 3. DE: candidates of one generation -> cand, per run (de_propose_kernel's in-kernel-draw branch: same statements)
+// ---- 3. DE: candidates of one generation -> cand, per run (de_propose_row with the run's key, settings and best row)
 template <int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void runs_de_propose_kernel(const sx_runs_rowwise_args a, const DeSweep sw,
                                                                                    const int per_run) {
@@ -113,55 +111,16 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void runs_de_propose_kern
     const int64_t P = a.P, ld = n;
     const RowIds<LPR> id(P, (int)(run * per_run));
     if (!id.active) return;
-    const int l = id.l;
-    const int64_t row = id.row, it = st->it, base = run * P * ld;
-    const uint32_t gen = (uint32_t)(it + 1), grow = (uint32_t)row;
-    const uint32_t key0 = a.keys[2 * run], key1 = a.keys[2 * run + 1];
-    const double *__restrict__ cur = ((it & 1) ? a.pop1 : a.pop0) + base;
-    const double *__restrict__ xi = cur + row * ld;
+    const int64_t it = st->it, base = run * P * ld;
     // the run's own settings (uniform in the workgroup): element `run` of a sweep's arrays, else the struct's scalars
-    const int strategy = run_setting(sw.strategy, run, a.strategy), k = donors_of(strategy);
-    const double F = run_setting(sw.F, run, a.F), CR = run_setting(sw.CR, run, a.CR);
-    const bool repair = a.constraints != 0;
-    int64_t d[kMaxDonors];
-    int irand;
-    philox_donors(P, k, row, grow, gen, key0, key1, n, d, irand);
-    const double *__restrict__ gb = a.gbest + run * ld;
-    double *__restrict__ out = a.pop2 + base + row * ld;
-    const int nq = (n + LPR - 1) / LPR;
-    for (int q0 = 0; q0 < nq; q0 += kStep) {  // four row steps per batch: one Philox call, loads in flight together
-        double x[kStep], dv[kMaxDonors][kStep], g[kStep], r[kStep];
-#pragma unroll
-        for (int t = 0; t < kStep; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            const bool in = e < n;
-            x[t] = in ? xi[e] : 0.0;
-            g[t] = in ? gb[e] : 0.0;
-#pragma unroll
-            for (int s = 0; s < kMaxDonors; ++s) dv[s][t] = (s < k && in) ? cur[d[s] * ld + e] : 0.0;
-        }
-#pragma unroll
-        for (int t = 0; t < kStep; t += 2) {  // 53-bit crossover uniforms, the fused kernel's layout
-            const U4 w = philox4x32_10((uint32_t)((q0 + t) >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposeDeCross, key0,
-                                       key1);
-            r[t] = u53(w.x, w.y);
-            r[t + 1] = u53(w.z, w.w);
-        }
-#pragma unroll
-        for (int t = 0; t < kStep; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            if (e >= n) continue;
-            const double v = de_mutant(strategy, g[t], dv[0][t], dv[1][t], dv[2][t], dv[3][t], dv[4][t], F);
-            double c = (e == irand || r[t] <= CR) ? v : x[t];  // de/_de.py:341-344
-            if (repair && (c < a.lower[e] || c > a.upper[e]))  // de/_constraints.py:21-26
-                c = a.lower[e] + (a.upper[e] - a.lower[e]) * philox_u53(e, LPR, grow, gen, kPurposeDeResample, key0, key1);
-            out[e] = c;
-        }
-    }
+    de_propose_row<SX_RNG_PHILOX, LPR>(((it & 1) ? a.pop1 : a.pop0) + base, ld, P, n, id.l, id.row, (uint32_t)id.row,
+                                       (uint32_t)(it + 1), a.keys[2 * run], a.keys[2 * run + 1],
+                                       run_setting(sw.strategy, run, a.strategy), run_setting(sw.F, run, a.F),
+                                       run_setting(sw.CR, run, a.CR), a.constraints != 0, a.lower, a.upper, a.gbest + run * ld,
+                                       a.pop2 + base + id.row * ld, DeHostDraws{});
 }
 
-// ---- 4. PSO: V = w*V + c1*r1*(pbest - X) + c2*r2*(gbest - X); X += V (after Shrink): X and V in place, per run
-//      (pso_move_kernel's in-kernel-draw branch; the raw velocities wait in the workgroup's LDS for the row-wide beta)
+// ---- 4. PSO: X and V in place, per run (pso_move_row; with Shrink the raw velocities always wait in the workgroup's LDS)
 template <int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void runs_pso_move_kernel(const sx_runs_rowwise_args a, const PsoSweep sw,
                                                                                  const int per_run) {
@@ -170,160 +129,53 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void runs_pso_move_kernel
     const sx_state *st = a.state + run;
     if (st->done) return;
     const int n = a.n;
-    const int64_t P = a.P, ld = n;
-    const RowIds<LPR> id(P, (int)(run * per_run));
-    const int l = id.l;
-    const int64_t rowc = id.rowc, base = run * P * ld;
-    double *Vn = lds + id.slot * (size_t)n;  // Shrink: the raw velocity waits here for the row-wide beta
-    const uint32_t gen = (uint32_t)(st->it + 1), grow = (uint32_t)rowc;
-    const uint32_t key0 = a.keys[2 * run], key1 = a.keys[2 * run + 1];
-    double *xr = a.pop0 + base + rowc * ld, *vr = a.pop1 + base + rowc * ld;
-    const double *pb = a.pop2 + base + rowc * ld, *gb = a.gbest + run * ld;
-    const double w = run_setting(sw.w, run, a.w), c1 = run_setting(sw.c1, run, a.c1), c2 = run_setting(sw.c2, run, a.c2);
+    const RowIds<LPR> id(a.P, (int)(run * per_run));
+    const int64_t at = (run * a.P + id.rowc) * (int64_t)n;
     const bool shrink = a.constraints != 0;
-    double beta = __builtin_huge_val();
-    const int nq = (n + LPR - 1) / LPR;
-    for (int q0 = 0; q0 < nq; q0 += 2) {  // two row steps share one Philox call: 53-bit r1 / r2, the fused kernel's layout
-        const U4 pw = philox4x32_10((uint32_t)(q0 >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposePsoR1, key0, key1);
-        const U4 pv = philox4x32_10((uint32_t)(q0 >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposePsoR2, key0, key1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            if (e >= n) continue;
-            const double v = vr[e], p = pb[e], g = gb[e], x = xr[e];
-            const double r1 = t ? u53(pw.z, pw.w) : u53(pw.x, pw.y), r2 = t ? u53(pv.z, pv.w) : u53(pv.x, pv.y);
-            const double vn = pso_velocity(w, v, c1, r1, p, x, c2, r2, g);
-            if (shrink) {  // cpso/_constraints.py:22-50
-                Vn[e] = vn;
-                const double xc = x + vn, lo = a.lower[e], hi = a.upper[e];
-                if (xc < lo) beta = fmin(beta, (lo - x) / vn);
-                if (xc > hi) beta = fmin(beta, (hi - x) / vn);
-            } else if (id.active) {
-                vr[e] = vn;
-                xr[e] = x + vn;
-            }
-        }
-    }
-    if (shrink) {
-        beta = row_min<LPR>(beta);
-        if (beta == __builtin_huge_val()) beta = 1.0;
-        for (int e = l; e < n; e += LPR) {  // own elements only
-            const double vn = Vn[e] * beta;
-            if (id.active) {
-                const double xn = xr[e] + vn;
-                vr[e] = vn;
-                xr[e] = xn;
-            }
-        }
-    }
+    pso_move_row<SX_RNG_PHILOX, LPR>(a.pop0 + at, a.pop1 + at, a.pop2 + at, a.gbest + run * n, n, id.l, id.active,
+                                     (uint32_t)id.rowc, (uint32_t)(st->it + 1), a.keys[2 * run], a.keys[2 * run + 1],
+                                     run_setting(sw.w, run, a.w), run_setting(sw.c1, run, a.c1), run_setting(sw.c2, run, a.c2),
+                                     shrink, a.lower, a.upper, lds + id.slot * (size_t)n, shrink, nullptr, nullptr);
 }
 
-// ---- 5. selection_sync after the evaluation (_common.py:127-129), per run: rows_select_kernel's statements.  DE: the winner
-//      or the old row into the other buffer; PSO: pbest in place; + the workgroup's best record
+// ---- 5. selection_sync after the evaluation, per run (rows_select_row).  DE: the winner or the old row into the other
+//      buffer; PSO: pbest in place
 template <int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void runs_select_kernel(const sx_runs_rowwise_args a, const int per_run) {
-    __shared__ double sf[kMaxRowsPerBlock];
-    __shared__ int64_t si[kMaxRowsPerBlock];
     const int64_t run = (int64_t)blockIdx.x / per_run;
     const sx_state *st = a.state + run;
     if (st->done) return;
     const int n = a.n;
-    const int64_t P = a.P, ld = n, base = run * P * ld, it = st->it;
-    const RowIds<LPR> id(P, (int)(run * per_run));
-    const double *__restrict__ f = a.f + run * P;
-    double *__restrict__ xfun = a.fit + run * P, *__restrict__ candfit = a.candfit + run * P;
+    const int64_t P = a.P, base = run * P * n, it = st->it;
     const bool de = a.method == kDe;
-    const double *cand = (de ? a.pop2 : a.pop0) + base;
-    const double *xin = (de ? ((it & 1) ? a.pop1 : a.pop0) : a.pop2) + base;
-    double *xout = (de ? ((it & 1) ? a.pop0 : a.pop1) : a.pop2) + base;
-    const double fc = f[id.rowc], fold = xfun[id.rowc];
-    const bool better = fc < fold;  // strict <
-    if (id.active) {
-        const double *src = better ? cand + id.row * ld : xin + id.row * ld;
-        double *dst = xout + id.row * ld;
-        if (better || xin != xout)
-            for (int e = id.l; e < n; e += LPR) dst[e] = src[e];
-        if (id.l == 0) {
-            if (better) xfun[id.row] = fc;
-            candfit[id.row] = fc;
-        }
-    }
-    block_partial<LPR>(better ? fc : fold, id, sf, si, a.part_f + run * per_run, a.part_i + run * per_run);
+    rows_select_row<LPR>(RowIds<LPR>(P, (int)(run * per_run)), (de ? a.pop2 : a.pop0) + base, n, a.f + run * P,
+                         (de ? ((it & 1) ? a.pop1 : a.pop0) : a.pop2) + base, (de ? ((it & 1) ? a.pop0 : a.pop1) : a.pop2) + base,
+                         n, a.fit + run * P, a.candfit + run * P, n, a.part_f + run * per_run, a.part_i + run * per_run);
 }
 
-// ---- 6. best of that generation, step of the best, status (_common.py:131-158): one workgroup per run,
-//      select_finalize_kernel's statements (sx_core.hip) -- its dx in its order: thread t of 256 adds the squares of its
-//      elements t, t + 256, ... in order, a wavefront's 64 sums meet in an xor butterfly (32 ... 1), the four wavefronts'
-//      totals are added in order (dx <= xtol decides the status).  A run that ends leaves its results and counts itself
+// ---- 6. best of that generation, step of the best, status: one workgroup per run (best_step, as select_finalize_kernel of
+//      sx_core.hip).  A run that ends leaves its results and counts itself
 __global__ __launch_bounds__(kFinalWorkgroup) void runs_finalize_kernel(const sx_runs_rowwise_args a, const int per_run) {
-    __shared__ double sf[kFinalWorkgroup / kWave];
-    __shared__ int64_t si[kFinalWorkgroup / kWave];
     const int64_t run = blockIdx.x;
-    sx_state *__restrict__ state = a.state + run;
+    sx_state *state = a.state + run;
     double bf = __builtin_huge_val();
     int64_t bi = INT64_MAX;
     scan_records(a.part_f + run * per_run, a.part_i + run * per_run, per_run, bf, bi);
     if (state->done) return;
     const int64_t it = state->it + 1;  // the generation being finalised
-    block_argmin(bf, bi, sf, si);
-
     const int n = a.n;
     const int64_t base = run * a.P * n;
-    double *__restrict__ gbest = a.gbest + run * n;
-    const double *rows = a.method == kDe ? ((it & 1) ? a.pop1 : a.pop0) : a.pop2;
-    const double *src = rows + base + bi * n;
-    constexpr int kPer = (kWideFrom + kFinalWorkgroup - 1) / kFinalWorkgroup;
-    double gv[kPer], sv[kPer];
-    double acc = 0.0;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-        const int e = threadIdx.x + u * kFinalWorkgroup;
-        gv[u] = e < n ? gbest[e] : 0.0;
-        sv[u] = e < n ? src[e] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-        if (threadIdx.x + u * kFinalWorkgroup < n) {
-            const double d = gv[u] - sv[u];
-            acc += d * d;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, kWave);
-    if ((threadIdx.x & 63) == 0) sf[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    double ss = 0.0;
-    for (int k = 0; k < kFinalWorkgroup / kWave; ++k) ss += sf[k];
-    const double dx = sqrt(ss);
-    int status = SX_STATUS_NONE;  // (every thread: the run's results below are written by all of them)
-    if (dx <= a.xtol && bf <= a.ftol)
-        status = 0;
-    else if (bf <= a.ftol)
-        status = 1;
-    else if (it >= a.maxiter)
-        status = -1;
-    const bool over = status != SX_STATUS_NONE;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-        const int e = threadIdx.x + u * kFinalWorkgroup;
-        if (e < n) {
-            gbest[e] = sv[u];
-            if (over) a.xs[run * n + e] = sv[u];
-        }
-    }
+    const bool de = a.method == kDe;
+    double *gbest = a.gbest + run * n;
+    const int status = best_step<(kWideFrom + kFinalWorkgroup - 1) / kFinalWorkgroup>(
+        bf, bi, it, (de ? a.pop0 : a.pop2) + base, (de ? a.pop1 : a.pop2) + base, n, n, gbest, state, a.maxiter, a.xtol, a.ftol);
+    if (status == SX_STATUS_NONE) return;
+    for (int e = threadIdx.x; e < n; e += kFinalWorkgroup) a.xs[run * n + e] = gbest[e];  // (this thread's own stores)
     if (threadIdx.x == 0) {
-        state->it = it;
-        state->gbidx = bi;
-        state->gfit = bf;
-        state->dx = dx;
-        state->status = status;
-        state->done = over;
-        if (over) {
-            a.funs[run] = bf;
-            a.nits[run] = it;
-            a.statuses[run] = status;
-            atomicAdd(a.ended, 1);
-        }
+        a.funs[run] = bf;
+        a.nits[run] = it;
+        a.statuses[run] = status;
+        atomicAdd(a.ended, 1);
     }
 }
 

@@ -4,20 +4,17 @@
 // with the same draws, arithmetic and record layout as the fused kernels: given bit-identical fitness values the
 // run is the fused run, bit for bit.
 //
-// Reference code replaced (paths relative to the reference checkout):
-//   stochopy/optimize/de/_de.py:314-351       de_sync up to the candidates U (mutation, crossover, Random)
-//   stochopy/optimize/cpso/_cpso.py:324-329   mutation (velocity / position) + cpso/_constraints.py:4-53
-//   stochopy/optimize/_common.py:123-130      selection_sync after `candfun = fun(cand)`: strict <, in place
-//   stochopy/optimize/_common.py:27-106       the population wrapper `fun(X)` itself is the caller's callable
+// The steps themselves -- and the reference code they replace -- are in sx_unfused.hpp, shared with the batched runs
+// (sx_runs_unfused.hip); the kernels here form ONE run's pointers and settings out of sx_de_args / sx_pso_args and call them.
+// Reference: stochopy/optimize/_common.py:27-106, the population wrapper `fun(X)`, is the caller's callable.
 #include "sx_device.hpp"
 #include "sx_host.hpp"
 #include "sx_rowops.hpp"
+#include "sx_unfused.hpp"
 
 using namespace sx;
 
 namespace {
-
-constexpr int kStep = 4;
 
 // candidates of one generation -> cand (P, n) row-major; nothing else is touched
 template <int RNG, int LPR>
@@ -25,182 +22,40 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void de_propose_kernel(co
                                                                               double *__restrict__ cand) {
     const sx_state *st = a.state;
     if (st->done) return;
-    const int n = a.n;
-    const int64_t P = a.P, ld = a.ld;
-    const RowIds<LPR> id(P);
+    const RowIds<LPR> id(a.P);
     if (!id.active) return;
-    const int l = id.l;
-    const int64_t row = id.row, it = st->it;
-    const uint32_t gen = (uint32_t)(it + 1), grow = (uint32_t)(a.row0 + row);
-    const double *__restrict__ cur = (it & 1) ? a.buf1 : a.buf0;
-    const double *__restrict__ xi = cur + row * ld;
-    const int strategy = a.strategy, k = donors_of(strategy);
-    const bool repair = a.constraints != 0;
-    int64_t d[kMaxDonors];
-    int irand;
-    if (RNG == SX_RNG_PHILOX) {
-        philox_donors(P, k, row, grow, gen, a.key0, a.key1, n, d, irand);
-    } else {
-#pragma unroll
-        for (int t = 0; t < kMaxDonors; ++t) d[t] = t < k ? (int64_t)a.donors[(int64_t)t * P + row] : 0;
-        irand = a.irand[row];
-    }
-    const double *__restrict__ gb = a.gbest != nullptr ? a.gbest : cur + st->gbidx * ld;
-    const double F = a.F, CR = a.CR;
-    double *__restrict__ out = cand + row * (int64_t)n;
-    const int nq = (n + LPR - 1) / LPR;
-    for (int q0 = 0; q0 < nq; q0 += kStep) {  // four row steps per batch: one Philox call, loads in flight together
-        double x[kStep], dv[kMaxDonors][kStep], g[kStep], r[kStep], rs[kStep];
-#pragma unroll
-        for (int t = 0; t < kStep; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            const bool in = e < n;
-            x[t] = in ? xi[e] : 0.0;
-            g[t] = in ? gb[e] : 0.0;
-#pragma unroll
-            for (int s = 0; s < kMaxDonors; ++s) dv[s][t] = (s < k && in) ? cur[d[s] * ld + e] : 0.0;
-            r[t] = (RNG == SX_RNG_HOST && in) ? a.r1[row * (int64_t)n + e] : 2.0;
-            rs[t] = (RNG == SX_RNG_HOST && in && repair) ? a.resample[row * (int64_t)n + e] : 0.0;
-        }
-        if (RNG == SX_RNG_PHILOX) {
-#pragma unroll
-            for (int t = 0; t < kStep; t += 2) {  // 53-bit crossover uniforms, the fused kernel's layout
-                const U4 w = philox4x32_10((uint32_t)((q0 + t) >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposeDeCross,
-                                           a.key0, a.key1);
-                r[t] = u53(w.x, w.y);
-                r[t + 1] = u53(w.z, w.w);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kStep; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            if (e >= n) continue;
-            const double v = de_mutant(strategy, g[t], dv[0][t], dv[1][t], dv[2][t], dv[3][t], dv[4][t], F);
-            double c = (e == irand || r[t] <= CR) ? v : x[t];  // de/_de.py:341-344
-            if (repair && (c < a.lower[e] || c > a.upper[e]))  // de/_constraints.py:21-26
-                c = RNG == SX_RNG_HOST ? rs[t]
-                                       : a.lower[e] + (a.upper[e] - a.lower[e]) *
-                                             philox_u53(e, LPR, grow, gen, kPurposeDeResample, a.key0, a.key1);
-            out[e] = c;
-        }
-    }
+    const int64_t it = st->it;
+    const double *cur = (it & 1) ? a.buf1 : a.buf0;
+    const double *gb = a.gbest != nullptr ? a.gbest : cur + st->gbidx * a.ld;
+    de_propose_row<RNG, LPR>(cur, a.ld, a.P, a.n, id.l, id.row, (uint32_t)(a.row0 + id.row), (uint32_t)(it + 1), a.key0, a.key1,
+                             a.strategy, a.F, a.CR, a.constraints != 0, a.lower, a.upper, gb, cand + id.row * (int64_t)a.n,
+                             DeHostDraws{a.r1, a.resample, a.donors, a.irand});
 }
 
-// V = w*V + c1*r1*(pbest - X) + c2*r2*(gbest - X); X += V (after Shrink): X and V in place
+// X and V of one generation in place.  has_stash: the launch brought rows_per_block(n) * n doubles of dynamic LDS (not for
+// wide rows, n > kWideFrom: pso_move_row's form without a stash)
 template <int RNG, int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void pso_move_kernel(const sx_pso_args a, const int has_stash) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const sx_state *st = a.state;
     if (st->done) return;
     const int n = a.n;
-    const int64_t P = a.P, ld = a.ld;
-    const RowIds<LPR> id(P);
-    const int l = id.l;
-    const int64_t rowc = id.rowc;
-    double *Vn = lds + id.slot * (size_t)n;  // Shrink: the raw velocity waits here for the row-wide beta
-    const uint32_t gen = (uint32_t)(st->it + 1), grow = (uint32_t)(a.row0 + rowc);
-    double *xr = a.X + rowc * ld, *vr = a.V + rowc * ld;
-    const double *pb = a.pbest + rowc * ld, *gb = a.gbest;
-    const double w = a.w, c1 = a.c1, c2 = a.c2;
+    const RowIds<LPR> id(a.P);
+    const int64_t at = id.rowc * a.ld, draws = id.rowc * (int64_t)n;
     const bool shrink = a.constraints != 0;
-    double beta = __builtin_huge_val();
-    const int nq = (n + LPR - 1) / LPR;
-    // wide rows (n > kWideFrom: one wavefront per row, no dynamic LDS -- has_stash = 0): with Shrink the raw velocities are
-    // formed AGAIN behind the row-wide beta instead of waiting in LDS -- same operands, same operations, same bits
-    const bool stash = shrink && has_stash;
-    // raw velocity of the two elements (q0 + t) * LPR + l, t = 0, 1 (one Philox call)
-    auto raw = [&](int q0, double(&x)[2], double(&vn)[2]) {
-        U4 pw = {0u, 0u, 0u, 0u}, pv = {0u, 0u, 0u, 0u};  // 53-bit r1 / r2, the fused kernel's layout
-        if (RNG == SX_RNG_PHILOX) {
-            pw = philox4x32_10((uint32_t)(q0 >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposePsoR1, a.key0, a.key1);
-            pv = philox4x32_10((uint32_t)(q0 >> 1) * (uint32_t)LPR + (uint32_t)l, grow, gen, kPurposePsoR2, a.key0, a.key1);
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            x[t] = 0.0, vn[t] = 0.0;
-            if (e >= n) continue;
-            const double v = vr[e], p = pb[e], g = gb[e];
-            x[t] = xr[e];
-            double r1 = t ? u53(pw.z, pw.w) : u53(pw.x, pw.y), r2 = t ? u53(pv.z, pv.w) : u53(pv.x, pv.y);
-            if (RNG == SX_RNG_HOST) {
-                r1 = a.r1[rowc * (int64_t)n + e];
-                r2 = a.r2[rowc * (int64_t)n + e];
-            }
-            vn[t] = pso_velocity(w, v, c1, r1, p, x[t], c2, r2, g);
-        }
-    };
-    for (int q0 = 0; q0 < nq; q0 += 2) {  // two row steps share one Philox call
-        double x[2], vn[2];
-        raw(q0, x, vn);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int e = (q0 + t) * LPR + l;
-            if (e >= n) continue;
-            if (shrink) {  // cpso/_constraints.py:22-50
-                if (stash) Vn[e] = vn[t];
-                const double xc = x[t] + vn[t], lo = a.lower[e], hi = a.upper[e];
-                if (xc < lo) beta = fmin(beta, (lo - x[t]) / vn[t]);
-                if (xc > hi) beta = fmin(beta, (hi - x[t]) / vn[t]);
-            } else if (id.active) {
-                vr[e] = vn[t];
-                xr[e] = x[t] + vn[t];
-            }
-        }
-    }
-    if (shrink) {
-        beta = row_min<LPR>(beta);
-        if (beta == __builtin_huge_val()) beta = 1.0;
-        if (stash) {
-            for (int e = l; e < n; e += LPR) {  // own elements only
-                const double vn = Vn[e] * beta;
-                if (id.active) {
-                    const double xn = xr[e] + vn;
-                    vr[e] = vn;
-                    xr[e] = xn;
-                }
-            }
-        } else {
-            for (int q0 = 0; q0 < nq; q0 += 2) {
-                double x[2], vn[2];
-                raw(q0, x, vn);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int e = (q0 + t) * LPR + l;
-                    if (e >= n || !id.active) continue;
-                    const double vb = vn[t] * beta;
-                    vr[e] = vb;
-                    xr[e] = x[t] + vb;
-                }
-            }
-        }
-    }
+    pso_move_row<RNG, LPR>(a.X + at, a.V + at, a.pbest + at, a.gbest, n, id.l, id.active, (uint32_t)(a.row0 + id.rowc),
+                           (uint32_t)(st->it + 1), a.key0, a.key1, a.w, a.c1, a.c2, shrink, a.lower, a.upper,
+                           lds + id.slot * (size_t)n, shrink && has_stash, RNG == SX_RNG_HOST ? a.r1 + draws : nullptr,
+                           RNG == SX_RNG_HOST ? a.r2 + draws : nullptr);
 }
 
-// selection_sync after the evaluation (_common.py:127-129): rows with f < xfun take the candidate;
-// xout may be xin (in place: PSO's pbest) or the other population buffer (DE); + the workgroup's best record
 template <int LPR>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void rows_select_kernel(
     const double *__restrict__ cand, int64_t ldc, const double *__restrict__ f, const double *xin, double *xout,
     int64_t ldx, double *__restrict__ xfun, double *__restrict__ candfit, int64_t P, int n, const sx_state *st,
     double *__restrict__ part_f, int64_t *__restrict__ part_i) {
-    __shared__ double sf[kMaxRowsPerBlock];
-    __shared__ int64_t si[kMaxRowsPerBlock];
     if (st->done) return;
-    const RowIds<LPR> id(P);
-    const double fc = f[id.rowc], fold = xfun[id.rowc];
-    const bool better = fc < fold;  // strict <
-    if (id.active) {
-        const double *src = better ? cand + id.row * ldc : xin + id.row * ldx;
-        double *dst = xout + id.row * ldx;
-        if (better || xin != xout)
-            for (int e = id.l; e < n; e += LPR) dst[e] = src[e];
-        if (id.l == 0) {
-            if (better) xfun[id.row] = fc;
-            if (candfit != nullptr) candfit[id.row] = fc;
-        }
-    }
-    block_partial<LPR>(better ? fc : fold, id, sf, si, part_f, part_i);
+    rows_select_row<LPR>(RowIds<LPR>(P), cand, ldc, f, xin, xout, ldx, xfun, candfit, n, part_f, part_i);
 }
 
 }  // namespace

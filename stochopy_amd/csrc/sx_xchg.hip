@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "sx_host.hpp"
+#include "sx_rowops.hpp"  // sync_status
 #include "sx_xchg.hpp"
 
 using namespace sx;
@@ -276,13 +277,7 @@ __global__ __launch_bounds__(kXfThreads) void xchg_finalize_kernel(
         double ss = 0.0;
         for (int w = 0; w < nw; ++w) ss += sd[w];
         const double dx = sqrt(ss);
-        int status = SX_STATUS_NONE;
-        if (dx <= xtol && gf <= ftol)
-            status = 0;
-        else if (gf <= ftol)
-            status = 1;
-        else if (it >= maxiter)
-            status = -1;
+        const int status = sync_status(dx, xtol, gf, ftol, it, maxiter);
         state->it = it;
         state->gbidx = gi;
         state->gfit = gf;

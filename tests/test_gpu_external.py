@@ -80,6 +80,38 @@ def test_batched_objective_reproduces_the_fused_run(sa, method, objective, n, op
     assert np.array_equal(ext.xall, fused.xall) and np.array_equal(ext.funall, fused.funall)
 
 
+def _wide_from():
+    from stochopy_amd import _lib
+
+    return _lib.wide_from()
+
+
+# the longest row of the wavefront-per-row geometry and the first wide one (64 threads and one record per row; the PSO move
+# without its LDS stash), with coefficients that drive rows out of the box: Random does repair, Shrink does scale
+EDGE_CASES = [
+    ("de", {"strategy": "rand2bin", "constraints": "Random", "mutation": 1.5}),
+    ("pso", {"constraints": "Shrink", "inertia": 1.0, "cognitivity": 3.0, "sociability": 3.0}),
+]
+
+
+@pytest.mark.parametrize("rng", ["philox", "numpy-legacy"])
+@pytest.mark.parametrize("over", [0, 1], ids=["n=wide_from", "n=wide_from+1"])
+@pytest.mark.parametrize("method,opts", EDGE_CASES, ids=["de-random", "pso-shrink"])
+def test_batched_objective_reproduces_the_fused_run_on_both_sides_of_wide_from(sa, method, opts, over, rng):
+    n = _wide_from() + over
+    o = dict(opts, popsize=6, maxiter=4, seed=13, rng=rng, backend="hip", return_all=True, updating="deferred")
+    fused = sa.optimize.minimize(sa.factory.sphere, _bounds(n), method=method, options=dict(o))
+    ext = sa.optimize.minimize(device_objective(sa, "sphere"), _bounds(n), method=method, options=dict(o))
+    assert (ext.nit, ext.nfev, ext.status) == (fused.nit, fused.nfev, fused.status)
+    assert np.array_equal(ext.x, fused.x) and ext.fun == fused.fun
+    assert np.array_equal(ext.xall, fused.xall) and np.array_equal(ext.funall, fused.funall)
+    # the constraint does act: without it the run ends elsewhere (the initial population lies inside the box)
+    free = sa.optimize.minimize(sa.factory.sphere, _bounds(n), method=method, options=dict(o, constraints=None))
+    assert free.nit == fused.nit
+    assert not np.array_equal(fused.xall[-1], free.xall[-1]), "no row ever left the box"
+    assert (np.abs(fused.xall) <= 5.12 * (1 + 1e-12)).all()  # (Shrink lands on a bound to rounding)
+
+
 def test_objective_that_synchronises_is_launched_eagerly(sa):
     """A caller may bridge a numpy objective inside their own batched callable (their code does the device -> host
     -> device round trip, with extra args as in the reference: fun(X, *args)).  Such an objective cannot be captured
