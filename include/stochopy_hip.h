@@ -770,6 +770,42 @@ int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, i
                            const double *fprop, const double *pmom, const double *k0, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Per-axis scale adaptation in the warm-up (a diagonal metric).  No counterpart in the reference.  On top of sx_sample_adapt:
+ * chain c carries m_c[e] (1.0 at the start) and eff_c[e] = m_c[e] * step[e]; an adapting sample reads s * eff[e] where it
+ * read s * step[e] (the same association), the momenta stay randn(n) and the kinetic energy 0.5 sum p^2 -- leap-frog in
+ * coordinates rescaled per axis; the decision is not changed.  The *_metric entry points take the arguments of the *_adapt
+ * forms with this struct behind `ad`.
+ *
+ * Windows: b_0 = win_start < b_1 = win_end[0] < ... < b_J = win_end[nwin - 1] <= warmup.  After the decision of sample `it`
+ * with b_{j-1} < it <= b_j, x the chain's current state and N = it - b_{j-1}, per element (Welford):
+ *     delta = x - mean;  mean += delta / N;  M2 += delta * (x - mean)
+ * At it == b_j, after that and after the sample's step of the dual averaging, with h_e = 0.5 * (upper_e - lower_e):
+ *     var = M2 / (N - 1);   v = (N / (N + 5)) * var + ((5 / (N + 5)) * 1e-3) * (h_e * h_e);   r_e = sqrt(v)
+ *     L = (sum_e log r_e) / n;   m_e = r_e / exp(L);   eff_e = m_e * step[e]
+ * unless some r_e is not finite or not positive: the chain then keeps its m.  mean and M2 are zeroed.  Then the step size
+ * restarts: sbase <- sbase * exp(logsbar) (1.0 at the start), hbar = logsbar = 0, the multiplier in use is sbase, and the
+ * rule's clock is t = (double)(it - b_j) for the samples that follow; while adapting s = sbase * exp(logs), at it == warmup
+ * s = sbase * exp(logsbar).  With nwin = 0 every output is the *_adapt form's, bit for bit, and the four pointers may be NULL.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_sample_metric {
+    double *sbase;           /* DEVICE (C): the multiplier the dual averaging restarted from */
+    double *m, *mean, *M2;   /* DEVICE (C, n): the scales and the running moments of the open window */
+    int32_t nwin;            /* 0 <= nwin <= 8 */
+    int64_t win_start;       /* b_0 >= 0 */
+    int64_t win_end[8];      /* b_1 < ... < b_nwin <= warmup */
+} sx_sample_metric;
+/* sizeof(sx_sample_metric) as the library was built (sx_struct_size is not extended) */
+int sx_sample_metric_bytes(void);
+int sx_sample_run_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it0,
+                         int64_t steps, void *stream);
+int sx_sample_propose_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it,
+                             double *prop, double *pmom, double *k0, void *stream);
+int sx_sample_leap_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, double coef, int move,
+                          double *q, double *pmom, const double *G, void *stream);
+int sx_sample_decide_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it,
+                            const double *prop, const double *fprop, const double *pmom, const double *k0, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Parallel tempering (replica exchange) for the Metropolis-Hastings chains (csrc/sx_sample_temper.hip): C ladders of K
  * device-resident replicas.  No counterpart in the reference.  Replica q = c K + k is rung k of ladder c and samples
  * p^(beta[k]), beta[k] = 1 / T_k with 1 = T_0 < T_1 < ...: sx_sample_run's mcmc sample with d = (fcur - fprop) * beta[k]

@@ -138,6 +138,15 @@ class SxSampleAdapt(C.Structure):
     ]
 
 
+class SxSampleMetric(C.Structure):
+    """sx_sample_metric: per-axis scale adaptation in the warm-up (its size is checked against sx_sample_metric_bytes)."""
+    _fields_ = [
+        ("sbase", vp), ("m", vp), ("mean", vp), ("M2", vp),
+        ("nwin", i32),
+        ("win_start", i64), ("win_end", i64 * 8),
+    ]
+
+
 class SxDeRunsArgs(C.Structure):
     _fields_ = [
         ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("xs", vp), ("funs", vp), ("nits", vp), ("statuses", vp),
@@ -279,6 +288,14 @@ PROTOTYPES = {
     "sx_sample_propose_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), i64, vp, vp, vp, vp]),
     "sx_sample_leap_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), f64, C.c_int, vp, vp, vp, vp]),
     "sx_sample_decide_adapt": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), i64, vp, vp, vp, vp, vp]),
+    "sx_sample_metric_bytes": (C.c_int, []),
+    "sx_sample_run_metric": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), C.POINTER(SxSampleMetric), i64, i64, vp]),
+    "sx_sample_propose_metric": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), C.POINTER(SxSampleMetric), i64, vp, vp,
+                                           vp, vp]),
+    "sx_sample_leap_metric": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), C.POINTER(SxSampleMetric), f64, C.c_int,
+                                        vp, vp, vp, vp]),
+    "sx_sample_decide_metric": (C.c_int, [C.POINTER(SxSampleArgs), C.POINTER(SxSampleAdapt), C.POINTER(SxSampleMetric), i64, vp, vp,
+                                          vp, vp, vp]),
     "sx_sample_tempered_run": (C.c_int, [C.POINTER(SxSampleArgs), vp, C.c_int, i64, vp, i64, i64, vp]),
     "sx_sample_tempered_max_rungs": (C.c_int, [C.c_int]),
     "sx_sample_decide_tempered": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, C.c_int, C.c_int, vp]),
@@ -364,6 +381,9 @@ def lib():
     if handle.sx_sample_adapt_bytes() != C.sizeof(SxSampleAdapt):
         raise HipLibraryError(f"{LIB_PATH}: sx_sample_adapt is {handle.sx_sample_adapt_bytes()} bytes, its mirror "
                               f"{C.sizeof(SxSampleAdapt)}; rebuild the library")
+    if handle.sx_sample_metric_bytes() != C.sizeof(SxSampleMetric):
+        raise HipLibraryError(f"{LIB_PATH}: sx_sample_metric is {handle.sx_sample_metric_bytes()} bytes, its mirror "
+                              f"{C.sizeof(SxSampleMetric)}; rebuild the library")
     _lib = handle
     return _lib
 

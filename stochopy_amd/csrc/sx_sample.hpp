@@ -1,7 +1,7 @@
 // What the sampler kernels share, written once: the draws, a chain's scalars and its step-size adaptation, the STEP of a chain
 // (the mcmc block perturbation and the Metropolis decision, for the kernels around a caller-supplied objective,
 // sx_sample_unfused.hip, and the tempered ladders, sx_sample_temper.hip), the unfused tail, the exchange rule of the ladders,
-// and the host's argument check and workgroup size.  The two resident kernels of sx_sample.hip share the draws, the scalars and
+// and the host's argument check and workgroup size.  The two resident kernels (sx_sample_kernels.hpp) share the draws, the scalars and
 // the adaptation, but spell the step themselves (folded into the functions below it ran 1 - 3 % slower there: DESIGN.md 19);
 // the same expressions under -ffp-contract=off -- with bit-identical objective (and gradient) values the resident and the
 // unfused path give the same run, bit for bit, which tests/test_gpu_sample_batched.py holds them to.
@@ -17,10 +17,11 @@ namespace {
 
 enum { kMcmc = 0, kHmcFd = 1, kHmcAnalytic = 2 };  // kernel variants
 
-// doubles of LDS one chain needs (the resident kernels: sx_sample.hip, sx_sample_temper.hip)
-__host__ __device__ inline int sample_row_doubles(int variant, int n) {
+// doubles of LDS one chain needs (the resident kernels: sx_sample.hip, sx_sample_temper.hip); `metric`: with the chain's
+// per-axis steps eff[n] behind them (sx_sample_metric)
+__host__ __device__ inline int sample_row_doubles(int variant, int n, bool metric = false) {
     const int S = gen_row_stride(n);
-    return variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S;
+    return (variant == kMcmc ? n + S : variant == kHmcAnalytic ? 2 * n + S : 2 * n + 3 * S) + (metric ? n : 0);
 }
 // Waves per workgroup of a kernel with one row group per chain (or row): the largest power of two within the row kernels' caps
 // (kMaxWavesPerBlock waves, kMaxRowsPerBlock rows) whose rows, at `row_bytes` of LDS each, fit 64 KiB.  One wave may need more
@@ -31,7 +32,9 @@ inline int waves_per_workgroup(int n, size_t row_bytes) {
     while (2 * w <= kMaxWavesPerBlock && 2 * w * rpw <= kMaxRowsPerBlock && 2 * w * rpw * row_bytes <= 64 * 1024) w *= 2;
     return w;
 }
-inline int sample_waves(int variant, int n) { return waves_per_workgroup(n, sizeof(double) * sample_row_doubles(variant, n)); }
+inline int sample_waves(int variant, int n, bool metric = false) {
+    return waves_per_workgroup(n, sizeof(double) * sample_row_doubles(variant, n, metric));
+}
 
 template <int LPR>
 __device__ __forceinline__ double row_prod(double v) {
@@ -123,25 +126,38 @@ struct AdaptState {
     __device__ __forceinline__ void start() { s = 1.0, hbar = 0.0, logsbar = 0.0, nacc_warm = 0; }
 };
 
-// the adapting kernels' last argument; the plain kernels take an empty struct in its place, which they never read
+// the adapting kernels' last argument; the plain kernels take an empty struct in its place, which they never read.  The
+// kernels with per-axis scales (METRIC, which implies ADAPT) take sx_sample_adapt with sx_sample_metric behind it.
 struct NoAdapt {};
-template <bool ADAPT>
-using AdaptArg = std::conditional_t<ADAPT, sx_sample_adapt, NoAdapt>;
-template <bool ADAPT>
-AdaptArg<ADAPT> adapt_arg(const sx_sample_adapt *ad) {  // (the plain entry points pass no `ad`)
-    if constexpr (ADAPT)
+struct MetricAdapt : sx_sample_adapt {
+    sx_sample_metric mt;
+};
+template <bool ADAPT, bool METRIC = false>
+using AdaptArg = std::conditional_t<METRIC, MetricAdapt, std::conditional_t<ADAPT, sx_sample_adapt, NoAdapt>>;
+template <bool ADAPT, bool METRIC = false>
+AdaptArg<ADAPT, METRIC> adapt_arg(const sx_sample_adapt *ad, const sx_sample_metric *mt = nullptr) {
+    if constexpr (METRIC) {
+        MetricAdapt r;
+        static_cast<sx_sample_adapt &>(r) = *ad;
+        r.mt = *mt;
+        return r;
+    } else if constexpr (ADAPT) {
         return *ad;
-    else
+    } else {  // (the plain entry points pass no `ad`)
         return {};
+    }
 }
 
 // After the decision of sample `it` >= 1 (d its own log acceptance ratio; feasible: it passed the box test; nacc the count
 // with this sample): one step of the rule for it <= warmup, the averaged multiplier frozen at it == warmup.  The decision
 // itself accepts a NaN d; HERE a NaN d counts as alpha = 0, so that a diverged trajectory shrinks the step.
-__device__ __forceinline__ void adapt_update(AdaptState &ad, int64_t warmup, double target, int64_t it, bool feasible, double d,
-                                             int64_t nacc) {
+// RESTARTS (the kernels with per-axis scales): the rule's clock runs from `origin`, the last window end before `it`, and the
+// multiplier is sbase times what the rule gives; without them origin = 0 and there is no sbase.
+template <bool RESTARTS>
+__device__ __forceinline__ void adapt_rule(AdaptState &ad, int64_t warmup, double target, int64_t it, int64_t origin, double sbase,
+                                           bool feasible, double d, int64_t nacc) {
     if (it > warmup) return;
-    const double t = (double)it;
+    const double t = RESTARTS ? (double)(it - origin) : (double)it;
     const double alpha = !feasible ? 0.0 : d < 0.0 ? exp(d) : d >= 0.0 ? 1.0 : 0.0;
     const double eta = 1.0 / (t + kAdaptT0);
     ad.hbar = (1.0 - eta) * ad.hbar + eta * (target - alpha);
@@ -150,7 +166,121 @@ __device__ __forceinline__ void adapt_update(AdaptState &ad, int64_t warmup, dou
     const double w = 1.0 / (rt * sqrt(rt));
     ad.logsbar = w * logs + (1.0 - w) * ad.logsbar;
     ad.s = it < warmup ? exp(logs) : exp(ad.logsbar);
+    if constexpr (RESTARTS) ad.s = sbase * ad.s;
     if (it == warmup) ad.nacc_warm = nacc;
+}
+__device__ __forceinline__ void adapt_update(AdaptState &ad, int64_t warmup, double target, int64_t it, bool feasible, double d,
+                                             int64_t nacc) {
+    adapt_rule<false>(ad, warmup, target, it, 0, 1.0, feasible, d, nacc);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-axis scales in the warm-up (sx_sample_metric; include/stochopy_hip.h states the rule).  Chain c's m, mean and M2 are rows
+// of (C, n) DEVICE arrays and its sbase an element of a (C) one: they are touched after a decision inside a window and at a
+// window end only, every element by the lane that owns it, so they need neither LDS nor a fence.  What a sample reads per
+// element is eff = m * step: the resident kernels keep it in the chain's LDS row, the unfused ones form it from m.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr double kMetricShrinkCount = 5.0;     // v = (N / (N + 5)) var + (5 / (N + 5)) 1e-3 h^2: Stan's shrinkage of a window's
+constexpr double kMetricShrinkScale = 1.0e-3;  // variance towards 1e-3 of the squared half-width (the units `step` is in)
+
+// where sample `it` stands among the windows: N = it - b_{j-1} inside window j (0 outside all), whether it ends it, and the
+// origin of the rule's clock, the last end BEFORE it (0 when there is none).  Neither is stored: both follow from it.
+struct MetricClock {
+    int64_t N = 0, origin = 0;
+    bool end = false;
+};
+__device__ __forceinline__ MetricClock metric_clock(const sx_sample_metric &mt, int64_t it) {
+    MetricClock k;
+    int64_t lo = mt.win_start;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (j < mt.nwin) {
+            const int64_t hi = mt.win_end[j];
+            if (it > lo && it <= hi) k.N = it - lo, k.end = it == hi;
+            if (hi < it) k.origin = hi;
+            lo = hi;
+        }
+    }
+    return k;
+}
+// chain c's scalar beside AdaptState
+__device__ __forceinline__ double metric_load_sbase(const sx_sample_metric &mt, int64_t c) { return mt.nwin > 0 ? mt.sbase[c] : 1.0; }
+// element e of chain c's eff
+__device__ __forceinline__ double metric_eff(const sx_sample_args &a, const sx_sample_metric &mt, int64_t c, int e) {
+    return mt.nwin > 0 ? mt.m[c * a.n + e] * a.step[e] : 1.0 * a.step[e];
+}
+// sample 0: m = 1, the moments empty, sbase = 1 (`active`: a padding row group stores nothing, here and below)
+template <int LPR>
+__device__ __forceinline__ void metric_start(const sx_sample_args &a, const sx_sample_metric &mt, int64_t c, int l, bool active,
+                                             double &sbase) {
+    sbase = 1.0;
+    if (mt.nwin == 0 || !active) return;
+    for (int e = l; e < a.n; e += LPR) mt.m[c * a.n + e] = 1.0, mt.mean[c * a.n + e] = 0.0, mt.M2[c * a.n + e] = 0.0;
+    if (l == 0) mt.sbase[c] = 1.0;
+}
+// After the decision of sample `it` >= 1, in the place of adapt_update: the Welford step on the chain's current state x(e), the
+// dual averaging on its clock, and at a window end the new scales -- put(e, eff_e) takes them -- and the restart of the step
+// size.  Every lane of the row group takes the same branches (the scalars are uniform in it, `ok` is reduced over it).
+template <int LPR, class X, class Put>
+__device__ __forceinline__ void metric_update(const sx_sample_args &a, const MetricAdapt &ad, AdaptState &as, double &sbase,
+                                              int64_t c, int l, bool active, int64_t it, bool feasible, double d, int64_t nacc,
+                                              X &&x, Put &&put) {
+    if (it > ad.warmup) return;  // (every window lies inside the warm-up: the sampling phase pays this test alone)
+    const sx_sample_metric &mt = ad.mt;
+    const int n = a.n;
+    const MetricClock k = metric_clock(mt, it);
+    const double N = (double)k.N;
+    if (k.N > 0) {
+        for (int e = l; e < n; e += LPR) {
+            const double v = x(e);
+            const double mean0 = mt.mean[c * n + e];
+            const double delta = v - mean0;
+            const double mean = mean0 + delta / N;
+            const double M2 = mt.M2[c * n + e] + delta * (v - mean);
+            if (active) mt.mean[c * n + e] = mean, mt.M2[c * n + e] = M2;
+        }
+    }
+    adapt_rule<true>(as, ad.warmup, ad.target, it, k.origin, sbase, feasible, d, nacc);
+    if (!k.end) return;
+    const double wn = N / (N + kMetricShrinkCount), wp = (kMetricShrinkCount / (N + kMetricShrinkCount)) * kMetricShrinkScale;
+    const auto r_of = [&](int e) {
+        const double h = 0.5 * (a.upper[e] - a.lower[e]);
+        return sqrt(wn * (mt.M2[c * n + e] / (N - 1.0)) + wp * (h * h));
+    };
+    double sumlog = 0.0;
+    bool ok = true;
+    for (int e = l; e < n; e += LPR) {
+        const double r = r_of(e);
+        ok = ok && r > 0.0 && r < __builtin_huge_val();  // (a NaN fails both)
+        sumlog += log(r);
+    }
+    ok = row_all<LPR>(ok);
+    const double gm = exp(row_sum<LPR>(sumlog) / (double)n);
+    for (int e = l; e < n; e += LPR) {
+        if (ok) {
+            const double m = r_of(e) / gm;
+            put(e, m * a.step[e]);
+            if (active) mt.m[c * n + e] = m;
+        }
+        if (active) mt.mean[c * n + e] = 0.0, mt.M2[c * n + e] = 0.0;
+    }
+    sbase = sbase * exp(as.logsbar);
+    as.hbar = 0.0, as.logsbar = 0.0, as.s = sbase;
+    if (active && l == 0) mt.sbase[c] = sbase;
+}
+// what every *_metric entry point requires of `mt` next to check_adapt (which comes first: ad is not null here)
+inline int check_metric(const sx_sample_adapt *ad, const sx_sample_metric *mt) {
+    SX_REQUIRE(mt != nullptr, "sx_sample (metric): null metric args");
+    SX_REQUIRE(mt->nwin >= 0 && mt->nwin <= 8, "sx_sample (metric): nwin outside [0, 8]");
+    if (mt->nwin > 0) {
+        SX_REQUIRE(mt->sbase && mt->m && mt->mean && mt->M2, "sx_sample (metric): null metric state pointer");
+        SX_REQUIRE(mt->win_start >= 0, "sx_sample (metric): win_start is negative");
+        int64_t lo = mt->win_start;
+        for (int j = 0; j < mt->nwin; lo = mt->win_end[j++])
+            SX_REQUIRE(mt->win_end[j] > lo, "sx_sample (metric): the window ends do not increase from win_start");
+        SX_REQUIRE(lo <= ad->warmup, "sx_sample (metric): a window ends after the warm-up");
+    }
+    return 0;
 }
 // thinning: is sample `it` recorded, and in which row of xall / funall (rec_every < 2^31, it < maxiter < 2^31)
 __device__ __forceinline__ bool adapt_record(const sx_sample_adapt &ad, int64_t it, int64_t &row) {

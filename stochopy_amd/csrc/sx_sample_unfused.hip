@@ -42,26 +42,36 @@ inline Geometry chain_geometry(int64_t C, int n) {
 
 // ADAPT, here and below: sx_sample_adapt as the kernel's last argument (sx_sample.hpp; without it an empty struct that is never
 // read).  The propose and leap kernels need chain c's multiplier of a.step alone: ad.scale, 1.0 while nothing adapts.
-template <bool ADAPT>
-__device__ __forceinline__ double chain_scale(const AdaptArg<ADAPT> &ad, int64_t c) {
+// METRIC (sx_sample_metric, with ADAPT): element e of the chain's step is scale * eff, eff = m[c, e] * a.step[e] formed from
+// the chain's row of m in device memory (metric_eff) -- the product the resident kernels keep in LDS.
+template <bool ADAPT, bool METRIC>
+__device__ __forceinline__ double chain_scale(const AdaptArg<ADAPT, METRIC> &ad, int64_t c) {
     if constexpr (ADAPT)
         if (ad.warmup > 0) return ad.scale[c];
     return 1.0;
 }
+template <bool ADAPT, bool METRIC>
+__device__ __forceinline__ double unfused_step(const sx_sample_args &a, const AdaptArg<ADAPT, METRIC> &ad, double scale,
+                                               int64_t c, int e) {
+    if constexpr (METRIC)
+        return scale * metric_eff(a, ad.mt, c, e);
+    else
+        return chain_step<ADAPT>(a, scale, e);
+}
 
 // sample `it`: the proposal (it = 0: the initial point) -> prop (C, n); hmc: momentum -> pmom (C, n), its kinetic energy -> k0 (C)
-template <int LPR, bool ADAPT>
+template <int LPR, bool ADAPT, bool METRIC>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kernel(const sx_sample_args a, int64_t it,
                                                                                   double *__restrict__ prop,
                                                                                   double *__restrict__ pmom,
                                                                                   double *__restrict__ k0,
-                                                                                  const AdaptArg<ADAPT> ad) {
+                                                                                  const AdaptArg<ADAPT, METRIC> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l, k = a.k;
     const int64_t c = id.rowc;
     const bool active = id.active;
     // (sample 0 takes no step; its decide kernel writes the first multiplier)
-    const double scale = it > 0 ? chain_scale<ADAPT>(ad, c) : 1.0;
+    const double scale = it > 0 ? chain_scale<ADAPT, METRIC>(ad, c) : 1.0;
     const double *X = a.cur + c * n;
     double *U = prop + c * n;
     if (it == 0) {
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kerne
         int j0, j1;
         mcmc_block(it, n, k, (n + k - 1) / k, j0, j1);
         mcmc_propose<LPR>(
-            a, (uint32_t)c, it, X, l, j0, j1, [&](int e) { return chain_step<ADAPT>(a, scale, e); },
+            a, (uint32_t)c, it, X, l, j0, j1, [&](int e) { return unfused_step<ADAPT, METRIC>(a, ad, scale, c, e); },
             [&](int e, double v) {
                 if (active) U[e] = v;
             });
@@ -99,21 +109,21 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_propose_kerne
 }
 
 // one momentum step with the gradient G, and the position step behind it when `move` (hmc/_hmc.py:143-155)
-template <int LPR, bool ADAPT>
+template <int LPR, bool ADAPT, bool METRIC>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_leap_kernel(const sx_sample_args a, double coef, int move,
                                                                                double *__restrict__ q,
                                                                                double *__restrict__ pmom,
                                                                                const double *__restrict__ G,
-                                                                               const AdaptArg<ADAPT> ad) {
+                                                                               const AdaptArg<ADAPT, METRIC> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
     double *Q = q + c * n, *Pm = pmom + c * n;
     const double *g = G + c * n;
-    const double scale = chain_scale<ADAPT>(ad, c);
+    const double scale = chain_scale<ADAPT, METRIC>(ad, c);
     for (int e = l; e < n; e += LPR) {
         const double gv = g[e];
-        const double st = chain_step<ADAPT>(a, scale, e);
+        const double st = unfused_step<ADAPT, METRIC>(a, ad, scale, c, e);
         const double p = Pm[e] - (coef * st) * gv;
         const double qn = Q[e] + st * p;
         if (id.active) {
@@ -166,13 +176,13 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_fd_gradient_k
 }
 
 // the decision on sample `it` with the proposal's value fprop (C), and the chain's bookkeeping
-template <int LPR, bool ADAPT>
+template <int LPR, bool ADAPT, bool METRIC>
 __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel(const sx_sample_args a, int64_t it,
                                                                                  const double *__restrict__ prop,
                                                                                  const double *__restrict__ fprop,
                                                                                  const double *__restrict__ pmom,
                                                                                  const double *__restrict__ k0,
-                                                                                 const AdaptArg<ADAPT> ad) {
+                                                                                 const AdaptArg<ADAPT, METRIC> ad) {
     const RowIds<LPR> id(a.C);
     const int n = a.n, l = id.l;
     const int64_t c = id.rowc;
@@ -185,6 +195,10 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
     if (it == 0) {
         st.start(fU);
         if constexpr (ADAPT) as.start();
+        if constexpr (METRIC) {
+            double sbase;
+            metric_start<LPR>(a, ad.mt, c, l, id.active, sbase);
+        }
     } else {
         st.load(a, c);
         if constexpr (ADAPT) as.load(ad, c);
@@ -198,7 +212,16 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_decide_kernel
         }
         const bool feasible = !a.reject || row_in_box<LPR>(a, U, n, l);
         r = chain_decide(st, a, (uint32_t)c, it, mcmc, feasible, mcmc ? st.fcur - fU : ((st.fcur - fU) + K0) - K, fU);
-        if constexpr (ADAPT) adapt_update(as, ad.warmup, ad.target, it, feasible, r.dstat, st.nacc);
+        if constexpr (METRIC) {  // (the chain's state after this decision: cur is committed below; eff is formed from m)
+            const double *X = a.cur + c * n;
+            const bool accepted = r.accept;
+            double sbase = metric_load_sbase(ad.mt, c);
+            metric_update<LPR>(
+                a, ad, as, sbase, c, l, id.active, it, feasible, r.dstat, st.nacc,
+                [&](int e) { return accepted ? U[e] : X[e]; }, [](int, double) {});
+        } else if constexpr (ADAPT) {
+            adapt_update(as, ad.warmup, ad.target, it, feasible, r.dstat, st.nacc);
+        }
     }
     if (!id.active) return;
     bool record = a.xall != nullptr;
@@ -287,76 +310,94 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void sample_swap_kernel(c
 
 // What every entry point `who` does first, for its sample `it` (the entry points without one pass 0): sx_sample_run's
 // conditions on the arguments these kernels read, and those on `ad` for the adapting / thinning forms
-template <bool ADAPT = false>
-int check_entry(const char *who, const sx_sample_args *a, int64_t it, const sx_sample_adapt *ad = nullptr) {
-    return (check_sample_args(who, a, it, 1, false, false) || (ADAPT && check_adapt(a, ad))) ? -1 : 0;
+template <bool ADAPT = false, bool METRIC = false>
+int check_entry(const char *who, const sx_sample_args *a, int64_t it, const sx_sample_adapt *ad = nullptr,
+                const sx_sample_metric *mt = nullptr) {
+    return (check_sample_args(who, a, it, 1, false, false) || (ADAPT && check_adapt(a, ad)) || (METRIC && check_metric(ad, mt)))
+               ? -1
+               : 0;
 }
 
-// each plain entry point and its *_adapt form: one body
-template <bool ADAPT>
-int propose(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop, double *pmom,
+// each plain entry point, its *_adapt and its *_metric form: one body
+template <bool ADAPT, bool METRIC = false>
+int propose(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it, double *prop, double *pmom,
             double *k0, void *stream) {
-    if (check_entry<ADAPT>(who, a, it, ad)) return -1;
+    if (check_entry<ADAPT, METRIC>(who, a, it, ad, mt)) return -1;
     SX_SAMPLE_REQUIRE(prop != nullptr, "null proposal array");
     SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "hmc needs pmom and k0");
     const Geometry g = chain_geometry(a->C, a->n);
     Enqueue q((hipStream_t)stream);
-    SX_DISPATCH_LPR(a->n, return q.kernel(sample_propose_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
-                                          pmom, k0, adapt_arg<ADAPT>(ad)))
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_propose_kernel<LPR, ADAPT, METRIC>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
+                                          pmom, k0, adapt_arg<ADAPT, METRIC>(ad, mt)))
     return -1;
 }
 
-template <bool ADAPT>
-int leap(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q, double *pmom,
+template <bool ADAPT, bool METRIC = false>
+int leap(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, double coef, int move, double *q, double *pmom,
          const double *G, void *stream) {
-    if (check_entry<ADAPT>(who, a, 0, ad)) return -1;
+    if (check_entry<ADAPT, METRIC>(who, a, 0, ad, mt)) return -1;
     SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_HMC && q && pmom && G, "hmc with q, pmom and G");
     const Geometry g = chain_geometry(a->C, a->n);
     Enqueue sink((hipStream_t)stream);
-    SX_DISPATCH_LPR(a->n, return sink.kernel(sample_leap_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, coef, move, q,
-                                             pmom, G, adapt_arg<ADAPT>(ad)))
+    SX_DISPATCH_LPR(a->n, return sink.kernel(sample_leap_kernel<LPR, ADAPT, METRIC>, dim3(g.blocks), dim3(g.threads), 0, *a, coef, move, q,
+                                             pmom, G, adapt_arg<ADAPT, METRIC>(ad, mt)))
     return -1;
 }
 
-template <bool ADAPT>
-int decide(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
+template <bool ADAPT, bool METRIC = false>
+int decide(const char *who, const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it, const double *prop,
            const double *fprop, const double *pmom, const double *k0, void *stream) {
-    if (check_entry<ADAPT>(who, a, it, ad)) return -1;
+    if (check_entry<ADAPT, METRIC>(who, a, it, ad, mt)) return -1;
     SX_SAMPLE_REQUIRE(prop && fprop, "null proposal / value array");
     SX_SAMPLE_REQUIRE(a->method == SX_SAMPLE_MCMC || it == 0 || (pmom && k0), "hmc needs pmom and k0");
     const Geometry g = chain_geometry(a->C, a->n);
     Enqueue q((hipStream_t)stream);
-    SX_DISPATCH_LPR(a->n, return q.kernel(sample_decide_kernel<LPR, ADAPT>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
-                                          fprop, pmom, k0, adapt_arg<ADAPT>(ad)))
+    SX_DISPATCH_LPR(a->n, return q.kernel(sample_decide_kernel<LPR, ADAPT, METRIC>, dim3(g.blocks), dim3(g.threads), 0, *a, it, prop,
+                                          fprop, pmom, k0, adapt_arg<ADAPT, METRIC>(ad, mt)))
     return -1;
 }
 
 }  // namespace
 
 extern "C" int sx_sample_propose(const sx_sample_args *a, int64_t it, double *prop, double *pmom, double *k0, void *stream) {
-    return propose<false>("sx_sample_propose", a, nullptr, it, prop, pmom, k0, stream);
+    return propose<false>("sx_sample_propose", a, nullptr, nullptr, it, prop, pmom, k0, stream);
 }
 extern "C" int sx_sample_leap(const sx_sample_args *a, double coef, int move, double *q, double *pmom, const double *G,
                               void *stream) {
-    return leap<false>("sx_sample_leap", a, nullptr, coef, move, q, pmom, G, stream);
+    return leap<false>("sx_sample_leap", a, nullptr, nullptr, coef, move, q, pmom, G, stream);
 }
 extern "C" int sx_sample_decide(const sx_sample_args *a, int64_t it, const double *prop, const double *fprop,
                                 const double *pmom, const double *k0, void *stream) {
-    return decide<false>("sx_sample_decide", a, nullptr, it, prop, fprop, pmom, k0, stream);
+    return decide<false>("sx_sample_decide", a, nullptr, nullptr, it, prop, fprop, pmom, k0, stream);
 }
 
 // The adapting / thinning forms (sx_sample_adapt)
 extern "C" int sx_sample_propose_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, double *prop,
                                        double *pmom, double *k0, void *stream) {
-    return propose<true>("sx_sample_propose_adapt", a, ad, it, prop, pmom, k0, stream);
+    return propose<true>("sx_sample_propose_adapt", a, ad, nullptr, it, prop, pmom, k0, stream);
 }
 extern "C" int sx_sample_leap_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, double coef, int move, double *q,
                                     double *pmom, const double *G, void *stream) {
-    return leap<true>("sx_sample_leap_adapt", a, ad, coef, move, q, pmom, G, stream);
+    return leap<true>("sx_sample_leap_adapt", a, ad, nullptr, coef, move, q, pmom, G, stream);
 }
 extern "C" int sx_sample_decide_adapt(const sx_sample_args *a, const sx_sample_adapt *ad, int64_t it, const double *prop,
                                       const double *fprop, const double *pmom, const double *k0, void *stream) {
-    return decide<true>("sx_sample_decide_adapt", a, ad, it, prop, fprop, pmom, k0, stream);
+    return decide<true>("sx_sample_decide_adapt", a, ad, nullptr, it, prop, fprop, pmom, k0, stream);
+}
+
+// The forms with per-axis scales (sx_sample_metric)
+extern "C" int sx_sample_propose_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it,
+                                        double *prop, double *pmom, double *k0, void *stream) {
+    return propose<true, true>("sx_sample_propose_metric", a, ad, mt, it, prop, pmom, k0, stream);
+}
+extern "C" int sx_sample_leap_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, double coef,
+                                     int move, double *q, double *pmom, const double *G, void *stream) {
+    return leap<true, true>("sx_sample_leap_metric", a, ad, mt, coef, move, q, pmom, G, stream);
+}
+extern "C" int sx_sample_decide_metric(const sx_sample_args *a, const sx_sample_adapt *ad, const sx_sample_metric *mt, int64_t it,
+                                       const double *prop, const double *fprop, const double *pmom, const double *k0,
+                                       void *stream) {
+    return decide<true, true>("sx_sample_decide_metric", a, ad, mt, it, prop, fprop, pmom, k0, stream);
 }
 
 extern "C" int sx_sample_fd_rows(const sx_sample_args *a, const double *q, int axis0, int naxes, double *W, void *stream) {

@@ -1,5 +1,6 @@
 """Per-chain step-size adaptation in a warm-up, burn-in and thinning (options ``warmup``, ``target_accept``, ``burn``,
-``thin`` of ``sample.mcmc`` / ``sample.hmc``; csrc/sx_sample.hpp ``adapt_update``).  The checks need no device."""
+``thin`` of ``sample.mcmc`` / ``sample.hmc``; csrc/sx_sample.hpp ``adapt_update``) and per-axis scale adaptation in that
+warm-up (``metric="diag"``; csrc/sx_sample.hpp ``metric_update``).  The checks need no device."""
 import numpy as np
 
 OPTIONS = ("warmup", "target_accept", "burn", "thin")
@@ -8,6 +9,8 @@ OPTIONS = ("warmup", "target_accept", "burn", "thin")
 class Adapt:
     """The checked options of one run: ``warmup`` W, ``target`` (the acceptance the rule steers to), ``burn`` B, ``thin`` T
     and ``rows`` M = ceil((maxiter - B) / T), the rows of xall / funall per chain."""
+
+    windows = None  # metric="diag": (start, ends) of metric_windows(warmup); None without per-axis scales
 
     def __init__(self, warmup, target, burn, thin, maxiter):
         self.warmup, self.target, self.burn, self.thin = warmup, target, burn, thin
@@ -38,10 +41,10 @@ def refuse_with_temperatures(warmup, target_accept, burn, thin):
                          "their step nor thin what they record)")
 
 
-def check(warmup, target_accept, burn, thin, rng, maxiter, default_target):
-    """None when every option is at its default (the run then takes the plain path), else the checked ``Adapt``.  Every
-    message names its option; nothing here touches the device."""
-    names = given(warmup, target_accept, burn, thin)
+def check(warmup, target_accept, burn, thin, rng, maxiter, default_target, metric=None):
+    """None when every option is at its default (the run then takes the plain path), else the checked ``Adapt`` -- with
+    ``metric="diag"`` carrying its windows.  Every message names its option; nothing here touches the device."""
+    names = given(warmup, target_accept, burn, thin) + (["metric"] if metric is not None else [])
     if not names:
         return None
     warmup = _integer("warmup", warmup)
@@ -65,6 +68,43 @@ def check(warmup, target_accept, burn, thin, rng, maxiter, default_target):
         raise ValueError(f"burn is an integer in [0, maxiter - 1] = [0, {maxiter - 1}], not {burn}")
     if thin < 1:
         raise ValueError(f"thin is an integer >= 1, not {thin}")
+    check_metric(metric)
     if rng != "philox":
         raise ValueError(f'{" / ".join(names)} need rng="philox": the adapting and thinning kernels make their draws themselves')
-    return Adapt(warmup, default_target if target_accept is None else target_accept, burn, thin, maxiter)
+    adapt = Adapt(warmup, default_target if target_accept is None else target_accept, burn, thin, maxiter)
+    if metric is not None:
+        if warmup < METRIC_MIN_WARMUP:
+            raise ValueError(f'metric="diag" learns the scales in the warm-up: it needs warmup >= {METRIC_MIN_WARMUP}, not {warmup}')
+        adapt.windows = metric_windows(warmup)
+    return adapt
+
+
+METRIC_MIN_WARMUP = 20
+METRIC_MAX_WINDOWS = 8  # (sx_sample_metric.win_end; the schedule below makes at most 4)
+
+
+def metric_windows(warmup):
+    """``(start, ends)``: the windows (start, ends[0]], (ends[0], ends[1]], ... of a warm-up of ``warmup >= 20`` samples in
+    which the per-axis scales are learnt.  The first 15 % of the warm-up settle the step size alone and the last 10 % settle
+    it for the final scales; between them J doubling windows, J the largest of 4 ... 1 whose first window has 8 samples or
+    more, the last one stretched to the end.  warmup 1000: 150 and (200, 300, 500, 900)."""
+    start = (15 * warmup) // 100
+    end = warmup - (10 * warmup) // 100
+    span = end - start
+    J = next(j for j in (4, 3, 2, 1) if span // (2 ** j - 1) >= 8)
+    first = span // (2 ** J - 1)
+    ends = [start + first * (2 ** j - 1) for j in range(1, J + 1)]
+    ends[-1] = end
+    return start, tuple(ends)
+
+
+def check_metric(metric, with_temperatures=False):
+    """``metric=None | "diag"``, after the other options' own checks; every message names ``metric``."""
+    if metric is None:
+        return
+    if not isinstance(metric, str):
+        raise TypeError(f'metric is None or "diag", not {type(metric).__name__}')
+    if metric != "diag":
+        raise ValueError(f'unknown metric {metric!r}: None or "diag" (per-axis scales learnt in the warm-up)')
+    if with_temperatures:
+        raise ValueError("metric: not served together with temperatures (the tempered kernels do not adapt)")

@@ -171,9 +171,10 @@ class _Unfused:
     propose -> fun -> decide; hmc puts nleap + 2 rounds of (gradient, leap) in front of fun.  The chains' state stays in the
     arrays of ``a``, as between the launches of a fused run with a callback."""
 
-    def __init__(self, s, ctx, a, ad=None):
+    def __init__(self, s, ctx, a, ad=None, mt=None):
         self.s, self.ctx, self.a, self.L = s, ctx, a, ctx.L
-        self.ad = ad  # SxSampleAdapt: propose / leap / decide then go through their *_adapt forms
+        self.ad = ad  # SxSampleAdapt: propose / leap / decide then go through their *_adapt forms,
+        self.mt = mt  # with SxSampleMetric behind it through their *_metric forms
         Cn, n = s.chains, s.ndim
         self.hmc = s.method == _lib.SX_SAMPLE_HMC
         self.prop = ctx.empty((Cn, n))
@@ -192,7 +193,9 @@ class _Unfused:
     def adapting(self, name, *args):
         if self.ad is None:
             return self.call(name, *args)
-        self.call(name + "_adapt", C.byref(self.ad), *args)
+        if self.mt is None:
+            return self.call(name + "_adapt", C.byref(self.ad), *args)
+        self.call(name + "_metric", C.byref(self.ad), C.byref(self.mt), *args)
 
     def gradient(self):
         s, ptr = self.s, _device.ptr
@@ -251,6 +254,20 @@ def chain_args(ctx, s, rows, chains=None, x0=None, draws=None):
     return dev, a
 
 
+def metric_args(ctx, dev, chains, ndim, start, ends):
+    """The SxSampleMetric of a run whose windows are (start, ends[0]], (ends[0], ends[1]], ...; its device arrays go into
+    ``dev`` (the launch that generates sample 0 writes them)."""
+    mt = _lib.SxSampleMetric()
+    dev["sbase"] = ctx.empty((chains,))
+    dev.update({name: ctx.empty((chains, ndim)) for name in ("m", "mean", "M2")})
+    for name in ("sbase", "m", "mean", "M2"):
+        setattr(mt, name, _device.ptr(dev[name]))
+    mt.nwin, mt.win_start = len(ends), start
+    for j, end in enumerate(ends):
+        mt.win_end[j] = end
+    return mt
+
+
 def run(s):
     L = _lib.lib()
     legacy = s.rng == "numpy-legacy"
@@ -275,6 +292,9 @@ def run(s):
                 setattr(ad, name, _device.ptr(dev.get(name)))
             ad.warmup, ad.rec_start, ad.rec_rows, ad.target = s.adapt.warmup, s.adapt.burn, rows, s.adapt.target
             ad.rec_every = min(s.adapt.thin, m)  # (the same rows; the library takes rec_every < 2^31)
+        mt = None
+        if s.adapt is not None and s.adapt.windows is not None:  # metric="diag": per-axis scales learnt in these windows
+            mt = metric_args(ctx, dev, Cn, n, *s.adapt.windows)
 
         def host(name):
             return dev[name].cpu().numpy()
@@ -282,11 +302,14 @@ def run(s):
         def launch(i, steps):
             if ad is None:
                 _lib.check(L.sx_sample_run(C.byref(a), i, steps, ctx.stream_ptr), "sx_sample_run")
+            elif mt is not None:
+                _lib.check(L.sx_sample_run_metric(C.byref(a), C.byref(ad), C.byref(mt), i, steps, ctx.stream_ptr),
+                           "sx_sample_run_metric")
             else:
                 _lib.check(L.sx_sample_run_adapt(C.byref(a), C.byref(ad), i, steps, ctx.stream_ptr), "sx_sample_run_adapt")
 
         if s.external is not None:
-            advance = _Unfused(s, ctx, a, ad).sample
+            advance = _Unfused(s, ctx, a, ad, mt).sample
         else:
             def advance(i):
                 launch(i, 1)
@@ -333,6 +356,8 @@ def run(s):
         warm = s.adapt is not None and s.adapt.warmup > 0
         if warm:
             scale, nacc_warm = host("scale"), host("nacc_warm")
+        if mt is not None:
+            metric = host("m")
     if stream is not None:
         stream.sync_back()  # numpy's global stream is where the reference would leave it
     b = int(np.argmin(fbest))  # (numpy's rule: the first NaN, else the first minimum; all inf: chain 0)
@@ -350,6 +375,9 @@ def run(s):
         res["stepsizes"] = scale[0] if Cn == 1 else scale
         res["accept_ratios_sampling"] = sampling[0] if Cn == 1 else sampling
         res["warmup"] = s.adapt.warmup
+    if mt is not None:
+        res["metric"] = metric[0] if Cn == 1 else metric
+        res["metric_windows"] = s.adapt.windows[1]
     if s.return_all:
         res["xall"] = xall[0] if Cn == 1 else xall
         res["funall"] = funall[0] if Cn == 1 else funall

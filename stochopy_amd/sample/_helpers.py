@@ -13,7 +13,7 @@ _sampler_map = {}
 class SampleResult(OptimizeResult):
     """Sampling result: keys x, fun, nit, accept_ratio (+ nfev for hmc, xall / funall with ``return_all``, and
     accept_ratios with more than one chain; with ``temperatures``: accept_ratios per ladder and rung, temperatures and
-    swap_ratios; with ``warmup``: stepsizes, accept_ratios_sampling and warmup)."""
+    swap_ratios; with ``warmup``: stepsizes, accept_ratios_sampling and warmup; with ``metric``: metric and metric_windows)."""
 
 
 def register(name, sample):
@@ -50,6 +50,9 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
       adapts a per-chain multiplier of ``stepsize`` over samples 1 ... W (dual averaging towards ``target_accept``) and
       freezes it; ``xall`` / ``funall`` hold samples ``burn, burn + thin, ...`` only (``burn`` defaults to ``warmup``).
       The result gains ``stepsizes``, ``accept_ratios_sampling`` and ``warmup``.  See ``sample.mcmc``.
+    - ``metric="diag"`` (``warmup >= 20``, ``rng="philox"``; not with ``temperatures``): every chain also learns one scale
+      per axis in windows of the warm-up, from the variance of its own samples, for targets whose axes differ in width.
+      The result gains ``metric`` and ``metric_windows``.  See ``sample.mcmc``.
 
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """

@@ -30,6 +30,7 @@ def sample(
     target_accept=None,
     burn=None,
     thin=1,
+    metric=None,
 ):
     """Sample the variable space with Hamiltonian Monte-Carlo (``hmc/_hmc.py:13-200``), ``chains`` independent
     chains in one kernel.
@@ -61,9 +62,15 @@ def sample(
     burn-in and thinning, as ``sample.mcmc`` describes them; the multiplier scales the momentum and the position steps
     alike, the default ``target_accept`` is 0.65, and a trajectory whose ``d`` is NaN counts as rejected in the
     adaptation (it shrinks the step) while the decision itself stays what it is.  They work with every ``jac``.
+
+    ``metric="diag"`` (``warmup >= 20``, ``rng="philox"``): per-axis scales learnt in the warm-up, as ``sample.mcmc``
+    describes them.  The momentum and the position steps read ``s_c * m_c[e] * stepsize[e]``; the momenta stay ``randn(ndim)``
+    and the kinetic energy ``0.5 sum p^2`` -- leap-frog in coordinates rescaled per axis, which is HMC with the diagonal mass
+    matrix ``1 / m^2``, so the decision rule is untouched.  It works with every ``jac``.
     """
     if temperatures is not None or swap_every is not None:
         _adapt.refuse_with_temperatures(warmup, target_accept, burn, thin)
+        _adapt.check_metric(metric, with_temperatures=True)
         raise ValueError('temperatures / swap_every (parallel tempering) are served by method="mcmc" only')
     run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                         backend, nleap=nleap)
@@ -86,7 +93,7 @@ def sample(
     elif own_gradient:
         run.gradient = _chains.AutogradGradient(run.external)
     run.fd_step = float(finite_diff_abs_step)
-    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.65)
+    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.65, metric)
     return _chains.run(run)
 
 

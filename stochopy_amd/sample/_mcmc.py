@@ -27,6 +27,7 @@ def sample(
     target_accept=None,
     burn=None,
     thin=1,
+    metric=None,
 ):
     """Sample the variable space with the Metropolis-Hastings algorithm (``mcmc/_mcmc.py:13-161``), ``chains``
     independent chains in one kernel.
@@ -74,11 +75,24 @@ def sample(
     ``accept_ratios_sampling`` (``(C,)``: accepted samples after the warm-up over ``maxiter - 1 - W``; 0.0 when there is
     none) -- both scalars for one chain -- and ``warmup``.  The callback is called once per generated sample as before;
     its state's ``xall`` / ``funall`` hold the recorded rows among the samples before the newest.
+
+    Per-axis scales in the warm-up (no counterpart in the reference): ``metric="diag"`` (default ``None``; needs
+    ``warmup >= 20`` and ``rng="philox"``; not with ``temperatures``).  One multiplier per chain cannot serve a target whose
+    axes have different widths: it settles on the narrowest.  With ``"diag"`` chain c also carries ``m_c[e]`` (1.0 at the
+    start, geometric mean 1) and steps by ``s_c * m_c[e] * stepsize[e]``.  The warm-up is cut as Stan cuts it: 15 % for the
+    step size alone, then up to four doubling windows (``_adapt.metric_windows``; W = 1000: ends 200, 300, 500, 900), 10 % at
+    the end.  In a window the chain accumulates the variance of its own samples per axis (Welford); at a window's end
+    ``m`` becomes the square root of that variance, shrunk towards ``1e-3`` of the squared half-width of the box with weight
+    ``5 / (N + 5)``, over its geometric mean -- a chain whose variance is not finite or not positive on some axis keeps its
+    ``m`` -- and the dual averaging restarts from its average.  Chains stay independent of each other and of ``chains``.  The
+    result gains ``metric`` (``(C, ndim)``, ``(ndim,)`` for one chain: the final ``m``) and ``metric_windows`` (the ends);
+    ``stepsizes`` is the final multiplier ``s_c``, so the step in use is ``stepsizes * metric * stepsize``.
     """
     if temperatures is not None or swap_every is not None:
         from . import _temper
 
         _adapt.refuse_with_temperatures(warmup, target_accept, burn, thin)
+        _adapt.check_metric(metric, with_temperatures=True)
         ladder, every = _temper.check_ladder(temperatures, swap_every, rng)
         run = _chains.Setup(fun, bounds, x0, args, maxiter, stepsize, seed, constraints, return_all, callback, chains, rng,
                             backend)
@@ -95,7 +109,8 @@ def sample(
         raise ValueError()
     run.method = _lib.SX_SAMPLE_MCMC
     run.k = max(1, int(perc * run.ndim))
-    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.44 if run.k == 1 else 0.234)
+    run.adapt = _adapt.check(warmup, target_accept, burn, thin, rng, run.maxiter, 0.44 if run.k == 1 else 0.234,
+                             metric)
     return _chains.run(run)
 
 

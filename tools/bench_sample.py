@@ -28,6 +28,14 @@ plain configuration's, ratio of the medians) and with `mcmc+xall` keeping every 
 its line carries the bytes stored per second and `vs_plain` too).
 
     python tools/bench_sample.py --adapt --no-cpu [--rounds 5] [--out FILE]
+
+--metric: what the per-axis scales cost (sx_sample_run_metric, metric="diag").  `mcmc` and `hmc analytic`, plain, with
+warmup = maxiter // 2 alone and with the scales learnt in the windows of that warm-up, take turns by the same protocol.  The
+metric line carries `vs_warmup` (samples / s over the whole call, over the warm-up-only line's), the chains per workgroup of
+either form, and `sampling_vs_warmup`: the same ratio over the sampling phase alone -- each form's whole run minus a run that
+stops after its warm-up (maxiter = warmup + 1), timed the same way.
+
+    python tools/bench_sample.py --metric --no-cpu [--rounds 5] [--out profiles/sample_metric_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -140,6 +148,36 @@ class AdaptRun(DeviceRun):
                    "sx_sample_run_adapt")
 
 
+class MetricRun(AdaptRun):
+    """The same configuration through sx_sample_run_metric, as stochopy_amd.sample launches it with metric="diag"."""
+
+    def __init__(self, ctx, method, ndim, chains, o, warmup):
+        from stochopy_amd.sample import _adapt
+        from stochopy_amd.sample._chains import metric_args
+
+        super().__init__(ctx, method, ndim, chains, o, warmup=warmup, burn=min(warmup, o["maxiter"] - 1))
+        self.mt = metric_args(ctx, self.dev, chains, ndim, *_adapt.metric_windows(warmup))
+
+    def launch(self):
+        from stochopy_amd import _lib
+
+        _lib.check(self.L.sx_sample_run_metric(C.byref(self.a), C.byref(self.ad), C.byref(self.mt), 0, self.m,
+                                               self.ctx.stream_ptr), "sx_sample_run_metric")
+
+
+def metric_chains_per_workgroup(method, jac, ndim):
+    """Chains per workgroup of the form with per-axis scales: csrc/sx_sample.hpp sample_waves with the row that holds eff --
+    the largest power of two of waves (<= 8 waves, <= 16 chains) whose rows fit 64 KiB."""
+    lpr = 16 if ndim <= 64 else 32 if ndim <= 128 else 64
+    stride = ndim + 8  # (gen_row_stride for ndim <= 256, the benchmark's range)
+    row = {"mcmc": ndim + stride, "analytic": 2 * ndim + stride, None: 2 * ndim + 3 * stride}[method if method == "mcmc" else jac]
+    row = (row + ndim) * 8
+    rpw, w = 64 // lpr, 1
+    while 2 * w <= 8 and 2 * w * rpw <= 16 and 2 * w * rpw * row <= 64 * 1024:
+        w *= 2
+    return w * rpw
+
+
 def cpu_rate(method, ndim, o):
     """Samples per second of one chain on one core, and what ran."""
     o = dict(o, seed=3)
@@ -174,6 +212,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--tempered", action="store_true", help="the plain mcmc kernel next to ladders of 16 replicas")
     ap.add_argument("--adapt", action="store_true", help="the plain configurations next to a warm-up and to thin=10")
+    ap.add_argument("--metric", action="store_true", help="plain, warm-up alone and warm-up with per-axis scales")
     args = ap.parse_args()
     from stochopy_amd import _device
 
@@ -199,6 +238,33 @@ def main():
         method, ndim, o = by_tag["mcmc+xall"]
         runs.append(("mcmc+xall thin=10", method, ndim, dict(o, thin=10), AdaptRun(ctx, method, ndim, args.chains, o, thin=10)))
         plain_of["mcmc+xall thin=10"] = "mcmc+xall"
+    warm_of, short_of = {}, {}
+    if args.metric:
+        from stochopy_amd import _lib
+
+        args.no_cpu = True
+        by_tag = {tag: (method, ndim, o) for tag, method, ndim, o in CONFIGS}
+        runs = [r for r in runs if r[0] in ("mcmc", "hmc analytic")]
+        for tag in ("mcmc", "hmc analytic"):
+            method, ndim, o = by_tag[tag]
+            W = o["maxiter"] // 2
+            short = dict(o, maxiter=W + 1)  # the run that stops after its warm-up: what the sampling phase is measured against
+            for kind in ("warmup", "warmup+metric"):
+                for which, oo in (("", o), (" (warm-up only)", short)):
+                    if kind == "warmup":
+                        run = AdaptRun(ctx, method, ndim, args.chains, oo, warmup=W, burn=min(W, oo["maxiter"] - 1))
+                    else:
+                        run = MetricRun(ctx, method, ndim, args.chains, oo, warmup=W)
+                    runs.append((f"{tag} {kind}={W}{which}", method, ndim, dict(oo, warmup=W), run))
+                    plain_of[f"{tag} {kind}={W}{which}"] = tag
+            warm_of[f"{tag} warmup+metric={W}"] = f"{tag} warmup={W}"
+            for kind in ("warmup", "warmup+metric"):
+                short_of[f"{tag} {kind}={W}"] = f"{tag} {kind}={W} (warm-up only)"
+            jac = _lib.SX_JAC_ANALYTIC if o.get("jac") == "analytic" else _lib.SX_JAC_FINITE_DIFF
+            meth = _lib.SX_SAMPLE_MCMC if method == "mcmc" else _lib.SX_SAMPLE_HMC
+            print(json.dumps({"config": tag, "ndim": ndim,
+                              "chains_per_workgroup": ctx.L.sx_sample_chains_per_workgroup(meth, jac, ndim),
+                              "chains_per_workgroup_metric": metric_chains_per_workgroup(method, o.get("jac"), ndim)}), flush=True)
     launches = {}
     for tag, *_, r in runs:
         r.timed()  # warm-up: code object load, first touch of xall
@@ -208,6 +274,7 @@ def main():
         for tag, *_, r in runs:
             times[tag].append(r.timed(launches[tag]))
     lines = []
+    runs_maxiter = {tag: o["maxiter"] for tag, _, _, o, _ in runs}
     for tag, method, ndim, o, r in runs:
         ts = np.array(times[tag])
         line = {"config": tag, "method": method, "ndim": ndim, "chains": args.chains, "maxiter": o["maxiter"],
@@ -219,7 +286,11 @@ def main():
             line["vs_plain"] = float(np.median(times[runs[0][0]])) / float(np.median(ts)) * r.samples / runs[0][4].samples
         if tag in plain_of:
             line.update({k: o[k] for k in ("warmup", "thin") if k in o})
-            line["vs_plain"] = float(np.median(times[plain_of[tag]])) / float(np.median(ts))
+            line["vs_plain"] = float(np.median(times[plain_of[tag]])) / float(np.median(ts)) * o["maxiter"] / runs_maxiter[plain_of[tag]]
+        if tag in warm_of:
+            med = {t: float(np.median(times[t])) for t in times}
+            line["vs_warmup"] = med[warm_of[tag]] / med[tag]
+            line["sampling_vs_warmup"] = (med[warm_of[tag]] - med[short_of[warm_of[tag]]]) / (med[tag] - med[short_of[tag]])
         if r.stored:
             line["stored_bytes_per_s"] = r.stored / float(np.median(ts))
             line["share_of_hbm_peak"] = line["stored_bytes_per_s"] / HBM_PEAK
