@@ -677,7 +677,7 @@ void sx_mt_set_state(sx_mt *g, const uint32_t *key, int pos, int has_gauss, doub
  *   the reference's fmin / imin), fmin / imin (C) numpy's argmin over the samples so far (first NaN wins),
  *   xbest (C,n) the sample the method reports as x: iacc's for mcmc, imin's for hmc.
  * ------------------------------------------------------------------------- */
-enum { SX_SAMPLE_MCMC = 0, SX_SAMPLE_HMC = 1 };
+enum { SX_SAMPLE_MCMC = 0, SX_SAMPLE_HMC = 1, SX_SAMPLE_ENSEMBLE = 2 /* the sx_sample_ensemble_* entry points only */ };
 enum { SX_JAC_FINITE_DIFF = 0, SX_JAC_ANALYTIC = 1 };
 
 typedef struct sx_sample_args {
@@ -838,6 +838,40 @@ int sx_sample_decide_tempered(const sx_sample_args *a, int64_t it, const double 
  * fcur and the best values of a->..., nswap as above).  At odd j it writes row `it` of xall / funall (the state of rung 0
  * after the event).  No launch when no rung has a partner (K = 2, even j). */
 int sx_sample_swap(const sx_sample_args *a, int64_t it, int64_t j, const double *beta, int K, int64_t *nswap, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * The affine-invariant ensemble sampler (Goodman & Weare 2010: the stretch move; csrc/sx_sample_ensemble.hip): C ensembles
+ * of W device-resident walkers.  No counterpart in the reference.  No step size, no gradient: a walker moves along the line
+ * through itself and a walker of the other half of its ensemble, so the sampler performs alike on p(x) and p(Ax + b).
+ * W is even, W >= 4 and W >= 2 n; h = W / 2.  Walker w of ensemble g is replica q = g W + w, which takes the chain index's
+ * place in every draw and in the per-chain arrays (a->C = C*W, every one that long; a->method = SX_SAMPLE_ENSEMBLE,
+ * a->rng = SX_RNG_PHILOX; step, k, nleap, jac, fd_step, normals and logu are not read; x0 is NULL or one row per replica).
+ * Sample 0 is the initial state.  Sample it >= 1 is two half-sweeps: half 0 proposes the walkers [0, h) against the walkers
+ * [h, W), half 1 the walkers [h, W) against [0, h) as half 0 left them.  The active walker q, with (d0, d1) the two doubles of
+ * Philox (slot 0, row q, gen it, purpose 15), base the first walker of the other half and a = stretch:
+ *     j = base + min(h - 1, (int)(d0 * h));   z = ((a - 1) * d1 + 1)^2 / a;   Y[e] = X_j[e] + z * (X_q[e] - X_j[e])
+ *     d = (n - 1) * log(z) + (fcur_q - f(Y));   accepted when  min(0, d) > log(u)   (a NaN d accepts)
+ * u the acceptance draw of (q, it) (purpose 12); with reject a Y outside [lower, upper] is rejected without that draw and
+ * nfeas counts the others.  facc / iacc / fmin / imin / xbest follow the mcmc rule per walker.
+ * xall (C, maxiter, W, n) / funall (C, maxiter, W): row ((g maxiter + it) W + w).
+ * ------------------------------------------------------------------------- */
+/* samples [it0, it0 + steps) of every ensemble in ONE launch, one workgroup per ensemble, the walkers in its LDS; it0 = 0
+ * starts them.  A run cut into launches is the same run, bit for bit.  Requires 0 < sx_sample_ensemble_lds_bytes(W, n) <=
+ * 160 KiB and stretch finite and > 1 */
+int sx_sample_ensemble_run(const sx_sample_args *a, int W, double stretch, int64_t it0, int64_t steps, void *stream);
+/* HOST only: the dynamic LDS of an ensemble's workgroup, 8 (W n + W + rows (n + 8)) bytes with rows = RPW * min(cap, ceil(h / RPW))
+ * row groups, RPW = 4 (n <= 64) or 2 (n <= 128) rows per wavefront and cap = 4 or 8 wavefronts; -1 for a shape the launch does
+ * not serve (W odd, < 4 or < 2 n; n < 1 or n > 128) */
+int sx_sample_ensemble_lds_bytes(int W, int n);
+/* Around a caller-supplied objective, sample 0:  propose(it = 0) -> fprop = fun(prop) on (C*W, n) -> decide(it = 0)
+ * and sample it >= 1, for half = 0, 1:           propose -> fprop = fun(prop) on (C*h, n) -> decide
+ * Row g h + i of prop / fprop / logzf belongs to walker half * h + i of ensemble g; logzf (C*h) DEVICE takes the factors
+ * (n - 1) * log(z) from propose to decide (not used at it = 0, may be NULL there).  The walkers live in a->cur; any n the
+ * samplers serve.  With bit-identical objective values this is sx_sample_ensemble_run's run, bit for bit. */
+int sx_sample_ensemble_propose(const sx_sample_args *a, int W, double stretch, int64_t it, int half, double *prop,
+                               double *logzf, void *stream);
+int sx_sample_ensemble_decide(const sx_sample_args *a, int W, int64_t it, int half, const double *prop, const double *fprop,
+                              const double *logzf, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).

@@ -112,7 +112,7 @@ class SxCmaArgs(C.Structure):
     ]
 
 
-SX_SAMPLE_MCMC, SX_SAMPLE_HMC = 0, 1
+SX_SAMPLE_MCMC, SX_SAMPLE_HMC, SX_SAMPLE_ENSEMBLE = 0, 1, 2
 SX_JAC_FINITE_DIFF, SX_JAC_ANALYTIC = 0, 1
 
 
@@ -300,6 +300,10 @@ PROTOTYPES = {
     "sx_sample_tempered_max_rungs": (C.c_int, [C.c_int]),
     "sx_sample_decide_tempered": (C.c_int, [C.POINTER(SxSampleArgs), i64, vp, vp, vp, C.c_int, C.c_int, vp]),
     "sx_sample_swap": (C.c_int, [C.POINTER(SxSampleArgs), i64, i64, vp, C.c_int, vp, vp]),
+    "sx_sample_ensemble_run": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, f64, i64, i64, vp]),
+    "sx_sample_ensemble_lds_bytes": (C.c_int, [C.c_int, C.c_int]),
+    "sx_sample_ensemble_propose": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, f64, i64, C.c_int, vp, vp, vp]),
+    "sx_sample_ensemble_decide": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, i64, C.c_int, vp, vp, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_sweep_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp, vp, vp, vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),

@@ -178,6 +178,7 @@ enum : uint32_t {
     kPurposeSampleAccept = 12,   // the acceptance uniform: slot 0, first double of the call
     kPurposeSampleInit = 13,     // the initial point (gen 0): the uniform of element e
     kPurposeSampleSwap = 14,     // parallel tempering: the exchange uniform of a pair: slot 0, row = the LOWER rung's replica, first double
+    kPurposeSampleStretch = 15,  // ensemble sampler: slot 0, row = the active walker's replica: first double the partner, second the stretch
 };
 
 // Element e of a row sits in lane l = e % LPR of the row's lanes at step q = e / LPR (LPR a power of two).

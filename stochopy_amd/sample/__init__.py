@@ -1,5 +1,6 @@
 """Samplers behind stochopy's ``sample`` API: Metropolis-Hastings and Hamiltonian Monte-Carlo with many independent,
 device-resident chains (reference: stochopy/sample)."""
+from ._ensemble import sample as ensemble
 from ._helpers import SampleResult, sample
 from ._hmc import sample as hmc
 from ._mcmc import sample as mcmc
@@ -7,6 +8,7 @@ from ._mcmc import sample as mcmc
 __all__ = [
     "SampleResult",
     "sample",
+    "ensemble",
     "hmc",
     "mcmc",
 ]

@@ -8,6 +8,8 @@ from ..optimize._helpers import OptimizeResult
 __all__ = ["SampleResult", "sample", "register"]
 
 _sampler_map = {}
+# this backend's own methods (no counterpart in the reference): consulted after _sampler_map
+_own_sampler_map = {}
 
 
 class SampleResult(OptimizeResult):
@@ -19,6 +21,11 @@ class SampleResult(OptimizeResult):
 def register(name, sample):
     """Register a sampler under ``method=name`` (reference _helpers.py:36-38)."""
     _sampler_map[name] = sample
+
+
+def register_own(name, sample):
+    """Register one of this backend's own samplers under ``method=name``."""
+    _own_sampler_map[name] = sample
 
 
 def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=None):
@@ -54,8 +61,15 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
       per axis in windows of the warm-up, from the variance of its own samples, for targets whose axes differ in width.
       The result gains ``metric`` and ``metric_windows``.  See ``sample.mcmc``.
 
+    ``method="ensemble"`` (this backend's own; ``rng="philox"``): the affine-invariant ensemble sampler -- ``chains``
+    ensembles of ``walkers`` walkers, no step size, no gradient.  See ``sample.ensemble``.
+
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """
     options = options if options else {}
+    if method not in _sampler_map and method in _own_sampler_map:
+        sampler = _own_sampler_map[method]
+    else:
+        sampler = _sampler_map[method]
 
-    return _sampler_map[method](fun=fun, bounds=bounds, x0=x0, args=args, callback=callback, **options)
+    return sampler(fun=fun, bounds=bounds, x0=x0, args=args, callback=callback, **options)

@@ -36,6 +36,13 @@ either form, and `sampling_vs_warmup`: the same ratio over the sampling phase al
 stops after its warm-up (maxiter = warmup + 1), timed the same way.
 
     python tools/bench_sample.py --metric --no-cpu [--rounds 5] [--out profiles/sample_metric_bench.jsonl]
+
+--ensemble: the affine-invariant ensemble sampler (csrc/sx_sample_ensemble.hip, method="ensemble"): rosenbrock, return_all off,
+maxiter 300, ndim 32 with 256 ensembles of 64 walkers and ndim 64 with 128 ensembles of 128 walkers, each taking turns by the same
+protocol with the plain mcmc kernel (perc 1.0) on as many chains as there are walkers at the same ndim.  samples / s counts every
+walker's samples; `vs_plain` is the ratio of the medians.  --chains is not used.  No CPU side.
+
+    python tools/bench_sample.py --ensemble [--rounds 5] [--out profiles/sample_ensemble_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -116,6 +123,28 @@ class TemperedRun(DeviceRun):
         _lib.check(self.L.sx_sample_tempered_run(C.byref(self.a), _device.ptr(self.beta), self.K, self.swap_every,
                                                  _device.ptr(self.nswap), 0, self.m, self.ctx.stream_ptr),
                    "sx_sample_tempered_run")
+
+
+class EnsembleRun(DeviceRun):
+    """`ensembles` ensembles of W walkers, launched as stochopy_amd.sample does with method="ensemble"."""
+
+    def __init__(self, ctx, ndim, ensembles, W, o, stretch=2.0):
+        from stochopy_amd import _lib
+
+        super().__init__(ctx, "mcmc", ndim, ensembles * W, o)
+        self.a.method = _lib.SX_SAMPLE_ENSEMBLE
+        self.W, self.stretch = W, stretch
+        self.lds = ctx.L.sx_sample_ensemble_lds_bytes(W, ndim)
+
+    def launch(self):
+        from stochopy_amd import _lib
+
+        _lib.check(self.L.sx_sample_ensemble_run(C.byref(self.a), self.W, self.stretch, 0, self.m, self.ctx.stream_ptr),
+                   "sx_sample_ensemble_run")
+
+
+ENSEMBLE_SHAPES = [(32, 64, 256), (64, 128, 128)]  # (ndim, walkers, ensembles)
+ENSEMBLE_OPTIONS = {"maxiter": 300, "stepsize": 0.05, "perc": 1.0, "return_all": False}
 
 
 class AdaptRun(DeviceRun):
@@ -213,11 +242,22 @@ def main():
     ap.add_argument("--tempered", action="store_true", help="the plain mcmc kernel next to ladders of 16 replicas")
     ap.add_argument("--adapt", action="store_true", help="the plain configurations next to a warm-up and to thin=10")
     ap.add_argument("--metric", action="store_true", help="plain, warm-up alone and warm-up with per-axis scales")
+    ap.add_argument("--ensemble", action="store_true", help="the ensemble sampler next to the plain mcmc kernel on as many rows")
     args = ap.parse_args()
     from stochopy_amd import _device
 
     ctx = _device.Context()
-    if args.tempered:
+    ensemble_of = {}
+    if args.ensemble:
+        args.no_cpu = True
+        runs, o = [], ENSEMBLE_OPTIONS
+        for ndim, W, ensembles in ENSEMBLE_SHAPES:
+            plain, tag = f"mcmc ndim={ndim} chains={ensembles * W}", f"ensemble ndim={ndim} W={W} ensembles={ensembles}"
+            runs.append((plain, "mcmc", ndim, o, DeviceRun(ctx, "mcmc", ndim, ensembles * W, o)))
+            runs.append((tag, "ensemble", ndim, dict(o, walkers=W, ensembles=ensembles, stretch=2.0),
+                         EnsembleRun(ctx, ndim, ensembles, W, o)))
+            ensemble_of[tag] = plain
+    elif args.tempered:
         args.no_cpu = True
         tag, method, ndim, o = CONFIGS[0]
         runs = [(tag, method, ndim, o, DeviceRun(ctx, method, ndim, args.chains, o))]
@@ -277,13 +317,17 @@ def main():
     runs_maxiter = {tag: o["maxiter"] for tag, _, _, o, _ in runs}
     for tag, method, ndim, o, r in runs:
         ts = np.array(times[tag])
-        line = {"config": tag, "method": method, "ndim": ndim, "chains": args.chains, "maxiter": o["maxiter"],
+        line = {"config": tag, "method": method, "ndim": ndim, "chains": r.samples // r.m, "maxiter": o["maxiter"],
                 "seconds_median": float(np.median(ts)), "seconds_min": float(ts.min()), "seconds_max": float(ts.max()),
                 "samples_per_s": r.samples / float(np.median(ts)),
                 "samples_per_s_spread": [r.samples / float(ts.max()), r.samples / float(ts.min())], "rounds": args.rounds, "launches_per_round": launches[tag]}
         if args.tempered:
             line.update({k: o[k] for k in ("ladders", "K", "swap_every") if k in o})
             line["vs_plain"] = float(np.median(times[runs[0][0]])) / float(np.median(ts)) * r.samples / runs[0][4].samples
+        if tag in ensemble_of:
+            line.update({k: o[k] for k in ("walkers", "ensembles", "stretch")})
+            line["lds_bytes"] = r.lds
+            line["vs_plain"] = float(np.median(times[ensemble_of[tag]])) / float(np.median(ts))
         if tag in plain_of:
             line.update({k: o[k] for k in ("warmup", "thin") if k in o})
             line["vs_plain"] = float(np.median(times[plain_of[tag]])) / float(np.median(ts)) * o["maxiter"] / runs_maxiter[plain_of[tag]]
