@@ -874,6 +874,60 @@ int sx_sample_ensemble_decide(const sx_sample_args *a, int W, int64_t it, int ha
                               const double *logzf, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * The ensemble sampler with several moves, a burn-in and thinning (csrc/sx_sample_ensemble_moves.hip).  No counterpart in the
+ * reference.  The stretch move keeps a walker on the line through itself and one partner, at 1/a to a times their distance
+ * from the partner: it cannot carry a walker from one mode of a target into another.  The differential-evolution move (ter
+ * Braak 2006) and the snooker move (ter Braak & Vrugt 2008) can.  sx_sample_args stays what it is; the options travel in a
+ * second struct, and the *_moves entry points take the arguments of sx_sample_ensemble_run / _propose / _decide with it in
+ * the place of `stretch` (decide: behind W).  Everything above holds -- replicas, half-sweeps, the decision, the counters --
+ * but the proposal of sample it >= 1:
+ *
+ * The move.  Ensemble g uses ONE entry k of (kind, cum, param) in both half-sweeps of sample it: with u the first double of
+ * Philox (slot 0, row g W, gen it, purpose 16), the first k with cum[k] > u, or nmoves - 1 when there is none (cum: the
+ * running sums of the normalised weights, cum[nmoves - 1] = 1.0).
+ * SX_ENSEMBLE_STRETCH: the rule above (purpose 15) with a = param[k].
+ * The other two draw (d0, d1) from slot 0 and (d2, d3) from slot 1 of Philox (row q, gen it, purpose 17) for the active
+ * walker q and pick distinct walkers of the other half, whose first walker is base, by their indices in it:
+ *     j1 = min(h - 1, (int)(d0 * h));   j2 = min(h - 2, (int)(d1 * (h - 1)));   j2 += (j2 >= j1)
+ * SX_ENSEMBLE_DE, gamma0 = param[k]:
+ *     gamma = gamma0 * (1 + 1e-5 * (2 * d2 - 1));   Y[e] = X_q[e] + gamma * (X_j1[e] - X_j2[e]);   d = fcur_q - f(Y)
+ * SX_ENSEMBLE_SNOOKER, gammas = param[k] (W >= 6):
+ *     j3 = min(h - 3, (int)(d2 * (h - 2)));   j3 += (j3 >= min(j1, j2));   j3 += (j3 >= max(j1, j2))
+ *     delta[e] = X_q[e] - X_j1[e];   dd = sum_e delta[e] * delta[e];   pr = sum_e delta[e] * (X_j2[e] - X_j3[e])
+ *     c = gammas * (pr / dd), and c = 0 where dd is not > 0 or c is not finite;   Y[e] = X_q[e] + c * delta[e]
+ *     d = (n - 1) * log(|1 + c|) + (fcur_q - f(Y))
+ * (Y - X_j1 = (1 + c) delta: the factor is |Y - X_j1|^(n-1) / |X_q - X_j1|^(n-1); at c = -1 it is -inf and Y is rejected.)
+ * The two sums: lane l of the row's LPR lanes (16 / 32 / 64 for n <= 64 / <= 128 / larger) adds its elements e = l, l + LPR,
+ * ... in that order, then v += v[lane ^ 1], ^ 2, ^ 4, ... up to LPR / 2.  No fused multiply-add anywhere.
+ *
+ * Recording: sample `it` goes to row r = (it - rec_start) / rec_every of xall (C, rec_rows, W, n) / funall (C, rec_rows, W)
+ * -- at ((g rec_rows + r) W + w) -- when it >= rec_start and (it - rec_start) % rec_every == 0.  nacc, nfeas and the best
+ * values run over all samples.
+ * With nmoves = 1, kind[0] = SX_ENSEMBLE_STRETCH, rec_start = 0 and rec_every = 1 every output is that of the entry points
+ * above with stretch = param[0], bit for bit.
+ * ------------------------------------------------------------------------- */
+enum { SX_ENSEMBLE_STRETCH = 0, SX_ENSEMBLE_DE = 1, SX_ENSEMBLE_SNOOKER = 2 };
+typedef struct sx_sample_ensemble_opts {
+    int32_t nmoves;                 /* 1 <= nmoves <= 4 entries */
+    int32_t kind[4];                /* SX_ENSEMBLE_* */
+    double cum[4];                  /* 0 < cum[0] < ... < cum[nmoves - 1] = 1.0 */
+    double param[4];                /* stretch: a, finite and > 1; de: gamma0, snooker: gammas, finite and > 0 */
+    int64_t rec_start, rec_every;   /* 0 <= rec_start <= maxiter - 1, 1 <= rec_every < 2^31 */
+    int64_t rec_rows;               /* ceil((maxiter - rec_start) / rec_every): rows of xall / funall per ensemble */
+} sx_sample_ensemble_opts;
+/* sizeof(sx_sample_ensemble_opts) as the library was built (sx_struct_size is not extended) */
+int sx_sample_ensemble_opts_bytes(void);
+/* the resident run: one workgroup per ensemble, one launch, the LDS of sx_sample_ensemble_lds_bytes; a run cut into launches
+ * is the same run, bit for bit */
+int sx_sample_ensemble_run_moves(const sx_sample_args *a, int W, const sx_sample_ensemble_opts *mv, int64_t it0, int64_t steps, void *stream);
+/* around a caller-supplied objective, as above; logzf takes the factor 0 / (n - 1) log(z) / (n - 1) log(|1 + c|) to decide.
+ * With bit-identical objective values this is sx_sample_ensemble_run_moves's run, bit for bit. */
+int sx_sample_ensemble_propose_moves(const sx_sample_args *a, int W, const sx_sample_ensemble_opts *mv, int64_t it, int half, double *prop,
+                               double *logzf, void *stream);
+int sx_sample_ensemble_decide_moves(const sx_sample_args *a, int W, const sx_sample_ensemble_opts *mv, int64_t it, int half, const double *prop, const double *fprop,
+                              const double *logzf, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).
  * replaces: R calls of de/_de.py:176-301 (`de`: initial population :208-218, the generation loop :236-283) with
  *           de_sync (:314-351), the strategies (de/_strategy.py:1-46), Random (de/_constraints.py:13-28),

@@ -147,6 +147,18 @@ class SxSampleMetric(C.Structure):
     ]
 
 
+SX_ENSEMBLE_STRETCH, SX_ENSEMBLE_DE, SX_ENSEMBLE_SNOOKER = 0, 1, 2
+
+
+class SxSampleEnsembleOpts(C.Structure):
+    """sx_sample_ensemble_opts: the moves of an ensemble run (kind, running sum of the weights, parameter), its burn-in and
+    thinning (its size is checked against sx_sample_ensemble_opts_bytes)."""
+    _fields_ = [
+        ("nmoves", i32), ("kind", i32 * 4), ("cum", f64 * 4), ("param", f64 * 4),
+        ("rec_start", i64), ("rec_every", i64), ("rec_rows", i64),
+    ]
+
+
 class SxDeRunsArgs(C.Structure):
     _fields_ = [
         ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("xs", vp), ("funs", vp), ("nits", vp), ("statuses", vp),
@@ -304,6 +316,12 @@ PROTOTYPES = {
     "sx_sample_ensemble_lds_bytes": (C.c_int, [C.c_int, C.c_int]),
     "sx_sample_ensemble_propose": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, f64, i64, C.c_int, vp, vp, vp]),
     "sx_sample_ensemble_decide": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, i64, C.c_int, vp, vp, vp, vp]),
+    "sx_sample_ensemble_opts_bytes": (C.c_int, []),
+    "sx_sample_ensemble_run_moves": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, C.POINTER(SxSampleEnsembleOpts), i64, i64, vp]),
+    "sx_sample_ensemble_propose_moves": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, C.POINTER(SxSampleEnsembleOpts), i64, C.c_int,
+                                                   vp, vp, vp]),
+    "sx_sample_ensemble_decide_moves": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, C.POINTER(SxSampleEnsembleOpts), i64, C.c_int,
+                                                  vp, vp, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_sweep_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp, vp, vp, vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),
@@ -388,6 +406,9 @@ def lib():
     if handle.sx_sample_metric_bytes() != C.sizeof(SxSampleMetric):
         raise HipLibraryError(f"{LIB_PATH}: sx_sample_metric is {handle.sx_sample_metric_bytes()} bytes, its mirror "
                               f"{C.sizeof(SxSampleMetric)}; rebuild the library")
+    if handle.sx_sample_ensemble_opts_bytes() != C.sizeof(SxSampleEnsembleOpts):
+        raise HipLibraryError(f"{LIB_PATH}: sx_sample_ensemble_opts is {handle.sx_sample_ensemble_opts_bytes()} bytes, its mirror "
+                              f"{C.sizeof(SxSampleEnsembleOpts)}; rebuild the library")
     _lib = handle
     return _lib
 

@@ -179,6 +179,8 @@ enum : uint32_t {
     kPurposeSampleInit = 13,     // the initial point (gen 0): the uniform of element e
     kPurposeSampleSwap = 14,     // parallel tempering: the exchange uniform of a pair: slot 0, row = the LOWER rung's replica, first double
     kPurposeSampleStretch = 15,  // ensemble sampler: slot 0, row = the active walker's replica: first double the partner, second the stretch
+    kPurposeSampleMove = 16,     // ensemble sampler, several moves: slot 0, row = the ensemble's first replica: first double picks the entry
+    kPurposeSampleDonors = 17,   // ... "de" / "snooker": row = the active walker's replica: slot 0 (d0, d1) the partners, slot 1 (d2, d3)
 };
 
 // Element e of a row sits in lane l = e % LPR of the row's lanes at step q = e / LPR (LPR a power of two).

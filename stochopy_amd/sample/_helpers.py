@@ -62,7 +62,8 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
       The result gains ``metric`` and ``metric_windows``.  See ``sample.mcmc``.
 
     ``method="ensemble"`` (this backend's own; ``rng="philox"``): the affine-invariant ensemble sampler -- ``chains``
-    ensembles of ``walkers`` walkers, no step size, no gradient.  See ``sample.ensemble``.
+    ensembles of ``walkers`` walkers, no step size, no gradient; ``moves`` adds the differential-evolution and snooker
+    moves for targets with separated modes, ``burn`` / ``thin`` choose the samples recorded.  See ``sample.ensemble``.
 
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """

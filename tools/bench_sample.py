@@ -43,6 +43,12 @@ protocol with the plain mcmc kernel (perc 1.0) on as many chains as there are wa
 walker's samples; `vs_plain` is the ratio of the medians.  --chains is not used.  No CPU side.
 
     python tools/bench_sample.py --ensemble [--rounds 5] [--out profiles/sample_ensemble_bench.jsonl]
+
+--ensemble --moves: the moves of the ensemble sampler (csrc/sx_sample_ensemble_moves.hip) at the same two shapes: "de", "snooker"
+and the mixture [("de", .7), ("de", .1, 1.0), ("snooker", .2)] through sx_sample_ensemble_run_moves, each taking turns by the same
+protocol with the stretch move through sx_sample_ensemble_run; `vs_stretch` is the ratio of the medians.
+
+    python tools/bench_sample.py --ensemble --moves [--rounds 5] [--out profiles/sample_ensemble_moves_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -143,6 +149,29 @@ class EnsembleRun(DeviceRun):
                    "sx_sample_ensemble_run")
 
 
+class EnsembleMovesRun(EnsembleRun):
+    """The same ensembles with ``moves``, launched as stochopy_amd.sample does with method="ensemble" and moves=..."""
+
+    def __init__(self, ctx, ndim, ensembles, W, o, moves):
+        from stochopy_amd import _lib
+        from stochopy_amd.sample import _ensemble
+
+        super().__init__(ctx, ndim, ensembles, W, o)
+        self.moves, cum = _ensemble.check_moves(moves, ndim, W, self.stretch)
+        self.mv = mv = _lib.SxSampleEnsembleOpts()
+        mv.nmoves = len(self.moves)
+        for k, (name, _, param) in enumerate(self.moves):
+            mv.kind[k], mv.cum[k], mv.param[k] = _ensemble.MOVE_KINDS[name], cum[k], param
+        mv.rec_start, mv.rec_every, mv.rec_rows = 0, 1, self.m
+
+    def launch(self):
+        from stochopy_amd import _lib
+
+        _lib.check(self.L.sx_sample_ensemble_run_moves(C.byref(self.a), self.W, C.byref(self.mv), 0, self.m, self.ctx.stream_ptr),
+                   "sx_sample_ensemble_run_moves")
+
+
+ENSEMBLE_MOVES = {"de": "de", "snooker": "snooker", "mixture": [("de", 0.7), ("de", 0.1, 1.0), ("snooker", 0.2)]}
 ENSEMBLE_SHAPES = [(32, 64, 256), (64, 128, 128)]  # (ndim, walkers, ensembles)
 ENSEMBLE_OPTIONS = {"maxiter": 300, "stepsize": 0.05, "perc": 1.0, "return_all": False}
 
@@ -243,12 +272,27 @@ def main():
     ap.add_argument("--adapt", action="store_true", help="the plain configurations next to a warm-up and to thin=10")
     ap.add_argument("--metric", action="store_true", help="plain, warm-up alone and warm-up with per-axis scales")
     ap.add_argument("--ensemble", action="store_true", help="the ensemble sampler next to the plain mcmc kernel on as many rows")
+    ap.add_argument("--moves", action="store_true", help='with --ensemble: "de", "snooker" and their mixture next to the stretch move')
     args = ap.parse_args()
+    if args.moves and not args.ensemble:
+        ap.error("--moves goes with --ensemble")
     from stochopy_amd import _device
 
     ctx = _device.Context()
-    ensemble_of = {}
-    if args.ensemble:
+    ensemble_of, stretch_of = {}, {}
+    if args.ensemble and args.moves:
+        args.no_cpu = True
+        runs, o = [], ENSEMBLE_OPTIONS
+        for ndim, W, ensembles in ENSEMBLE_SHAPES:
+            shape = f"ndim={ndim} W={W} ensembles={ensembles}"
+            runs.append((f"ensemble {shape}", "ensemble", ndim, dict(o, walkers=W, ensembles=ensembles, stretch=2.0),
+                         EnsembleRun(ctx, ndim, ensembles, W, o)))
+            for name, moves in ENSEMBLE_MOVES.items():
+                run = EnsembleMovesRun(ctx, ndim, ensembles, W, o, moves)
+                runs.append((f"ensemble moves={name} {shape}", "ensemble", ndim,
+                             dict(o, walkers=W, ensembles=ensembles, moves=[list(e) for e in run.moves]), run))
+                stretch_of[runs[-1][0]] = f"ensemble {shape}"
+    elif args.ensemble:
         args.no_cpu = True
         runs, o = [], ENSEMBLE_OPTIONS
         for ndim, W, ensembles in ENSEMBLE_SHAPES:
@@ -328,6 +372,10 @@ def main():
             line.update({k: o[k] for k in ("walkers", "ensembles", "stretch")})
             line["lds_bytes"] = r.lds
             line["vs_plain"] = float(np.median(times[ensemble_of[tag]])) / float(np.median(ts))
+        if tag in stretch_of:
+            line.update({k: o[k] for k in ("walkers", "ensembles", "moves")})
+            line["lds_bytes"] = r.lds
+            line["vs_stretch"] = float(np.median(times[stretch_of[tag]])) / float(np.median(ts))
         if tag in plain_of:
             line.update({k: o[k] for k in ("warmup", "thin") if k in o})
             line["vs_plain"] = float(np.median(times[plain_of[tag]])) / float(np.median(ts)) * o["maxiter"] / runs_maxiter[plain_of[tag]]
