@@ -500,6 +500,14 @@ int sx_cmaes_generation(const sx_cma_args *a, int64_t gen, int do_eigh, void *st
  * (NaN last, ties by lower index); with besthist, state (an sx_cma_state) gets best_row / fbest = order[0] and
  * reserved[5] = np.argmin(fit) (the first NaN if any), besthist[gen - 1] = fit[order[0]].  Nothing happens once state.done. */
 int sx_cma_rank(const double *fit, int64_t P, int64_t *order, void *state, double *besthist, int64_t gen, void *stream);
+/* The Penalize step of the device-resident CMA-ES / VD-CMA generations on its own (cmaes/_constraints.py:4-82): pen_order =
+ * argsort of the fit GIVEN (the percentiles are taken of it), the boundary-weight bookkeeping in pen_ws, then fit = objective
+ * of the clipped arx + the weighted squared excess (pen_ws's penalty slots).  Reads of h: arx, fit, xm, xstd, xmean, xold,
+ * state (its sigma and done), pen_ws, pen_order, n, P, mueff, fun_id, and C (its diagonal) when dvec == NULL; dvec / vvec
+ * DEVICE (n): the diagonal is d (1 + v^2) d (VD-CMA).  Non-zero, nothing launched: a null pointer among those, a bad shape,
+ * or a spread history of more than 256 entries (20 + 3n/P + 1 > 256).  Once state.done the ranking, the bookkeeping and the
+ * addition rest (pen_ws's weights, v, history and flags keep their values); the evaluation still writes fit. */
+int sx_cma_penalize(const sx_cma_args *h, int64_t gen, const double *dvec, const double *vvec, void *stream);
 /* The same generation in two steps for candidates sharded over ranks (workers > 1; what the reference's parallel backends
  * shard: _common.py:58-72).  stage 0: this rank's candidates [row0, row0 + rows) -- Philox normals keyed by the global
  * row, sampling GEMM, objective -- into arx_loc (rows,n) / fit_loc (rows); the caller

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void cma_history_kernel(const sx_cma_args a, i
     const int e = (int)(t % n);
     const int64_t src = a.hist_rows > 0 ? r : (int64_t)state->reserved[5];  // (argmin, see cma_rank_kernel)
     double x = a.arx[src * n + e];
-    if (a.pen_ws != nullptr) x = fmin(fmax(x, -1.0), 1.0);  // Penalize: the caller sees the clipped points (:238-256)
+    if (a.pen_ws != nullptr) x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);  // Penalize: the caller sees the clipped points (:238-256)
     a.hist_x[((gen - 1) * rows + r) * n + e] = x * a.xstd[e] + a.xm[e];
     if (e == 0) a.hist_f[(gen - 1) * rows + r] = a.fit[src];
 }
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(kPathThreads) void cma_stop_kernel(const sx_cma_arg
         const double *row = a.arx + state->best_row * (int64_t)n;
         for (int e = tid; e < n; e += kPathThreads) {
             double x = row[e];
-            if (a.pen_ws != nullptr) x = fmin(fmax(x, -1.0), 1.0);  // Penalize: the clipped point (:336-350)
+            if (a.pen_ws != nullptr) x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);  // Penalize: the clipped point (:336-350)
             a.xbest[e] = x * a.xstd[e] + a.xm[e];
         }
     }
@@ -501,6 +501,15 @@ extern "C" int sx_cma_rank(const double *fit, int64_t P, int64_t *order, void *s
                            void *stream) {
     SX_REQUIRE(fit && order && state && P >= 1 && (besthist == nullptr || gen >= 1), "sx_cma_rank: bad arguments");
     return sx::cma_rank_launch(fit, P, order, (sx_cma_state *)state, besthist, gen, stream);
+}
+
+extern "C" int sx_cma_penalize(const sx_cma_args *h, int64_t gen, const double *dvec, const double *vvec, void *stream) {
+    SX_REQUIRE(h && h->arx && h->fit && h->xm && h->xstd && h->xmean && h->xold && h->state && h->pen_ws && h->pen_order &&
+                   (dvec != nullptr || h->C != nullptr) && (dvec == nullptr) == (vvec == nullptr),
+               "sx_cma_penalize: null pointer");
+    SX_REQUIRE(h->P >= 2 && h->n >= 1 && h->mueff > 0.0 && h->fun_id >= 0 && h->fun_id < SX_FUN_COUNT && gen >= 1,
+               "sx_cma_penalize: bad shape, objective or generation number");
+    return sx::cma_penalize_launch(*h, gen, dvec, vvec, stream);
 }
 
 extern "C" int sx_cmaes_generation(const sx_cma_args *a, int64_t gen, int do_eigh, void *stream) {

@@ -292,7 +292,7 @@ __global__ __launch_bounds__(kVdThreads) void vd_update_kernel(const sx_vd_args 
         const double *row = a.arx + state->best_row * (int64_t)n;
         for (int e = tid; e < n; e += kVdThreads) {
             double x = row[e];
-            if (a.pen_ws != nullptr) x = fmin(fmax(x, -1.0), 1.0);  // Penalize: the clipped point is what the caller sees
+            if (a.pen_ws != nullptr) x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);  // Penalize: the clipped point is what the caller sees
             a.xbest[e] = x * a.xstd[e] + a.xm[e];
         }
     }
@@ -675,7 +675,7 @@ __device__ __forceinline__ void vw_h_phase(const sx_vd_args &a, int64_t gen, dou
         const int64_t br = (int64_t)s_scal[kSState + 6] * (int64_t)n;
         VW_FOR_E {
             double x = a.arx != nullptr ? a.arx[br + e] : a.xold[e] + m.sigma0 * a.ary[br + e];
-            if (a.pen_ws != nullptr) x = fmin(fmax(x, -1.0), 1.0);
+            if (a.pen_ws != nullptr) x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);
             a.xbest[e] = x * a.xstd[e] + a.xm[e];
         }
     }

@@ -963,7 +963,7 @@ __global__ __launch_bounds__(T) void wide_vd_candidates_kernel(const sx_vd_args 
                     if (keep_x) xo[e] = x;
                     tkacc += (inj ? y / dd[u] : yd) * vv[u];  // (the division only for the injected pair: rounding apart the same)
                 }
-                const double xc = clip ? fmin(fmax(x, -1.0), 1.0) : x;  // cmaes/_constraints.py:29-31
+                const double xc = clip ? (x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x)) : x;  // cmaes/_constraints.py:29-31
                 stage_put<Obj<FUN>::NEXT>(Sd, e, e0, xc * xs[u] + xo0[u]);  // cmaes/_cmaes.py:171
             }
         }

@@ -63,6 +63,8 @@ def test_wide_eval_affine_clip_and_penalty(sa, n):
     rs = np.random.RandomState(n % 97)
     P = 9
     X = rs.uniform(-1.4, 1.4, (P, n))
+    if n == 4097:  # a NaN element stays NaN through the clip (np.where(x < -1, -1, x) keeps it): objective and penalty are NaN
+        X[3, 100] = np.nan
     xm, xstd, v = rs.uniform(-1, 1, n), rs.uniform(0.5, 2.0, n), rs.uniform(0.0, 2.0, n)
     ctx = _device.Context()
     d = lambda a: torch.as_tensor(a, device=ctx.device)
@@ -70,14 +72,17 @@ def test_wide_eval_affine_clip_and_penalty(sa, n):
     fid = _lib.FUN_IDS["rosenbrock"]
     _common.evaluate_rows(ctx, fid, Xd, n, f, xm=d(xm), xstd=d(xstd))
     ctx.sync()
-    assert np.array_equal(f.cpu().numpy(), OBJECTIVES["rosenbrock"](X * xstd + xm))
+    assert np.array_equal(f.cpu().numpy(), OBJECTIVES["rosenbrock"](X * xstd + xm), equal_nan=True)
     _common.evaluate_rows(ctx, fid, Xd, n, f, xm=d(xm), xstd=d(xstd), clip=True)
     ctx.sync()
     Xc = np.clip(X, -1.0, 1.0)
-    assert np.array_equal(f.cpu().numpy(), OBJECTIVES["rosenbrock"](Xc * xstd + xm))
+    assert np.isnan(Xc).sum() == (n == 4097) and np.isnan(f.cpu().numpy()).sum() == (n == 4097)
+    assert np.array_equal(f.cpu().numpy(), OBJECTIVES["rosenbrock"](Xc * xstd + xm), equal_nan=True)
     _common.penalty_rows(ctx, fid, Xd, n, d(xm), d(xstd), d(v), f, pen)
     ctx.sync()
-    assert np.allclose(pen.cpu().numpy(), (((Xc - X) ** 2) * v).sum(axis=1), rtol=1e-12)
+    assert np.array_equal(f.cpu().numpy(), OBJECTIVES["rosenbrock"](Xc * xstd + xm), equal_nan=True)
+    assert np.isnan(pen.cpu().numpy()).sum() == (n == 4097)
+    assert np.allclose(pen.cpu().numpy(), (((Xc - X) ** 2) * v).sum(axis=1), rtol=1e-12, equal_nan=True)
 
 
 def _trace_pair(sa, objective, bounds, method, opts):
