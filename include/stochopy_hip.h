@@ -936,6 +936,84 @@ int sx_sample_ensemble_decide_moves(const sx_sample_args *a, int W, const sx_sam
                               const double *logzf, void *stream);
 
 /* ------------------------------------------------------------------------- *
+ * Tempered sequential Monte Carlo with evidence (csrc/sx_sample_smc.hip; method="smc").  No counterpart in the reference.
+ * C populations of P particles, each independent of the others and of C; particle i of population c is the global row
+ * q = c P + i, which keys its draws.  fun = -log likelihood, the prior is uniform on the box: a proposal outside it is always
+ * rejected.  The populations go from beta = 0 (the prior) to beta = 1 (the target) and return log Z, Z = the integral of
+ * exp(-fun) over the box divided by the box's volume.
+ *
+ * Stage 0: x_q = initial_value's rule (purpose 13, row q, gen 0), f_q = fun(x_q); beta_0 = 0, logZ = 0, scale_1 = scale.
+ * Stage s = 1, 2, ... while beta_{s-1} < 1 and s <= maxiter:
+ *  1. fmin = the least finite f.  w_i(beta) = exp(-((beta - beta_{s-1}) * (f_i - fmin))), 0 where f_i is NaN or +inf;
+ *     ESS(beta) = (sum w)^2 / sum w^2.  If ESS(1) >= ess * P then beta_s = 1; otherwise lo = beta_{s-1}, hi = 1 and EXACTLY 52
+ *     times mid = (lo + hi) / 2; ESS(mid) >= ess * P ? lo = mid : hi = mid; then beta_s = lo > beta_{s-1} ? lo : hi.
+ *  2. logZ = logZ + (log(sum w_i(beta_s) / P) - (beta_s - beta_{s-1}) * fmin); reported ESS(beta_s) / P.
+ *  3. u = the first double of Philox (slot 0, row c P, gen s, purpose 18); cum the inclusive running sum of w(beta_s) in index
+ *     order; ancestor a_i = the least j with cum_j >= ((i + u) / P) * cum_{P-1}, found by bisection (lo = 0, hi = P - 1; mid =
+ *     (lo + hi) >> 1; cum_mid >= target ? hi = mid : lo = mid + 1), so P - 1 when there is none.  x_i <- x_{a_i},
+ *     f_i <- f_{a_i}, into the other buffer (stage s works in buffer s & 1; stage 0 fills buffer 0).
+ *  4. sd_e = the standard deviation (two passes, divisor P) of the resampled population on axis e;
+ *     step_e = scale_s * max(sd_e, 1e-8 * h_e), h_e = (upper_e - lower_e) / 2.
+ *  5. M = steps Metropolis steps per particle, step m = 1 ... M being sample g = (s - 1) M + m of chain q in the sense of
+ *     sx_sample_run: proposal x + step * z on ALL variables (the normals of purpose 10, row q, gen g), feasible when inside
+ *     the box, accepted when min(0, d) > log(u'), d = beta_s * (f_cur - f_prop), u' the uniform of purpose 12 (row q, gen g);
+ *     a NaN d accepts.
+ *  6. r_s = accepted / (P M); scale_{s+1} = scale_s * exp(r_s - target).
+ * A population ends after the mutation of the stage with beta_s = 1 (status 0), after maxiter stages with beta < 1 (status -1:
+ * its particles sample p^beta), or at the start of a stage where no f is finite or one is -inf (status -2, logZ = -inf).
+ * An ended population is frozen: the kernels leave its arrays alone.
+ *
+ * The order of the sums, fixed by P alone.  Stage kernel (one workgroup of 1 024 threads per population, f in LDS): thread t
+ * owns particles [t K, min(P, t K + K)), K = ceil(P / 1024).  sum w and sum w^2: each thread 0.0 + its terms in index order;
+ * over the 64 threads of a wave v += v[lane ^ 1], ^ 2, ... ^ 32; then 0.0 + the 16 waves' sums in order.  cum: the threads'
+ * totals scanned over the wave (v += v[lane - off] for lane >= off, off = 1, 2, ... 32), base = 0.0 + the totals of the waves
+ * before (the wave's last inclusive value), and cum_i = ((base + the exclusive value of the thread) + its own w) + ... one by
+ * one.  Gather kernel: for axis e thread r of 16 adds particles r, r + 16, ... in that order from 0.0, the 16 sums are added in
+ * the order of r from 0.0; mean = sum / P; the squared deviations from it the same way; sd = sqrt(sum / P).
+ * No fused multiply-add anywhere.
+ *
+ * state (C, 8) doubles, the record of population c (integers exact): [0] status (1 while running), [1] beta_s, [2] logZ,
+ * [3] ESS(beta_s) / P, [4] scale_s, [5] r of the last stage whose step 6 ran, [6] s = the stages done, [7] the accepted steps
+ * behind [5].  sx_smc_stage(s) first performs step 6 of stage s - 1 for the populations whose [6] is s - 1, then steps 1 - 3
+ * of stage s for those still running; call it once more (s = last + 1 <= maxiter + 1) after the last mutation for that step 6.
+ * The host reads the records once per stage to decide whether to go on; nothing else is synchronised.
+ * ------------------------------------------------------------------------- */
+typedef struct sx_smc_args {
+    double *x[2];            /* DEVICE (C P, n) each: the particles of stage s live in x[s & 1]; initialised memory          */
+    double *f[2];            /* DEVICE (C P) each: their values                                                             */
+    int32_t *anc;            /* DEVICE (C P): the ancestors of the latest stage, indices inside the population              */
+    int64_t *nacc;           /* DEVICE (C P): the accepted steps of each particle in the latest mutation                    */
+    double *step;            /* DEVICE (C, n): step 4                                                                       */
+    double *state;           /* DEVICE (C, 8): the records                                                                  */
+    const double *lower, *upper; /* DEVICE (n)                                                                              */
+    int64_t C, P;            /* C >= 1, 4 <= P <= sx_smc_max_particles(), C P < 2^31                                        */
+    int32_t n, fun_id;       /* 1 <= n <= sx_wide_from(); fun_id is read by sx_smc_init / sx_smc_mutate alone               */
+    int32_t steps, maxiter;  /* M >= 1, the most stages >= 1; steps * maxiter < 2^31                                        */
+    double ess, target;      /* both in (0, 1)                                                                              */
+    double scale;            /* scale_1: finite, > 0                                                                        */
+    uint32_t key0, key1;
+} sx_smc_args;
+/* sizeof(sx_smc_args) as the library was built (sx_struct_size is not extended) */
+int sx_smc_args_bytes(void);
+/* the most particles of one population: their values fit one workgroup's LDS (160 KiB) */
+int sx_smc_max_particles(void);
+/* Every entry point below is one launch, checks its arguments as sx_sample_run does (-1 and sx_last_error), and takes the
+ * stage s it works on.  stage 0: draw and evaluate the particles into x[0] / f[0], start the records */
+int sx_smc_init(const sx_smc_args *a, void *stream);
+/* step 6 of stage s - 1, steps 1 - 3 of stage s (1 <= s <= maxiter + 1): state, anc */
+int sx_smc_stage(const sx_smc_args *a, int s, void *stream);
+/* the rest of step 3 and step 4 (1 <= s <= maxiter): x / f [(s - 1) & 1] through anc -> x / f [s & 1]; step */
+int sx_smc_resample(const sx_smc_args *a, int s, void *stream);
+/* step 5 with the objective fun_id in the kernel: x / f [s & 1] in place, nacc */
+int sx_smc_mutate(const sx_smc_args *a, int s, void *stream);
+/* step 5 around a caller-supplied objective, per step m = 1 ... M: propose -> fprop = fun(prop) -> decide; prop (C P, n),
+ * fprop (C P) DEVICE.  A frozen particle proposes itself.  Stage 0 is (s, m) = (0, 0): propose draws the particles into prop,
+ * decide moves them and fprop into x[0] / f[0] and starts the records.  With bit-identical objective values this is
+ * sx_smc_init / sx_smc_mutate's run, bit for bit. */
+int sx_smc_propose(const sx_smc_args *a, int s, int m, double *prop, void *stream);
+int sx_smc_decide(const sx_smc_args *a, int s, int m, const double *prop, const double *fprop, void *stream);
+
+/* ------------------------------------------------------------------------- *
  * Differential Evolution, many independent runs in one launch (csrc/sx_de_runs.hip).
  * replaces: R calls of de/_de.py:176-301 (`de`: initial population :208-218, the generation loop :236-283) with
  *           de_sync (:314-351), the strategies (de/_strategy.py:1-46), Random (de/_constraints.py:13-28),

@@ -159,6 +159,17 @@ class SxSampleEnsembleOpts(C.Structure):
     ]
 
 
+class SxSmcArgs(C.Structure):
+    """sx_smc_args: tempered sequential Monte Carlo (its size is checked against sx_smc_args_bytes)."""
+    _fields_ = [
+        ("x", vp * 2), ("f", vp * 2), ("anc", vp), ("nacc", vp), ("step", vp), ("state", vp), ("lower", vp), ("upper", vp),
+        ("C", i64), ("P", i64),
+        ("n", i32), ("fun_id", i32), ("steps", i32), ("maxiter", i32),
+        ("ess", f64), ("target", f64), ("scale", f64),
+        ("key0", C.c_uint32), ("key1", C.c_uint32),
+    ]
+
+
 class SxDeRunsArgs(C.Structure):
     _fields_ = [
         ("keys", vp), ("lower", vp), ("upper", vp), ("x0", vp), ("xs", vp), ("funs", vp), ("nits", vp), ("statuses", vp),
@@ -323,6 +334,14 @@ PROTOTYPES = {
                                                    vp, vp, vp]),
     "sx_sample_ensemble_decide_moves": (C.c_int, [C.POINTER(SxSampleArgs), C.c_int, C.POINTER(SxSampleEnsembleOpts), i64, C.c_int,
                                                   vp, vp, vp, vp]),
+    "sx_smc_args_bytes": (C.c_int, []),
+    "sx_smc_max_particles": (C.c_int, []),
+    "sx_smc_init": (C.c_int, [C.POINTER(SxSmcArgs), vp]),
+    "sx_smc_stage": (C.c_int, [C.POINTER(SxSmcArgs), C.c_int, vp]),
+    "sx_smc_resample": (C.c_int, [C.POINTER(SxSmcArgs), C.c_int, vp]),
+    "sx_smc_mutate": (C.c_int, [C.POINTER(SxSmcArgs), C.c_int, vp]),
+    "sx_smc_propose": (C.c_int, [C.POINTER(SxSmcArgs), C.c_int, C.c_int, vp, vp]),
+    "sx_smc_decide": (C.c_int, [C.POINTER(SxSmcArgs), C.c_int, C.c_int, vp, vp, vp]),
     "sx_de_runs_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp]),
     "sx_de_runs_sweep_launch": (C.c_int, [C.POINTER(SxDeRunsArgs), vp, vp, vp, vp]),
     "sx_de_runs_lds_bytes": (i64, [i64, C.c_int]),
@@ -410,6 +429,9 @@ def lib():
     if handle.sx_sample_ensemble_opts_bytes() != C.sizeof(SxSampleEnsembleOpts):
         raise HipLibraryError(f"{LIB_PATH}: sx_sample_ensemble_opts is {handle.sx_sample_ensemble_opts_bytes()} bytes, its mirror "
                               f"{C.sizeof(SxSampleEnsembleOpts)}; rebuild the library")
+    if handle.sx_smc_args_bytes() != C.sizeof(SxSmcArgs):
+        raise HipLibraryError(f"{LIB_PATH}: sx_smc_args is {handle.sx_smc_args_bytes()} bytes, its mirror "
+                              f"{C.sizeof(SxSmcArgs)}; rebuild the library")
     _lib = handle
     return _lib
 

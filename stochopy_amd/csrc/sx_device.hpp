@@ -181,6 +181,7 @@ enum : uint32_t {
     kPurposeSampleStretch = 15,  // ensemble sampler: slot 0, row = the active walker's replica: first double the partner, second the stretch
     kPurposeSampleMove = 16,     // ensemble sampler, several moves: slot 0, row = the ensemble's first replica: first double picks the entry
     kPurposeSampleDonors = 17,   // ... "de" / "snooker": row = the active walker's replica: slot 0 (d0, d1) the partners, slot 1 (d2, d3)
+    kPurposeSampleResample = 18, // tempered SMC: slot 0, row = the population's first particle, gen = the stage: first double the offset u
 };
 
 // Element e of a row sits in lane l = e % LPR of the row's lanes at step q = e / LPR (LPR a power of two).

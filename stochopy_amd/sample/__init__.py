@@ -4,6 +4,7 @@ from ._ensemble import sample as ensemble
 from ._helpers import SampleResult, sample
 from ._hmc import sample as hmc
 from ._mcmc import sample as mcmc
+from ._smc import sample as smc
 
 __all__ = [
     "SampleResult",
@@ -11,4 +12,5 @@ __all__ = [
     "ensemble",
     "hmc",
     "mcmc",
+    "smc",
 ]

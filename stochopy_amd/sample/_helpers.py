@@ -65,6 +65,12 @@ def sample(fun, bounds, x0=None, args=(), method="mcmc", options=None, callback=
     ensembles of ``walkers`` walkers, no step size, no gradient; ``moves`` adds the differential-evolution and snooker
     moves for targets with separated modes, ``burn`` / ``thin`` choose the samples recorded.  See ``sample.ensemble``.
 
+    ``method="smc"`` (this backend's own; ``rng="philox"``): tempered sequential Monte Carlo -- ``chains`` populations of
+    ``particles`` particles walked from the uniform prior on ``bounds`` to ``exp(-fun)`` through a ladder of inverse
+    temperatures the sampler chooses itself, ``steps`` Metropolis steps per particle and stage.  It returns the final particles
+    and ``log_evidence``, the log of the integral of ``exp(-fun)`` over the box divided by the box's volume, which no chain or
+    ensemble can give, and finds the weights of separated modes from a cold start.  See ``sample.smc``.
+
     See ``sample.mcmc`` / ``sample.hmc`` for where this backend departs from the reference.
     """
     options = options if options else {}

@@ -49,6 +49,15 @@ and the mixture [("de", .7), ("de", .1, 1.0), ("snooker", .2)] through sx_sample
 protocol with the stretch move through sx_sample_ensemble_run; `vs_stretch` is the ratio of the medians.
 
     python tools/bench_sample.py --ensemble --moves [--rounds 5] [--out profiles/sample_ensemble_moves_bench.jsonl]
+
+--smc: tempered sequential Monte Carlo (csrc/sx_sample_smc.hip, method="smc"): rosenbrock, 16 populations of 1 024 particles at
+ndim 4 and ndim 128.  The mutation launch (sx_smc_mutate of stage 1, 200 steps per particle, after one init / stage / resample)
+takes turns by the same protocol with the plain mcmc kernel (perc 1.0, 201 samples, return_all off) on as many chains at the
+same ndim; samples / s counts every particle's steps, `vs_mcmc` is the ratio of the medians.  Then the whole run of the public
+call on the sphere of tests/_smc_cases.py (16 x 1 024 particles, 8 steps, ndim 4): wall-clock seconds over --rounds runs, and
+the stages.  --chains is not used.  No CPU side.
+
+    python tools/bench_sample.py --smc [--rounds 5] [--out profiles/sample_smc_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -176,6 +185,61 @@ ENSEMBLE_SHAPES = [(32, 64, 256), (64, 128, 128)]  # (ndim, walkers, ensembles)
 ENSEMBLE_OPTIONS = {"maxiter": 300, "stepsize": 0.05, "perc": 1.0, "return_all": False}
 
 
+class SmcMutateRun:
+    """The mutation launch of stage 1 of `populations` populations of P particles, M steps per particle, as stochopy_amd.sample
+    launches it with method="smc" (after the init, stage and resample launches, which are not timed)."""
+
+    stored = 0
+    timed = DeviceRun.timed
+
+    def __init__(self, ctx, ndim, populations, P, M, seed=3):
+        from stochopy_amd import _lib
+        from stochopy_amd.sample import _smc
+
+        self.ctx, self.L, self.m, self.samples = ctx, ctx.L, M, populations * P * M
+        s = types.SimpleNamespace(chains=populations, particles=P, ndim=ndim, lower=np.full(ndim, -5.12), upper=np.full(ndim, 5.12),
+                                  fun_id=_lib.FUN_IDS["rosenbrock"], steps=M, maxiter=2, ess=0.5, target=0.234,
+                                  scale=2.38 / np.sqrt(ndim), key=(seed, 0))
+        t = __import__("torch")
+        with t.cuda.stream(ctx.stream):
+            self.dev, self.a = _smc.smc_args(ctx, s)
+            _lib.check(self.L.sx_smc_init(C.byref(self.a), ctx.stream_ptr), "sx_smc_init")
+            _lib.check(self.L.sx_smc_stage(C.byref(self.a), 1, ctx.stream_ptr), "sx_smc_stage")
+            _lib.check(self.L.sx_smc_resample(C.byref(self.a), 1, ctx.stream_ptr), "sx_smc_resample")
+        ctx.sync()
+
+    def launch(self):
+        from stochopy_amd import _lib
+
+        _lib.check(self.L.sx_smc_mutate(C.byref(self.a), 1, self.ctx.stream_ptr), "sx_smc_mutate")
+
+
+SMC_SHAPES = [(4, 16, 1024), (128, 16, 1024)]  # (ndim, populations, particles)
+SMC_STEPS = 200
+
+
+def smc_whole_run(rounds):
+    """The public call on the sphere of tests/_smc_cases.py: wall-clock seconds per run."""
+    import _smc_cases as cases
+    import stochopy_amd as sa
+
+    def once():
+        t0 = time.perf_counter()
+        res = sa.sample.sample(sa.factory.sphere, cases.SPHERE_BOUNDS, method="smc", options=dict(cases.SPHERE_OPTIONS, seed=1))
+        return time.perf_counter() - t0, res
+
+    once()
+    ts, res = [], None
+    for _ in range(rounds):
+        dt, res = once()
+        ts.append(dt)
+    o = cases.SPHERE_OPTIONS
+    return {"config": "smc whole run, sphere ndim=4", "method": "smc", "ndim": 4, "populations": o["chains"],
+            "particles": o["particles"], "steps": o["steps"], "stages": int(res.nit), "nfev": int(res.nfev),
+            "seconds_median": float(np.median(ts)), "seconds_min": float(min(ts)), "seconds_max": float(max(ts)),
+            "particle_steps_per_s": o["chains"] * o["particles"] * o["steps"] * int(res.nit) / float(np.median(ts)), "rounds": rounds}
+
+
 class AdaptRun(DeviceRun):
     """The same configuration through sx_sample_run_adapt, as stochopy_amd.sample launches it with warmup / burn / thin."""
 
@@ -273,14 +337,25 @@ def main():
     ap.add_argument("--metric", action="store_true", help="plain, warm-up alone and warm-up with per-axis scales")
     ap.add_argument("--ensemble", action="store_true", help="the ensemble sampler next to the plain mcmc kernel on as many rows")
     ap.add_argument("--moves", action="store_true", help='with --ensemble: "de", "snooker" and their mixture next to the stretch move')
+    ap.add_argument("--smc", action="store_true", help="the mutation launch of method=\"smc\" next to the plain mcmc kernel; the whole run")
     args = ap.parse_args()
     if args.moves and not args.ensemble:
         ap.error("--moves goes with --ensemble")
     from stochopy_amd import _device
 
     ctx = _device.Context()
-    ensemble_of, stretch_of = {}, {}
-    if args.ensemble and args.moves:
+    ensemble_of, stretch_of, mcmc_of = {}, {}, {}
+    if args.smc:
+        args.no_cpu = True
+        runs = []
+        for ndim, populations, P in SMC_SHAPES:
+            o = {"maxiter": SMC_STEPS + 1, "stepsize": 0.05, "perc": 1.0, "return_all": False}
+            plain, tag = f"mcmc ndim={ndim} chains={populations * P}", f"smc mutation ndim={ndim} populations={populations} particles={P}"
+            runs.append((plain, "mcmc", ndim, o, DeviceRun(ctx, "mcmc", ndim, populations * P, o)))
+            runs.append((tag, "smc", ndim, {"maxiter": SMC_STEPS, "populations": populations, "particles": P},
+                         SmcMutateRun(ctx, ndim, populations, P, SMC_STEPS)))
+            mcmc_of[tag] = plain
+    elif args.ensemble and args.moves:
         args.no_cpu = True
         runs, o = [], ENSEMBLE_OPTIONS
         for ndim, W, ensembles in ENSEMBLE_SHAPES:
@@ -359,6 +434,7 @@ def main():
             times[tag].append(r.timed(launches[tag]))
     lines = []
     runs_maxiter = {tag: o["maxiter"] for tag, _, _, o, _ in runs}
+    runs_rate = {tag: r.samples / float(np.median(times[tag])) for tag, *_, r in runs}
     for tag, method, ndim, o, r in runs:
         ts = np.array(times[tag])
         line = {"config": tag, "method": method, "ndim": ndim, "chains": r.samples // r.m, "maxiter": o["maxiter"],
@@ -372,6 +448,9 @@ def main():
             line.update({k: o[k] for k in ("walkers", "ensembles", "stretch")})
             line["lds_bytes"] = r.lds
             line["vs_plain"] = float(np.median(times[ensemble_of[tag]])) / float(np.median(ts))
+        if tag in mcmc_of:
+            line.update({k: o[k] for k in ("populations", "particles")})
+            line["vs_mcmc"] = line["samples_per_s"] / (runs_rate[mcmc_of[tag]])
         if tag in stretch_of:
             line.update({k: o[k] for k in ("walkers", "ensembles", "moves")})
             line["lds_bytes"] = r.lds
@@ -391,6 +470,9 @@ def main():
             line.update({"cpu_one_chain_samples_per_s": rate, "cpu_what": what, "speedup": line["samples_per_s"] / rate})
         lines.append(line)
         print(json.dumps(line), flush=True)
+    if args.smc:
+        lines.append(smc_whole_run(args.rounds))
+        print(json.dumps(lines[-1]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             for line in lines:
