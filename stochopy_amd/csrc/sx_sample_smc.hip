@@ -354,8 +354,10 @@ __global__ __launch_bounds__(kMaxWavesPerBlock *kWave) void smc_propose_kernel(c
         }
         return;
     }
-    const bool live = a.state[c * kStWords + kStStages] == (double)s;
-    const double *X = a.x[s & 1] + q * n;
+    const double stages = a.state[c * kStWords + kStStages];
+    const bool live = stages == (double)s;
+    // (an ended population's particles are where its last stage left them, in the buffer its own record names -- not in x[s & 1])
+    const double *X = a.x[(live ? s : (int)stages) & 1] + q * n;
     const double *step = a.step + c * n;
     const int64_t g = (int64_t)(s - 1) * a.steps + m;
     mcmc_propose<LPR>(
